@@ -2,7 +2,7 @@
 """Headline benchmark: log-likelihoods/sec of a Gaussian RAT-SPN (D=784, depth 2, 8 repetitions) on synthetic
 batches of 65536 samples per GPU, evaluated by the fused HIP kernel (leaf layer on the matrix cores).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 With N > 1 and no torch.distributed environment the script re-executes itself under torch.distributed.run (one
 process per GPU, RCCL); launched by torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
@@ -14,10 +14,12 @@ Inputs live in HBM before the timed region; a ring of >= 4 distinct batches (>= 
 cycled so that the x stream really comes from HBM.  For N > 1 the default is the metric's own reading, --scaling strong:
 65536 samples IN TOTAL, 65536 / N per rank, stepped through a sharded evaluation window captured
 as a HIP graph (deeprob.parallel.GraphedEvaluationWindow: the local evaluations and their one all-reduce in one graph
-launch -- a rank's shard kernel is shorter than the host's enqueue of it); the weak figure (65536 per rank) is measured
-in the same run and printed beside it (config.weak_scaling).  --scaling weak makes the weak figure the headline.
+launch -- a rank's shard kernel is shorter than the host's enqueue of it); with --full the weak figure (65536 per rank)
+is measured in the same run and printed beside it (config.other_scaling).  --scaling weak makes the weak figure the headline.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused whole-model forward: since round 5
+Prints ONE JSON line (rank 0).  A plain run measures the headline alone: set-up, warm-up, the K timed steps, the line.
+--dump-outputs DIR writes what the timed path handed its caller in its last step (dump_outputs).  Everything else below
+is measured only with --full.  `roofline` is for the dominant kernel (the fused whole-model forward: since round 5
 ratspn_gemm_slice_kernel, csrc/ratspn_gemm_slice.hip, from 8193 samples per launch): algorithmic bytes per launch = B * 4*(784 + C) (SURVEY 8d fully-fused bound) over its mean duration
 measured with HIP events on the launch stream inside the timed loop.  `cpu_baseline` times the oracle (op-for-op
 PyTorch-CPU restatement of the reference) on the host cores over a bounded sample of the same workload.  `secondary`
@@ -55,9 +57,15 @@ def parse():
     ap.add_argument('--rg-batch', type=int, default=2)
     ap.add_argument('--rg-sum', type=int, default=2)
     ap.add_argument('--ring', type=int, default=0, help='distinct resident batches (0: >= 4 and >= 768 MiB worth)')
-    ap.add_argument('--cpu-samples', type=int, default=262144, help='cpu_baseline sample size (0 = skip)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary configurations')
-    ap.add_argument('--no-kernel-events', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: roofline (kernel events), cpu_baseline, the '
+                         'secondary configurations, the frozen-model / fp32-exact / graphed-window figures, and for N > 1 '
+                         'the other scaling mode and BASELINE config 3; writes the verbose detail file')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0's shard for N > 1)")
+    ap.add_argument('--cpu-samples', type=int, default=262144, help='cpu_baseline sample size (0 = skip; --full)')
+    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary configurations (--full)')
+    ap.add_argument('--no-kernel-events', action='store_true', help='no roofline kernel events (--full)')
     ap.add_argument('--prewarm', type=int, default=384, help='untimed steps before the warm-up (runtime pool growth)')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend ('nccl' = RCCL; 'gloo' only to "
                     "rehearse the multi-rank path on a box with fewer GPUs than ranks)")
@@ -817,6 +825,25 @@ def write_detail(obj):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as DIR/<name>.npy, float64 arrays as float64, the rest as float32.  An array larger than
+    its share of `limit` is cut to a fixed, seeded sample of its rows (the same rows in every run), so that two builds
+    compare output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def headline_kernel_name(two_channel: bool, B: int) -> str:
     """The kernel a clean-evidence launch of B samples takes, from the LIBRARY's thresholds (dpk_ratspn_slice_batch_min /
     dpk_ratspn_small_batch_max), not from literals that can drift."""
@@ -937,7 +964,8 @@ def main():
         # process now and then on this stack, tests/test_parallel_nccl_gpu.py::_run_case: it stays alive to the end)
         _KEEP_ALIVE.append(win)
         del xs_g
-        return float(tt.item()), means[-1], L
+        last_ll = win.lanes[(L - 1) % len(win.lanes)].last_ll    # (the last step's per-sample LLs, written by every replay)
+        return float(tt.item()), means[-1], L, last_ll
 
     ring = args.ring or max(4, -(-(768 << 20) // (B * D * 4)))
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)  # every rank its own shard of the batch
@@ -947,7 +975,7 @@ def main():
     # (inside the launch); the frozen-model figure (static_params=True: the caller vouches) is printed beside it.
     evaluator = ShardedLogLikelihood(model, group=dist.group.WORLD if world > 1 else None, static_inputs=True,
                                      static_params=False)
-    time_kernel = not args.no_kernel_events
+    time_kernel = args.full and not args.no_kernel_events
     timer = KernelTimer()
     n_spare = 64   # event pairs for the untimed steps
     handles = [timer.pair() for _ in range(args.steps + n_spare)] if time_kernel else []
@@ -1015,6 +1043,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     mean_ll = results[-1]
+    # (per-sample LLs, mean LL) of the last timed step of the loop whose time is the headline: --dump-outputs
+    last_out = (evaluator.last_ll.cpu(), mean_ll) if args.dump_outputs else None
     eager_ms = dt / args.steps * 1e3
     step_mode = 'eager: one C call per step (host enqueue below the kernel time at this shard size)'
     weak_entry = None
@@ -1024,18 +1054,20 @@ def main():
         # that cannot be captured (a backend whose collective is not capturable) leaves the eager figure in place.
         try:
             with torch.no_grad():
-                dtg, mean_g, L = graphed_run(B, args.steps, args.warmup)
+                dtg, mean_g, L, ll_g = graphed_run(B, args.steps, args.warmup)
                 dt, mean_ll = dtg, mean_g
+                if args.dump_outputs:
+                    last_out = (ll_g.cpu(), mean_g)
                 step_mode = ('HIP graph: {} steps on {} parallel chains + their one all-reduce per replay (eager loop of the '
                              'same steps: {:.5f} ms/step)'.format(L, args.chains, eager_ms))
-                if world > 1:
+                if world > 1 and args.full:
                     Bo = plan['other_per_rank']
-                    dto, _, _ = graphed_run(Bo, args.steps, args.warmup)
+                    dto, _, _, _ = graphed_run(Bo, args.steps, args.warmup)
                     weak_entry = {'scaling': plan['other_scaling'], 'samples_per_gpu_per_step': Bo,
                                   'value': Bo * world * args.steps / dto, 'ms_per_step': dto / args.steps * 1e3}
                     # BASELINE config 3's own shape: 32768 samples per rank (262144 over 8 GPUs)
                     B3 = plan['config3_per_rank']
-                    dt3, _, _ = graphed_run(B3, args.steps, args.warmup)
+                    dt3, _, _, _ = graphed_run(B3, args.steps, args.warmup)
                     weak_entry['config3_32768_per_rank'] = {'global_batch': B3 * world, 'value': B3 * world * args.steps / dt3,
                                                             'ms_per_step': dt3 / args.steps * 1e3}
         except Exception as ex:
@@ -1085,6 +1117,9 @@ def main():
             one_stream_ms = dt / args.steps * 1e3
             if dt2 <= 1.15 * dt:
                 dt = dt2
+                if args.dump_outputs:
+                    last = (args.steps - 1) % ns
+                    last_out = (evs[last].last_ll.cpu(), means2[last][-1])
                 step_mode = ('eager: {} evaluation streams, alternate steps, a model replica each (single-stream loop of the '
                              'same steps: {:.5f} ms/step; roofline.kernel_ms comes from that loop)'.format(ns, one_stream_ms))
             else:
@@ -1111,7 +1146,7 @@ def main():
             return (time.perf_counter() - t1) / steps * 1e3
 
     ms_frozen = ms_exact = ms_graph_chains = None
-    if world == 1:
+    if world == 1 and args.full:
         if args.streams > 1:      # (--streams 1 = nothing but launches that have the chip to themselves: the profiled command)
             ms_graph_chains = _time_window(model, xs, reps=max(1, 24 // len(xs)), chains=CHAINS)
         ms_frozen = plain_loop(ShardedLogLikelihood(model, static_inputs=True, static_params=True), args.steps)
@@ -1177,9 +1212,9 @@ def main():
                            'slice kernel reads whole 100 KB blocks of 32 consecutive rows (64-byte pieces per request '
                            'lane quad); peak = the 8 TB/s specification'}
         threads = min(os.cpu_count() or 1, 32)
-        if args.cpu_samples > 0 and world == 1:
+        if args.full and args.cpu_samples > 0 and world == 1:
             out['cpu_baseline'], threads = cpu_baseline(cpu_state, D, args.cpu_samples)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 sec = secondary(dev, timer, threads, xs, model)
                 detail['secondary'] = sec
@@ -1189,11 +1224,13 @@ def main():
                 out['secondary_error'] = '{}: {}'.format(type(ex).__name__, ex)[:300]
                 import traceback
                 traceback.print_exc(file=sys.stderr)
-        out_path = write_detail(detail)
+        out_path = write_detail(detail) if args.full else None
         if out_path:
             out['detail_file'] = out_path
             if 'configs' in out:   # (keep `configs` the last key)
                 out['configs'] = out.pop('configs')
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'log_likelihoods': last_out[0].numpy(), 'mean_log_likelihood': [last_out[1]]})
         print(json.dumps(out), flush=True)
     if world > 1:
         # Every rank is past its last collective; the line is out.  The ranks leave WITHOUT tearing down the communicator

@@ -1,5 +1,6 @@
-"""The driver's contract on bench.py: one JSON line on stdout with the agreed keys, a roofline and a cpu_baseline block,
-internally consistent numbers.  A short run of the real script on the GPU (secondary configurations skipped)."""
+"""The driver's contract on bench.py: one JSON line on stdout with the agreed keys, a roofline and a cpu_baseline block
+with --full, internally consistent numbers; a plain run measures the headline alone and dumps its last step's outputs.
+Short runs of the real script on the GPU (secondary configurations skipped)."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _run(*flags, chatter=False):
 
 
 def test_bench_line_contract():
-    d = _run('--steps', '24', '--warmup', '4', '--prewarm', '32', '--no-secondary', '--cpu-samples', '4096')
+    d = _run('--full', '--steps', '24', '--warmup', '4', '--prewarm', '32', '--no-secondary', '--cpu-samples', '4096')
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
                 'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert key in d, key
@@ -59,3 +60,26 @@ def test_bench_two_rank_rehearsal_on_one_device():
     assert abs(d['value'] - 65536 / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
     assert d['step_mode'].startswith(('eager', 'HIP graph')) and abs(d['config']['mean_ll'] + 1430.6) < 1.0
     assert 'graphed window failed' in d['config']['step_mode'] or d['step_mode'] == 'HIP graph'
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain run: the headline keys, none of the --full measurements, --steps timed steps, and --dump-outputs writes the
+    last timed step's per-sample LLs and mean LL -- the same from run to run (seeded inputs)."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / 'run{}'.format(k)
+        d = _run('--steps', '24', '--warmup', '4', '--prewarm', '32', '--dump-outputs', str(out))
+        for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert key in d, key
+        for key in ('roofline', 'cpu_baseline', 'configs', 'secondary_error', 'detail_file'):
+            assert key not in d, key
+        assert d['steps'] == 24 and d['warmup'] == 4 and d['dtype'] == 'f32' and d['ms_per_step'] > 0
+        assert abs(d['value'] - d['config']['global_batch'] / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+        ll, mean = np.load(out / 'log_likelihoods.npy'), np.load(out / 'mean_log_likelihood.npy')
+        assert ll.dtype == np.float32 and ll.shape == (65536, 1) and np.isfinite(ll).all()
+        assert mean.dtype == np.float64 and mean.shape == (1,)
+        assert abs(ll.astype(np.float64).mean() - mean[0]) <= 1e-6 * abs(mean[0])
+        assert abs(mean[0] - d['config']['mean_ll']) <= 1e-6 * abs(mean[0]) and abs(mean[0] + 1430.6) < 1.0
+        dumps.append((ll, mean))
+    assert np.allclose(dumps[0][0], dumps[1][0], rtol=1e-6, atol=0) and np.allclose(dumps[0][1], dumps[1][1], rtol=1e-9)

@@ -195,3 +195,25 @@ def test_bench_multi_gpu_plan_names_the_shards():
     plan = bench.shard_plan(4, 65536, 'weak')
     assert plan['per_rank'] == 65536 and plan['global'] == 262144 and plan['other_per_rank'] == 16384
     assert 'all-reduce' not in bench.workload_string(2, 2, 65536, 1, 'nccl')
+
+
+def test_bench_dump_outputs_types_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, everything else is written as float32; an array over its share of
+    the size limit becomes the same seeded sample of its rows in every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ll = np.arange(4096 * 3, dtype=np.float32).reshape(4096, 3)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {'ll': ll, 'mean': [1.5], 'half': ll[:8].astype(np.float16)},
+                           limit=3 * 12 * 1000)
+    for k in range(2):
+        got = np.load(tmp_path / str(k) / 'll.npy')
+        assert got.dtype == np.float32 and got.shape == (1000, 3) and got.nbytes <= 12 * 1000
+        assert np.array_equal(got, ll[np.sort(got[:, 0].astype(np.int64) // 3)])     # whole rows, in order
+        assert np.array_equal(got, np.load(tmp_path / '0' / 'll.npy'))
+        mean = np.load(tmp_path / str(k) / 'mean.npy')
+        assert mean.dtype == np.float64 and mean.tolist() == [1.5]
+        half = np.load(tmp_path / str(k) / 'half.npy')
+        assert half.dtype == np.float32 and np.array_equal(half, ll[:8])

@@ -15,7 +15,7 @@ ENV = dict(os.environ, TMPDIR='/tmp')
 what = sys.argv[1] if len(sys.argv) > 1 else 'all'
 
 WORKLOADS = {   # name -> command (relative to the repo root)
-    'headline': ['python', 'bench.py', '--cpu-samples', '0', '--no-secondary'],
+    'headline': ['python', 'bench.py', '--full', '--cpu-samples', '0', '--no-secondary'],
     'config2': ['python', 'tools/bench_small.py', '--wide', '4096'],
     'marginal': ['python', 'tools/bench_small.py', '65536'],
     'wide': ['python', 'tools/bench_wide_small.py', '4096', '65536'],
@@ -73,7 +73,7 @@ def pmc(name, cmd, counter):
 if what in ('all', 'trace'):
     for name, cmd in WORKLOADS.items():
         kernel_trace(name, cmd)
-    r = subprocess.run(['python', os.path.join(ROOT, 'bench.py')], cwd=ROOT, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    r = subprocess.run(['python', os.path.join(ROOT, 'bench.py'), '--full'], cwd=ROOT, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     open(os.path.join(OUT, 'r03_bench_line.json'), 'wb').write(r.stdout.strip().splitlines()[-1] + b'\n' if r.stdout.strip() else b'')
 
 if what in ('all', 'pmc'):

@@ -16,7 +16,7 @@ what = sys.argv[1] if len(sys.argv) > 1 else 'all'
 only = sys.argv[2:]      # optional: workload names
 
 WORKLOADS = {   # name -> command (relative to the repo root)
-    'headline': ['python', 'bench.py', '--cpu-samples', '0', '--no-secondary'],
+    'headline': ['python', 'bench.py', '--full', '--cpu-samples', '0', '--no-secondary'],
     'config2': ['python', 'tools/bench_config2_modes.py', '4096'],
     'marginal': ['python', 'tools/bench_small.py', '65536'],
     'wide': ['python', 'tools/bench_wide_small.py', '4096', '65536'],
@@ -83,7 +83,7 @@ if what in ('all', 'trace'):
         kernel_trace(name, cmd)
     if only:
         sys.exit(0)
-    r = subprocess.run(['python', os.path.join(ROOT, 'bench.py')], cwd=ROOT, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    r = subprocess.run(['python', os.path.join(ROOT, 'bench.py'), '--full'], cwd=ROOT, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     open(os.path.join(OUT, 'r04_bench_line.json'), 'wb').write(r.stdout.strip().splitlines()[-1] + b'\n' if r.stdout.strip() else b'')
 
 if what in ('all', 'pmc'):
