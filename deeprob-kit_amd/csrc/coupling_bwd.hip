@@ -8,6 +8,7 @@
 // batches are hundreds of samples, so this route is correctness-first; the 64k-sample density path is the
 // fused forward kernel in coupling.hip.
 #include "common.h"
+#include "gemm_f32.h"
 #include <mutex>
 #include <type_traits>
 #include <math.h>
@@ -15,22 +16,6 @@
 namespace dpk {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct GemmArgs {
-    const float *A, *Bm;
-    float *C;
-    int M, N, K;
-    int64_t sam, sak, sbk, sbn, ldc;
-    const float *kscale;   // A(m,k) *= kscale[k]
-    const float *nscale;   // result(m,n) *= nscale[n]
-    const float *bias;     // + bias[n] (before relu)
-    const float *gate;     // result zeroed where gate[m*ldg + n] <= 0
-    int64_t ldg;
-    int relu, accumulate;
-    int ksplit, kchunk;    // > 1: blockIdx.z owns K range [z*kchunk, (z+1)*kchunk)
-    float *partials;       // split-K: [tile][slice][16][256] partial tiles; the last slice to finish a tile sums them in slice
-    unsigned *tickets;     // order and runs the epilogue ([tile] arrival counts, zero between launches).  Null: the partial
-};                         // sums meet by atomicAdd into a zeroed C and gemm_epilogue_kernel follows (fallback)
 
 constexpr int kGT = 64, kGK = 64;
 
@@ -261,7 +246,7 @@ static bool gemm_pool_take(int64_t floats, int tiles, float **p, unsigned **t, h
     return true;
 }
 
-static void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
+void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
     if (g_in.M <= 0 || g_in.N <= 0) return;
     GemmArgs g = g_in;
     const int tiles = cdiv(g.N, kGT) * cdiv(g.M, kGT);

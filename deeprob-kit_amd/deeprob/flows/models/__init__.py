@@ -1,2 +1,3 @@
 from .base import NormalizingFlow
 from .realnvp import RealNVP1d, RealNVP2d
+from .maf import MAF

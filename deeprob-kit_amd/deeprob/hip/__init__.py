@@ -218,6 +218,27 @@ SIGNATURES = {
     'dpk_flat_spn_workspace_bytes': (_i64, [_i64, _i32, _i32]),
     'dpk_flat_spn_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32] + [_c_void] * 11 +
                              [_i32, _c_void, _c_void, _c_void, _c_void, _c_void, _i64, _c_void]),
+    'dpk_maf_chain_workspace_bytes': (_i64, [_i64, _i32, _i32, _c_void, _i32]),
+    'dpk_maf_sample_deep_workspace_bytes': (_i64, [_i32, _i32, _c_void]),
+    'dpk_maf_sample_deep_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32] +
+                                    [_c_void] * 7 + [_i64, _c_void]),
+    'dpk_maf_conditioner_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32,
+                                                   _c_void, _c_void, _i64, _c_void]),
+    'dpk_maf_density_chain': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32, _c_void,
+                                             _c_void, _c_void, _c_void, _i64, _c_void]),
+    'dpk_maf_density_chain_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void,
+                                                      _i32, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
+                                                      _c_void, _c_void, _i32, _c_void, _i64, _c_void]),
+    'dpk_maf_density_workspace_bytes': (_i64, [_i32, _i32]),
+    'dpk_maf_density_forward': (ctypes.c_int, [_c_void, _i64, _i32] + [_c_void] * 6 + [_i32, _i32] + [_c_void] * 8 +
+                                [_i32, _c_void, _i64, _c_void]),
+    'dpk_maf_sample_workspace_bytes': (_i64, [_i32, _i32]),
+    'dpk_maf_sample_forward': (ctypes.c_int, [_c_void, _i64, _i32] + [_c_void] * 6 + [_i32, _i32] + [_c_void] * 4 +
+                               [_c_void, _i64, _c_void]),
+    'dpk_masked_linear_workspace_bytes': (_i64, [_i32, _i32]),
+    'dpk_masked_linear_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _c_void,
+                                                 _i64, _c_void]),
+    'dpk_masked_linear_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32] + [_c_void] * 7 + [_i64, _c_void]),
 }
 
 _lib = None

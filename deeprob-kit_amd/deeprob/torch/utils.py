@@ -1,6 +1,7 @@
 """Small torch helpers used by the flows (interface of deeprob/torch/utils.py:12-70)."""
 from typing import Union
 
+import numpy as np
 import torch
 from torch import nn
 from torch import optim
@@ -34,6 +35,23 @@ class ScaledTanh(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.weight * torch.tanh(x)
+
+
+class MaskedLinear(nn.Linear):
+    """``x (mask * weight)^T + bias`` (reference :73-96).  A real nn.Linear: construction draws the initial weight and bias
+    from torch's generator exactly as the reference does.  The product runs on the HIP conditioner op
+    (deeprob/hip/ops_maf.py); there is no F.linear route."""
+
+    def __init__(self, in_features: int, out_features: int, mask: np.ndarray):
+        """:raises ValueError: if the mask's shape is not (out_features, in_features)."""
+        super().__init__(in_features, out_features)
+        if mask.shape[0] != out_features or mask.shape[1] != in_features:
+            raise ValueError("Inconsistent mask shape")
+        self.register_buffer('mask', torch.tensor(mask, dtype=torch.float32))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from deeprob.hip import ops_maf
+        return ops_maf.masked_linear(x, self)
 
 
 class _WeightNormConvParameters(nn.Module):

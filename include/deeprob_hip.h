@@ -568,6 +568,8 @@ int dpk_profile_next_kernel(void *ev_start, void *ev_stop);
 #define DPK_KERNEL_COUPLING1D 3          /* dpk_coupling1d_forward, fused kernel                 */
 #define DPK_KERNEL_SPATIAL_PRODSUM 4     /* dpk_spatial_prodsum_forward                          */
 #define DPK_KERNEL_SPATIAL_SUMPRODROOT 5 /* dpk_spatial_sumprodroot_forward                      */
+#define DPK_KERNEL_MAF_DENSITY 6         /* dpk_maf_density_forward, fused kernel                */
+#define DPK_KERNEL_MAF_SAMPLE 7          /* dpk_maf_sample_forward, sampling kernel              */
 int dpk_profile_next_kernel_of(void *ev_start, void *ev_stop, int32_t kernel_id);
 
 /* torch.optim.Adam's update (the optimiser the reference's training loops build by name: torch/utils.py:32-49, stepped at
@@ -744,6 +746,75 @@ int dpk_coupling2d_transform_backward(const float *x, const float *z, const floa
                                       const float *dout, const float *dldj, float *dx, float *dz, double *dscale,
                                       void *stream);
 
+/* ---- Masked autoregressive flow (MAF): AutoregressiveLayer, deeprob/flows/layers/autoregressive.py:13-181 ----------
+ * A layer's conditioner is MaskedLinear (torch/utils.py:73-96: y = x (W * M)^T + b) layers with an activation between
+ * them (activation: 0 relu, 1 leaky-relu (0.01), 2 softplus (beta 1, threshold 20), 3 tanh, 4 sigmoid) and an output
+ * layer of 2D rows (translation t, then scale s).  W / M / b / grad_W / grad_b are host arrays of n_hidden + 1 device
+ * pointers; widths[l] (l < n_hidden) are the hidden widths.  act_weight: the ScaledTanh weight [1].
+ *
+ * Chained route (any depth and width): masked weights formed per call, one fp32-MFMA GEMM per layer.  The workspace
+ * holds the masked weights and every layer's activations; dpk_maf_chain_workspace_bytes(mode): 0 = what
+ * dpk_maf_conditioner_forward needs, 1 = dpk_maf_density_chain (+ Z), 2 = dpk_maf_density_chain_backward (+ the
+ * gradient buffers; a forward given a mode-2 workspace leaves in it what the backward reads).
+ * dpk_maf_conditioner_forward: Z [B, 2D] = network(x) (autoregressive.py:74).
+ * dpk_maf_density_chain: apply_backward (autoregressive.py:72-79), u = (x - t) exp(-s'), ildj = -sum s',
+ * s' = a tanh(s).  dpk_maf_density_chain_backward: its gradients w.r.t. x, every W (grad_W = M * (dOut^T In), what
+ * autograd of mask * weight gives), b and a (grad_act [1]); grad_Z != NULL instead differentiates
+ * dpk_maf_conditioner_forward (gradient of Z given; grad_act zeroed).  ws_holds_forward != 0: `ws` still holds what the
+ * forward call left for the same x and parameters (the conditioner is not evaluated again).  NULL grad_W[l] / grad_b[l]
+ * are skipped.                                                                                                       */
+int64_t dpk_maf_chain_workspace_bytes(int64_t B, int32_t D, int32_t n_hidden, const int32_t *widths, int32_t mode);
+int dpk_maf_conditioner_forward(const float *x, int64_t B, int32_t D, int32_t n_hidden, const float *const *W,
+                                const float *const *M, const float *const *b, const int32_t *widths, int32_t activation,
+                                float *Z, void *ws, int64_t ws_bytes, void *stream);
+int dpk_maf_density_chain(const float *x, int64_t B, int32_t D, int32_t n_hidden, const float *const *W,
+                          const float *const *M, const float *const *b, const int32_t *widths, int32_t activation,
+                          const float *act_weight, float *u, float *ildj, void *ws, int64_t ws_bytes, void *stream);
+int dpk_maf_density_chain_backward(const float *x, int64_t B, int32_t D, int32_t n_hidden, const float *const *W,
+                                   const float *const *M, const float *const *b, const int32_t *widths,
+                                   int32_t activation, const float *act_weight, const float *grad_u,
+                                   const float *grad_ildj, const float *grad_Z, float *grad_x, float *const *grad_W,
+                                   float *const *grad_b, float *grad_act, int32_t ws_holds_forward, void *ws,
+                                   int64_t ws_bytes, void *stream);
+/* Fused density kernel (autoregressive.py:72-79), depth 1, 1 <= units <= 256 (DPK_EUNSUPPORTED above), D >= 2: both
+ * GEMMs on the fp32 matrix cores, Z never written.  W1 / M1 [units, D], b1 [units], W2 / M2 [2D, units], b2 [2D].
+ * in_order [D] / hidden_order [units] / out_order [D]: the order in which inputs, hidden units and outputs are packed
+ * (a permutation each; sorted by degree, all-zero K blocks of a tile are skipped -- which blocks are zero is read from
+ * the live masks on every call).  in_scale / in_shift [D] or NULL: x' = x in_scale + in_shift is the layer's input (an
+ * eval-mode BatchNormLayer1d folded in front).  accumulate_ildj: ildj += instead of =.                            */
+int64_t dpk_maf_density_workspace_bytes(int32_t D, int32_t units);
+int dpk_maf_density_forward(const float *x, int64_t B, int32_t D, const float *W1, const float *M1, const float *b1,
+                            const float *W2, const float *M2, const float *b2, int32_t units, int32_t activation,
+                            const float *act_weight, const float *in_scale, const float *in_shift,
+                            const int32_t *in_order, const int32_t *hidden_order, const int32_t *out_order, float *u,
+                            float *ildj, int32_t accumulate_ildj, void *ws, int64_t ws_bytes, void *stream);
+/* Sampling kernel: apply_forward without autograd (autoregressive.py:81-99), depth 1, units <= 128
+ * (DPK_EUNSUPPORTED above), any masks: the D-step recurrence in one launch, variables produced in `order` [D]
+ * (the layer's inv_ordering).  x [B, D] = the sample, ldj [B] = sum s'.                                          */
+int64_t dpk_maf_sample_workspace_bytes(int32_t D, int32_t units);
+int dpk_maf_sample_forward(const float *u, int64_t B, int32_t D, const float *W1, const float *M1, const float *b1,
+                           const float *W2, const float *M2, const float *b2, int32_t units, int32_t activation,
+                           const float *act_weight, const int32_t *order, float *x, float *ldj, void *ws,
+                           int64_t ws_bytes, void *stream);
+/* The same for 2 .. 8 hidden layers of at most 512 units in all (DPK_EUNSUPPORTED beyond) whose masks are
+ * autoregressive in `order`: every hidden unit is final after a known step, and is propagated into the next layer once,
+ * at that step.  event_ptr [D + 2] / events: the host's schedule -- slot 0 lists the units final before the first step,
+ * slot p + 1 those that become final after step p, each as (hidden layer << 16) | unit, in increasing layer order
+ * (deeprob/hip/ops_maf.py derives it from the mask buffers).  W / M / b / widths as the chained route.            */
+int64_t dpk_maf_sample_deep_workspace_bytes(int32_t D, int32_t n_hidden, const int32_t *widths);
+int dpk_maf_sample_deep_forward(const float *u, int64_t B, int32_t D, int32_t n_hidden, const float *const *W,
+                                const float *const *M, const float *const *b, const int32_t *widths, int32_t activation,
+                                const float *act_weight, const int32_t *order, const int32_t *event_ptr,
+                                const int32_t *events, float *x, float *ldj, void *ws, int64_t ws_bytes, void *stream);
+
+/* MaskedLinear on its own (torch/utils.py:94-96): y [B, out] = x (W * M)^T + b (b may be NULL), and its backward
+ * (grad_x = grad_y (W * M), grad_W = M * (grad_y^T x), grad_b = column sums of grad_y; NULL outputs are skipped). */
+int64_t dpk_masked_linear_workspace_bytes(int32_t in_features, int32_t out_features);
+int dpk_masked_linear_forward(const float *x, int64_t B, int32_t in_features, int32_t out_features, const float *W,
+                              const float *M, const float *b, float *y, void *ws, int64_t ws_bytes, void *stream);
+int dpk_masked_linear_backward(const float *x, int64_t B, int32_t in_features, int32_t out_features, const float *W,
+                               const float *M, const float *grad_y, float *grad_x, float *grad_W, float *grad_b,
+                               void *ws, int64_t ws_bytes, void *stream);
 #ifdef __cplusplus
 }
 #endif
