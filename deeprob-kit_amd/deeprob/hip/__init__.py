@@ -218,6 +218,12 @@ SIGNATURES = {
     'dpk_flat_spn_workspace_bytes': (_i64, [_i64, _i32, _i32]),
     'dpk_flat_spn_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32] + [_c_void] * 11 +
                              [_i32, _c_void, _c_void, _c_void, _c_void, _c_void, _i64, _c_void]),
+    'dpk_flat_spn_topdown_workspace_bytes': (_i64, [_i64, _c_void]),
+    'dpk_flat_spn_topdown': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _i32, ctypes.c_uint64, _c_void, _i64, _c_void]),
+    'dpk_flat_spn_backward': (ctypes.c_int, [_c_void, _c_void, _i64, _c_void, _c_void]),
+    'dpk_flat_spn_em_step_workspace_bytes': (_i64, [_i64, _c_void]),
+    'dpk_flat_spn_em_step': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _i64, _c_void, ctypes.c_double, _c_void, _c_void,
+                                            _i64, _c_void]),
     'dpk_maf_chain_workspace_bytes': (_i64, [_i64, _i32, _i32, _c_void, _i32]),
     'dpk_maf_sample_deep_workspace_bytes': (_i64, [_i32, _i32, _c_void]),
     'dpk_maf_sample_deep_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32] +
@@ -240,6 +246,16 @@ SIGNATURES = {
                                                  _i64, _c_void]),
     'dpk_masked_linear_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32] + [_c_void] * 7 + [_i64, _c_void]),
 }
+
+
+
+class FlatSpnCircuit(ctypes.Structure):
+    """``dpk_flat_spn_circuit`` (include/deeprob_hip.h): sizes and device addresses of a flattened node-graph SPN."""
+    _fields_ = ([(k, _i32) for k in ('n_nodes', 'root', 'n_sum', 'n_vars', 'n_child', 'n_cat', 'n_slots', 'max_children')] +
+                [(k, _c_void) for k in ('order', 'kind', 'arg0', 'arg1', 'arg2', 'sum_index', 'child_index', 'child_slot',
+                                        'node_slot', 'cat_value', 'child_weight', 'child_logw', 'cat_logp', 'par0', 'par1',
+                                        'raw0', 'raw1', 'cat_prob')])
+
 
 _lib = None
 

@@ -664,6 +664,45 @@ int dpk_flat_spn_forward(const float *x, int64_t B, int32_t D, int32_t n_nodes, 
                          int32_t n_slots, const int32_t *node_slot, const int32_t *child_slot, float *out,
                          float *node_values, void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- vanilla SPN: MPE, sampling, log-gradients, EM (csrc/flat_spn_queries.hip) -----------------------------
+ * The circuit of dpk_flat_spn_forward as one record of device pointers and sizes, plus what the queries need:
+ *   sum_index [n_nodes]  position of a sum node among the sum nodes (0..n_sum-1), -1 for every other node
+ *   child_logw           float32 log of child_weight (parallel to it)
+ *   raw0 / raw1 [n_nodes] (double) the leaves' own parameters: Bernoulli p | Uniform start, width | Gaussian mean,
+ *                        stddev (par0 / par1 stay the derived values the forward pass reads)
+ *   cat_prob  [n_cat]    (double) the Categorical probabilities (cat_logp = float32 log of them)
+ *   n_vars = 1 + the largest variable id, n_child / n_cat = lengths of the child_* / cat_* arrays,
+ *   max_children = the largest child count of a sum node.
+ * The parameter arrays are written by dpk_flat_spn_em_step only.                                             */
+typedef struct dpk_flat_spn_circuit {
+    int32_t n_nodes, root, n_sum, n_vars, n_child, n_cat, n_slots, max_children;
+    const int32_t *order, *kind, *arg0, *arg1, *arg2, *sum_index;
+    const int32_t *child_index, *child_slot, *node_slot, *cat_value;
+    float *child_weight, *child_logw, *cat_logp;
+    double *par0, *par1, *raw0, *raw1, *cat_prob;
+} dpk_flat_spn_circuit;
+/* eval_top_down (deeprob/spn/algorithms/evaluation.py:99-177) in one launch, in place on x [B, D]: the NaN entries
+ * inside the circuit's scope are filled, nothing else is written.  mode 0 = mpe (inference.py:61-79, 106-126),
+ * mode 1 = sample (sampling.py:13-58, with the branch drawn from the exact posterior; counter based on `seed`, layout
+ * in the kernel file's header).  The node values live on chip when n_slots rows + 8 bytes per node + 64 bytes per
+ * sum node fit in 64 KB (workspace_bytes = 0); otherwise, or with n_slots = 0, in the workspace.  Both routes give
+ * the same output.  A sum node with more than 255 children is DPK_EUNSUPPORTED.                                */
+int64_t dpk_flat_spn_topdown_workspace_bytes(int64_t B, const dpk_flat_spn_circuit *c);
+int dpk_flat_spn_topdown(float *x, int64_t B, int32_t D, const dpk_flat_spn_circuit *c, int32_t mode, uint64_t seed,
+                         void *ws, int64_t ws_bytes, void *stream);
+/* eval_backward (gradient.py:13-63): lls [n_nodes, B] (the node_values of dpk_flat_spn_forward) -> grads
+ * [n_nodes, B] float32 log-gradients.                                                                        */
+int dpk_flat_spn_backward(const float *lls, float *grads, int64_t B, const dpk_flat_spn_circuit *c, void *stream);
+/* One iteration of batch EM (learning/em.py:84-107; node.py:100-111, leaf.py:167-174, 281-293, 536-545) on the B rows
+ * x[index[0..B-1]] of x [N, D]: the parameters in *c (raw and derived) are updated in place on the device with step
+ * size step_size in (0, 1); mean_ll (optional, one double) receives the batch mean of the root's log-likelihood
+ * before the update.  Statistics are summed in a fixed order in float64: the result is bitwise reproducible.
+ * Uniform leaves are left untouched.                                                                         */
+int64_t dpk_flat_spn_em_step_workspace_bytes(int64_t B, const dpk_flat_spn_circuit *c);
+int dpk_flat_spn_em_step(const float *x, int64_t N, int32_t D, const int32_t *index, int64_t B,
+                         const dpk_flat_spn_circuit *c, double step_size, double *mean_ll, void *ws, int64_t ws_bytes,
+                         void *stream);
+
 /* ---- RealNVP-2D evaluation path (density and sampling directions, running statistics) -----------
  * Conditioner convolutions (torch/utils.py:86-121 WeightNormConv2d inside flows/layers/resnet.py:9-90 and
  * flows/layers/densenet.py): NCHW fp32, kernel 1x1 or 3x3, stride 1, "same" zero padding.
