@@ -179,16 +179,16 @@ class LogitLayer(Bijector):
         parameters, so only an input that requires grad keeps the element-wise torch route."""
         if not (x.is_cuda and x.dtype == torch.float32) or (torch.is_grad_enabled() and x.requires_grad):
             return None
-        from deeprob.hip import load_library, check, ptr, stream_ptr
+        from deeprob.hip import load_library, call, ptr, stream_ptr
         xc = x.contiguous()
         n = xc.shape[0]
         out = torch.empty_like(xc)
         ldj = torch.empty(n, dtype=torch.float32, device=xc.device)
         if self._ldj_host is None:
             self._ldj_host = float(-np.prod(self.in_features) * np.log(1.0 - 2.0 * self.alpha))
-        check(load_library().dpk_logit1d_forward(ptr(xc), n, xc.numel() // max(n, 1) if n else 1, float(self.alpha),
+        call(load_library().dpk_logit1d_forward, ptr(xc), n, xc.numel() // max(n, 1) if n else 1, float(self.alpha),
                                                  self._ldj_host, int(inverse), ptr(out), ptr(ldj),
-                                                 stream_ptr(xc.device)), 'dpk_logit1d_forward')
+                                                 stream_ptr(xc.device))
         return out, ldj
 
     def apply_backward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

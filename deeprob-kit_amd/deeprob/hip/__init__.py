@@ -7,6 +7,7 @@ streams and ``torch.distributed`` only.
 """
 import ctypes
 import os
+import re
 from typing import Optional
 
 import torch
@@ -15,14 +16,97 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get(  # DEEPROB_HIP_LIB: measurement builds of the same ABI (profiles/README)
     'DEEPROB_HIP_LIB', os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_hip.so')))
 
-DPK_FLAG_STRUCT_CACHED = 1
-DPK_FLAG_UNIT_SCALE = 2
-DPK_FLAG_PARAMS_CACHED = 4
-DPK_FLAG_PARAMS_VERIFY = 8
-DPK_FLAG_IN_PIXEL_MAJOR = 16
-DPK_FLAG_OUT_PIXEL_MAJOR = 32
-DPK_FLAG_LL_SUM_SPREAD = 64
+
+class HipError(RuntimeError):
+    """Raised when the native library or its header is missing, or a C-ABI call reports a failure."""
+
+
+# ---- the C ABI: include/deeprob_hip.h is its only declaration -------------------------------------------------------
+# The prototypes, the DPK_* constants and the argument structs below are read from the header when this module is
+# imported; nothing of them is written down a second time.  The header is regular C: comments, `#define NAME value`,
+# `typedef struct { ... } name;` and one prototype per `;`.
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_hip.h'))
+
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32,
+            'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
+
+
+def _ctype(decl: str, named: bool, where: str):
+    """ctypes type of ``[const] type [*...] [name]``: every pointer is a ``c_void_p``, a scalar must be a known word."""
+    if '*' in decl:
+        return ctypes.c_void_p
+    words = re.sub(r'\bconst\b', ' ', decl).split()
+    if named and len(words) > 1:
+        words = words[:-1]
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise HipError("deeprob_hip.h: cannot read the type of '{}' in {}".format(decl.strip(), where))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text: str):
+    """``(signatures, constants, structs)`` of a header text: ``{name: (restype, argtypes)}``, ``{DPK_NAME: int}`` and
+    ``{struct name: [(field, ctype)]}``.  Raises HipError on anything it does not understand -- it never guesses."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    constants = {}
+    for m in re.finditer(r'^#define\s+(DPK_\w+)[ \t]+(.*)$', text, re.M):
+        value = re.fullmatch(r'\(?(-?\d+)u?\)?', m.group(2).strip())
+        if value is None:
+            raise HipError("deeprob_hip.h: cannot read the value '{}' of {}".format(m.group(2).strip(), m.group(1)))
+        constants[m.group(1)] = int(value.group(1))
+    text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
+    structs = {}
+    for m in re.finditer(r'typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;', text, re.S):
+        fields = []
+        for line in filter(None, (l.strip() for l in m.group(1).split(';'))):
+            first, *more = line.split(',')
+            base = re.sub(r'[\s\*]*\w+\s*$', '', first)          # the type words in front of the first declarator
+            for d in [first[len(base):]] + more:
+                fields.append((d.replace('*', '').strip(), _ctype(base + ' ' + d, True, 'struct ' + m.group(2))))
+        structs[m.group(2)] = fields
+    text = re.sub(r'typedef\s+struct\s*\w*\s*\{.*?\}\s*\w+\s*;', '', text, flags=re.S)
+    text = re.sub(r'extern\s+"C"\s*\{', '', text)
+    signatures = {}
+    for stmt in filter(None, (s.strip() for s in text.split(';'))):
+        if stmt == '}':            # (closes extern "C")
+            continue
+        m = re.fullmatch(r'(.+?)\b(dpk_\w+)\s*\((.*)\)', stmt, re.S)
+        if m is None:
+            raise HipError("deeprob_hip.h: not a prototype: '{}'".format(stmt))
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        if '*' in ret:
+            if re.sub(r'\s+', ' ', ret).strip() != 'const char *':
+                raise HipError("deeprob_hip.h: cannot read the return type '{}' of {}".format(ret.strip(), name))
+            restype = ctypes.c_char_p
+        else:
+            restype = _ctype(ret, False, name)
+        argtypes = [] if params == 'void' else [_ctype(p, True, name) for p in params.split(',')]
+        signatures[name] = (restype, argtypes)
+    return signatures, constants, structs
+
+
+def _read_header():
+    if not os.path.isfile(HEADER_PATH):
+        raise HipError("deeprob_hip.h not found at {} -- it is the declaration of the C ABI this binding is built "
+                       "from".format(HEADER_PATH))
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes) of every entry point; DPK_OK, DPK_E*, DPK_FLAG_*, DPK_KERNEL_* as module-level names
+SIGNATURES, CONSTANTS, _STRUCT_FIELDS = _read_header()
+globals().update(CONSTANTS)
 LL_SPREAD = 16            # partial sums in front of the count of a spread {sum LL, count} slot (17 doubles)
+
+
+def _struct(c_name: str, doc: str):
+    return type(c_name, (ctypes.Structure,), {'_fields_': _STRUCT_FIELDS[c_name], '__doc__': doc})
+
+
+FlatSpnCircuit = _struct('dpk_flat_spn_circuit', "sizes and device addresses of a flattened node-graph SPN")
+PairsTablesArgs = _struct('dpk_pairs_tables_args', "one layer of dpk_coupling1d_pairs_tables")
+BnFoldArgs = _struct('dpk_bn1d_fold_args', "one layer of dpk_bn1d_fold_many")
+SpatialTablesArgs = _struct('dpk_spatial_tables_args', "one level of dpk_spatial_tables")
+AdamTensor = _struct('dpk_adam_tensor', "one parameter tensor of dpk_adam_step")
 
 # What the operators pass when a module's cached tables were built from parameters whose addresses, shapes and version
 # counters are unchanged.  A write through ``param.data`` (hand-written optimisers, clipping, ``.data.copy_`` loaders)
@@ -39,229 +123,15 @@ def trust_version_counters(flag: bool = True) -> bool:
     return prev
 
 
+def trust_versions() -> bool:
+    return _trust_versions
+
+
 def cached_tables_flag() -> int:
     return DPK_FLAG_PARAMS_CACHED if _trust_versions else DPK_FLAG_PARAMS_VERIFY
 
-_c_void = ctypes.c_void_p
-_i64 = ctypes.c_int64
-_i32 = ctypes.c_int32
-_u32 = ctypes.c_uint32
-
-# name -> (restype, argtypes); mirrors include/deeprob_hip.h one to one
-SIGNATURES = {
-    'dpk_last_error': (ctypes.c_char_p, []),
-    'dpk_abi_version': (ctypes.c_int, []),
-    'dpk_workspace_forget': (ctypes.c_int, [_c_void, _i64]),
-    'dpk_ratspn_workspace_bytes': (_i64, [_i32] * 8),
-    'dpk_gaussian_leaf_forward_on_mfma': (ctypes.c_int, [_c_void, _c_void, _i32, _i32, _i32, _i32, _u32]),
-    'dpk_gaussian_leaf_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                 _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_bernoulli_leaf_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                                  _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_gaussian_leaf_backward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                                  _c_void, _i32, _i32, _i32, _c_void, _c_void, _c_void,
-                                                  _c_void, _i64, _u32, _c_void]),
-    'dpk_bernoulli_leaf_backward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                                   _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_bernoulli_leaf_backward_input': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                                         _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_product_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void]),
-    'dpk_product_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void]),
-    'dpk_sum_forward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _i64,
-                                       _c_void]),
-    'dpk_sum_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32,
-                                        _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_sum_workspace_bytes': (_i64, [_i64, _i32, _i32, _i32]),
-    'dpk_root_forward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _i32, _c_void, _c_void, _i64,
-                                        _c_void]),
-    'dpk_root_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _c_void,
-                                         _c_void, _c_void, _i64, _c_void]),
-    'dpk_ratspn_forward_on_mfma': (ctypes.c_int, [_c_void, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u32]),
-    'dpk_ratspn_small_batch_max': (_i64, [_i64]),
-    'dpk_ratspn_slice_batch_min': (_i64, [_i64]),
-    'dpk_ratspn_mfma_route': (_i32, [_i32]),
-    'dpk_spatial_leaf_fuse_min_k': (_i32, [_i32]),
-    'dpk_spatial_level_streams': (_i32, [_i32, _i64, _i32, _i32, _i32, _c_void, _i32, _c_void, _i32]),
-    'dpk_upper_tables_pair': (ctypes.c_int, [_c_void, _i32, _i32, _i32, _c_void, _i64, _c_void, _i32, _i32, _i32, _c_void, _i64,
-                                             _c_void]),
-    'dpk_prodsum_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32, _i32, _c_void,
-                                            _c_void, _c_void, _i64, _c_void]),
-    'dpk_ratspn_forward_train': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                                _i32, _i32, _i32, _i32, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                _c_void, _i64, _u32, _c_void]),
-    'dpk_ratspn_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                          _c_void, _c_void, _i32, _i32, _i32, _i32, _i32, _c_void, _c_void,
-                                          _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_coupling1d_workspace_bytes': (_i64, [_i32] * 4),
-    'dpk_coupling1d_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _i32, _i32, _c_void, _c_void,
-                                              _c_void, _c_void, _i32, _c_void, _c_void, _c_void, _i32, _i32,
-                                              _c_void, _c_void, _i32, _c_void, _i64, _c_void]),
-    'dpk_coupling1d_pairs_workspace_bytes': (_i64, [_i32, _i32]),
-    'dpk_coupling1d_pairs_logprob': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32,
-                                                    _c_void, _c_void, _c_void, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                    _c_void, _c_void, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_coupling1d_pairs_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32,
-                                                    _c_void, _c_void, _c_void, _i32, _i32, _c_void, _c_void, _i32,
-                                                    _c_void, _i64, _u32, _c_void]),
-    'dpk_bn1d_fold': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, ctypes.c_float, _i32, _i32, _c_void,
-                                     _c_void, _c_void, _c_void, _c_void, _i32, _c_void]),
-    'dpk_affine1d_forward': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _c_void, _c_void]),
-    'dpk_logit1d_forward': (ctypes.c_int, [_c_void, _i64, _i32, ctypes.c_float, ctypes.c_float, _i32, _c_void, _c_void,
-                                           _c_void]),
-    'dpk_conv2d_pack_floats': (_i64, [_i32] * 3),
-    'dpk_conv2d_prepare': (ctypes.c_int, [_c_void, _c_void, _i32, _i32, _i32, _c_void, _c_void, _c_void, _c_void,
-                                          ctypes.c_float, _c_void, _c_void, _c_void]),
-    'dpk_conv2d_forward': (ctypes.c_int, [_c_void, _i64, _i64, _i32, _i32, _i32, _c_void, _i32, _i32, _c_void, _c_void,
-                                          _c_void, _c_void, _i64, _c_void, _i64, _c_void]),
-    'dpk_coupling2d_transform': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32, _i32, _i32,
-                                                _i32, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_bn2d_bijector': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _c_void, ctypes.c_float, _i64, _i32, _i32,
-                                         _i32, _i32, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_space_to_depth': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _i32, _c_void, _c_void]),
-    'dpk_depth_to_space': (ctypes.c_int, [_c_void, _i32, _c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _c_void]),
-    'dpk_channel_stats': (ctypes.c_int, [_c_void, _i64, _i64, _i32, _i32, _i32, _i32, _c_void, _c_void]),
-    'dpk_channel_stats_backward': (ctypes.c_int, [_c_void, _i64, _i64, _i32, _i32, _i32, _c_void, _c_void, _c_void,
-                                                  _i32, _c_void, _c_void]),
-    'dpk_bn2d_fold_train': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, ctypes.c_float, ctypes.c_float,
-                                           _c_void, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_bn2d_fold_backward': (ctypes.c_int, [_c_void, _i32, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_channel_affine_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _c_void]),
-    'dpk_channel_affine_backward': (ctypes.c_int, [_c_void, _i64, _c_void, _i64, _i32, _i32, _i32, _c_void, _i32,
-                                                   _c_void, _c_void, _c_void, _c_void]),
-    'dpk_conv2d_backward_weight': (ctypes.c_int, [_c_void, _i64, _c_void, _i64, _i32, _i32, _i32, _i32, _i32, _c_void,
-                                                  _c_void, _c_void, _c_void]),
-    'dpk_coupling2d_transform_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32,
-                                                         _i32, _i32, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                                         _c_void]),
-    'dpk_normal_base_logprob': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                               _i64, _i32, _c_void, _c_void]),
-    'dpk_spatial_gaussian_forward': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _i32, _i32, _i32,
-                                                    _c_void, _c_void]),
-    'dpk_spatial_gaussian_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32,
-                                                     _i32, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_spatial_product_forward': (ctypes.c_int, [_c_void, _i64] + [_i32] * 15 + [_c_void, _c_void]),
-    'dpk_spatial_product_backward': (ctypes.c_int, [_c_void, _i64] + [_i32] * 15 + [_c_void, _c_void]),
-    'dpk_spatial_sum_workspace_bytes': (_i64, [_i32, _i32, _i32, _i32]),
-    'dpk_spatial_sum_forward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _i32, _i32, _i32, _c_void, _c_void,
-                                               _i64, _c_void]),
-    'dpk_spatial_sum_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32, _i32,
-                                                _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_spatial_prodsum_forward': (ctypes.c_int, [_c_void, _i64] + [_i32] * 13 + [_c_void, _i32, _c_void, _c_void,
-                                                                                  _i64, _u32, _c_void]),
-    'dpk_spatial_leaf_prodsum_forward': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64] + [_i32] * 14 + [_c_void, _i32, _c_void,
-                                                        _c_void, _i64, _u32, _c_void]),
-    'dpk_coupling1d_backward_workspace_bytes': (_i64, [_i64, _i32, _i32, _i32]),
-    'dpk_coupling1d_backward': (ctypes.c_int, [_c_void, _i64, _i32] + [_c_void] * 6 + [_i32, _c_void, _i32] +
-                                [_c_void] * 9 + [_i64, _c_void]),
-    'dpk_coupling1d_mlp_workspace_bytes': (_i64, [_i64, _i32, _c_void, _i32]),
-    'dpk_coupling1d_mlp_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _i32, _c_void, _c_void, _c_void,
-                                                  _c_void, _i32, _i32, _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_coupling1d_mlp_backward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _i32, _c_void, _c_void,
-                                                   _c_void, _c_void, _i32, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                                   _c_void, _i32, _c_void, _i64, _c_void]),
-    'dpk_coupling1d_mlp_backward_inverse': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _i32, _c_void, _c_void,
-                                                           _c_void, _c_void, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                           _c_void, _c_void, _i32, _c_void, _i64, _c_void]),
-    'dpk_bn1d_inverse_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                                 ctypes.c_float, _c_void, _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_bn1d_train_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void, ctypes.c_float,
-                                              ctypes.c_float, _c_void, _c_void, _c_void, _c_void, _c_void, _i64,
-                                              _c_void]),
-    'dpk_bn1d_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void,
-                                         ctypes.c_float, _i32, _c_void, _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_bn1d_local_moments': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void]),
-    'dpk_bn1d_sync_forward': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _c_void, _c_void, _i32, _c_void, _c_void,
-                                             ctypes.c_float, ctypes.c_float, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                             _i64, _c_void]),
-    'dpk_bn1d_backward_sums': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _c_void, _c_void, ctypes.c_float,
-                                              _c_void, _c_void]),
-    'dpk_bn1d_sync_backward': (ctypes.c_int, [_c_void, _c_void, _i64, _i64, _i32, _c_void, _c_void, _c_void,
-                                              ctypes.c_float, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void]),
-    'dpk_normal_base_backward': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _c_void, _c_void]),
-    'dpk_leaf_forward_dropout': (ctypes.c_int, [_i32, _c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void, _i32, _i32,
-                                                _i32, ctypes.c_float, ctypes.c_uint64, _c_void, _c_void]),
-    'dpk_leaf_backward_dropout': (ctypes.c_int, [_i32, _c_void, _c_void, _i64, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                 _i32, _i32, _i32, ctypes.c_float, ctypes.c_uint64, _c_void, _c_void,
-                                                 _c_void, _c_void, _i64, ctypes.c_uint32, _c_void]),
-    'dpk_spatial_gaussian_forward_dropout': (ctypes.c_int, [_c_void, _c_void, _c_void, _i64, _i32, _i32, _i32, _i32,
-                                                            ctypes.c_float, ctypes.c_uint64, _c_void, _c_void]),
-    'dpk_spatial_gaussian_backward_dropout': (ctypes.c_int, [_c_void, _c_void, _c_void, _c_void, _i64, _i32, _i32, _i32,
-                                                             _i32, ctypes.c_float, ctypes.c_uint64, _c_void, _c_void,
-                                                             _c_void, _c_void]),
-    'dpk_dropout_fill': (ctypes.c_int, [_c_void, _i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_float, _c_void,
-                                        _c_void]),
-    'dpk_spatial_prodroot_workspace_bytes': (_i64, [_i32, _i32, _i32, _i32]),
-    'dpk_spatial_prodroot_forward': (ctypes.c_int, [_c_void, _i64] + [_i32] * 13 + [_c_void, _i32, _c_void, _c_void,
-                                                                                   _i64, _c_void]),
-    'dpk_prodsum_workspace_bytes': (_i64, [_i32, _i32, _i32]),
-    'dpk_prodsum_forward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_prodroot_forward': (ctypes.c_int, [_c_void, _c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_ratspn_topdown': (ctypes.c_int, [_i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_void, _c_void,
-                                          _c_void, _c_void, _c_void, _c_void, _c_void, ctypes.c_uint64, _c_void, _c_void, _c_void]),
-    'dpk_profile_next_kernel': (ctypes.c_int, [_c_void, _c_void]),
-    'dpk_profile_next_kernel_of': (ctypes.c_int, [_c_void, _c_void, _i32]),
-    'dpk_ll_accumulate': (ctypes.c_int, [_c_void, _i64, _c_void, _c_void]),
-    'dpk_neg_mean_forward': (ctypes.c_int, [_c_void, _i64, _c_void, _c_void]),
-    'dpk_neg_mean_backward': (ctypes.c_int, [_c_void, _i64, _c_void, _c_void]),
-    'dpk_adam_step': (ctypes.c_int, [_i32, _c_void, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                     ctypes.c_float, _i32, _c_void, _c_void, _c_void]),
-    'dpk_spatial_prodsum_backward': (ctypes.c_int, [_c_void, _i64] + [_i32] * 13 + [_c_void, _i32, _c_void, _c_void,
-                                                                                   _c_void, _c_void, _c_void, _c_void, _i64,
-                                                                                   _u32, _c_void]),
-    'dpk_spatial_sumprodroot_workspace_bytes': (_i64, [_i32] * 7),
-    'dpk_spatial_sumprodroot_workspace_bytes_batch': (_i64, [_i64, _i32, _i32, _i32, _c_void, _i32, _c_void, _i32]),
-    'dpk_spatial_sumprodroot_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32, _c_void, _c_void, _i32, _c_void,
-                                                       _c_void, _i32, _c_void, _c_void, _i64, _u32, _c_void]),
-    'dpk_spatial_tables': (ctypes.c_int, [_i32, _c_void, _c_void]),
-    'dpk_bn1d_fold_many': (ctypes.c_int, [_i32, _c_void, _c_void, _c_void]),
-    'dpk_coupling1d_pairs_tables': (ctypes.c_int, [_i32, _c_void, _c_void]),
-    'dpk_flat_spn_workspace_bytes': (_i64, [_i64, _i32, _i32]),
-    'dpk_flat_spn_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _i32] + [_c_void] * 11 +
-                             [_i32, _c_void, _c_void, _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_flat_spn_topdown_workspace_bytes': (_i64, [_i64, _c_void]),
-    'dpk_flat_spn_topdown': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _i32, ctypes.c_uint64, _c_void, _i64, _c_void]),
-    'dpk_flat_spn_backward': (ctypes.c_int, [_c_void, _c_void, _i64, _c_void, _c_void]),
-    'dpk_flat_spn_em_step_workspace_bytes': (_i64, [_i64, _c_void]),
-    'dpk_flat_spn_em_step': (ctypes.c_int, [_c_void, _i64, _i32, _c_void, _i64, _c_void, ctypes.c_double, _c_void, _c_void,
-                                            _i64, _c_void]),
-    'dpk_maf_chain_workspace_bytes': (_i64, [_i64, _i32, _i32, _c_void, _i32]),
-    'dpk_maf_sample_deep_workspace_bytes': (_i64, [_i32, _i32, _c_void]),
-    'dpk_maf_sample_deep_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32] +
-                                    [_c_void] * 7 + [_i64, _c_void]),
-    'dpk_maf_conditioner_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32,
-                                                   _c_void, _c_void, _i64, _c_void]),
-    'dpk_maf_density_chain': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _i32, _c_void,
-                                             _c_void, _c_void, _c_void, _i64, _c_void]),
-    'dpk_maf_density_chain_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void,
-                                                      _i32, _c_void, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                                      _c_void, _c_void, _i32, _c_void, _i64, _c_void]),
-    'dpk_maf_density_workspace_bytes': (_i64, [_i32, _i32]),
-    'dpk_maf_density_forward': (ctypes.c_int, [_c_void, _i64, _i32] + [_c_void] * 6 + [_i32, _i32] + [_c_void] * 8 +
-                                [_i32, _c_void, _i64, _c_void]),
-    'dpk_maf_sample_workspace_bytes': (_i64, [_i32, _i32]),
-    'dpk_maf_sample_forward': (ctypes.c_int, [_c_void, _i64, _i32] + [_c_void] * 6 + [_i32, _i32] + [_c_void] * 4 +
-                               [_c_void, _i64, _c_void]),
-    'dpk_masked_linear_workspace_bytes': (_i64, [_i32, _i32]),
-    'dpk_masked_linear_forward': (ctypes.c_int, [_c_void, _i64, _i32, _i32, _c_void, _c_void, _c_void, _c_void, _c_void,
-                                                 _i64, _c_void]),
-    'dpk_masked_linear_backward': (ctypes.c_int, [_c_void, _i64, _i32, _i32] + [_c_void] * 7 + [_i64, _c_void]),
-}
-
-
-
-class FlatSpnCircuit(ctypes.Structure):
-    """``dpk_flat_spn_circuit`` (include/deeprob_hip.h): sizes and device addresses of a flattened node-graph SPN."""
-    _fields_ = ([(k, _i32) for k in ('n_nodes', 'root', 'n_sum', 'n_vars', 'n_child', 'n_cat', 'n_slots', 'max_children')] +
-                [(k, _c_void) for k in ('order', 'kind', 'arg0', 'arg1', 'arg2', 'sum_index', 'child_index', 'child_slot',
-                                        'node_slot', 'cat_value', 'child_weight', 'child_logw', 'cat_logp', 'par0', 'par1',
-                                        'raw0', 'raw1', 'cat_prob')])
-
 
 _lib = None
-
-
-class HipError(RuntimeError):
-    """Raised when the native library is missing or a C-ABI call reports a failure."""
 
 
 def load_library() -> ctypes.CDLL:
@@ -288,14 +158,21 @@ def load_library() -> ctypes.CDLL:
     return lib
 
 
-def check(rc: int, what: str):
-    if rc != 0:
+def check(rc: int, fn):
+    """Raise ``HipError("<name> failed (<rc>): <last error>")`` for the negative result ``rc`` of entry point ``fn``."""
+    if rc < 0:
         msg = load_library().dpk_last_error()
-        raise HipError("{} failed ({}): {}".format(what, rc, msg.decode() if msg else ''))
+        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
 
 
-def is_unsupported(rc: int) -> bool:
-    return rc == -4
+def call(fn, *args) -> int:
+    """``fn(*args)`` for an entry point that returns a status or a ``*_workspace_bytes`` size: the (non-negative) result,
+    HipError on a negative one.  The routing calls that read DPK_EUNSUPPORTED as "take the other route", and the knobs
+    whose negative results are values, call ``fn`` itself and get the raw code."""
+    rc = fn(*args)
+    if rc < 0:
+        check(rc, fn)
+    return rc
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -321,13 +198,58 @@ def require_device_f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def tensors_key(*tensors) -> tuple:
+    """These tensors as they are now -- address, version counter, shape (None stays None): what cached tables are keyed
+    on.  A write through ``.data`` moves none of the three: see ``cached_tables_flag``."""
+    return tuple(None if t is None else (t.data_ptr(), t._version, tuple(t.shape)) for t in tensors)
+
+
+# ---- one batched table pass per model forward --------------------------------------------------------------------
+# DgcSpn.forward (ops_spatial.tables_prepare) and NormalizingFlow's fused forward (ops_flows.flow1d_prepare) rebuild or
+# verify the tables of all their layers in one or two launches and mark what they covered with the forward's token; the
+# per-layer operators recognise the token while it is in force and pass DPK_FLAG_PARAMS_CACHED.  Forwards do not nest,
+# so one token is in force at a time.
+_prepare_token = None
+
+
+def prepare_begin() -> object:
+    """Ends the previous pass; the token of a new one, in force from ``prepare_commit`` (after its launches succeeded)."""
+    global _prepare_token
+    _prepare_token = None
+    return object()
+
+
+def prepare_commit(token):
+    global _prepare_token
+    _prepare_token = token
+
+
+def prepare_release():
+    global _prepare_token
+    _prepare_token = None
+
+
+def prepared(token) -> bool:
+    """Whether ``token`` (what a batched pass marked an object with) is the pass in force."""
+    return token is not None and token is _prepare_token
+
+
 class Workspace:
-    """A growable device scratch buffer owned by a module (never shared between streams)."""
+    """A growable device scratch buffer owned by a module (never shared between streams), and the module's belief about
+    the tables the kernels keep in it -- the cached-table protocol of every fused entry point:
+
+    1. the caller forms a key for "the tables built from these tensors" (``tensors_key`` plus route / mode words);
+    2. ``tables_flag(key)`` gives the flag to pass (0: build them) and records the key;
+    3. ``outcome(rc, fn, out)`` maps the call's result to *out / None / raise* and forgets the tables after a failure;
+    4. an operator that lays other tables over the buffer calls ``forget_tables()`` first; a replaced buffer forgets
+       everything."""
 
     def __init__(self):
         self.buf: Optional[torch.Tensor] = None
         self.struct_key = None  # what the cached structure tables were built from
-        self.params_key = None  # parameters (addresses, versions) the MFMA route's tables were built from
+        self.params_key = None  # what the cached parameter tables were built from
+        self._prep_token = None  # the batched pass (see prepare_begin) that last rebuilt / verified the parameter tables ...
+        self._prep_key = None    # ... and the key it did so for
         self._retired = []      # outgrown buffers: a captured HIP graph may still address them
 
     def __del__(self):
@@ -349,3 +271,64 @@ class Workspace:
             self.struct_key = None
             self.params_key = None
         return self.buf
+
+    def sized(self, size_fn, *args, device, or_none: bool = False) -> Optional[torch.Tensor]:
+        """The buffer, at least ``size_fn(*args)`` bytes (a ``*_workspace_bytes`` entry point).  A negative size raises;
+        with ``or_none`` it means "outside this kernel's envelope" and gives None (the caller takes another route)."""
+        n = size_fn(*args)
+        if n < 0:
+            if or_none:
+                return None
+            check(n, size_fn)
+        return self.get(n, device)
+
+    def structure_flag(self, key) -> int:
+        """DPK_FLAG_STRUCT_CACHED when the structure tables were built from ``key``; records it."""
+        flag = DPK_FLAG_STRUCT_CACHED if self.struct_key == key else 0
+        self.struct_key = key
+        return flag
+
+    def holds_tables(self, key) -> bool:
+        return self.params_key == key
+
+    def tables_flag(self, key, rebuilt: bool = False) -> int:
+        """The flag for a call whose parameter tables are keyed by ``key``: DPK_FLAG_PARAMS_CACHED when this forward's
+        batched pass covered them, ``cached_tables_flag()`` when an earlier call built them from the same key, else 0 and
+        the key is recorded.  ``rebuilt``: the call rebuilds them whatever is there (its structure tables changed)."""
+        if self._prep_token is not None and self._prep_token is _prepare_token and self._prep_key == key:
+            return DPK_FLAG_PARAMS_CACHED
+        if self.params_key == key and not rebuilt:
+            return cached_tables_flag()
+        self.params_key = key
+        return 0
+
+    def tables_built(self, key, token=None):
+        """A launch that SUCCEEDED built the tables for ``key`` (record it only then); ``token``: as part of that batched pass."""
+        self.params_key = key
+        if token is not None:
+            self._prep_token, self._prep_key = token, key
+
+    def forget_tables(self):
+        self.params_key = None
+
+    def forget_prepared(self):
+        self.params_key = None
+        self._prep_token = None
+
+    def forget_structure(self):
+        """The structure tables and, built on them, the parameter tables."""
+        self.struct_key = None
+        self.params_key = None
+
+    def outcome(self, rc: int, fn, out, forget_structure: bool = False):
+        """Result of a fused call ``rc = fn(...)`` on this workspace: ``out`` when it ran; None for DPK_EUNSUPPORTED (the
+        caller takes the per-layer route); HipError otherwise.  Any failure forgets the parameter tables (a failed call
+        built nothing), DPK_EUNSUPPORTED on request the structure tables too."""
+        if rc == 0:
+            return out
+        self.params_key = None
+        if rc == DPK_EUNSUPPORTED:
+            if forget_structure:
+                self.struct_key = None
+            return None
+        check(rc, fn)

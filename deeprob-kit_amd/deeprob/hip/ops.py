@@ -9,13 +9,10 @@ from typing import Optional, Tuple
 import torch
 
 from deeprob.hip import (
-    load_library, check, ptr, stream_ptr, require_device_f32, Workspace, HipError, DPK_FLAG_STRUCT_CACHED,
-    DPK_FLAG_UNIT_SCALE, DPK_FLAG_PARAMS_CACHED, DPK_FLAG_LL_SUM_SPREAD, LL_SPREAD, cached_tables_flag,
+    load_library, call, check, ptr, stream_ptr, require_device_f32, Workspace, HipError, DPK_EUNSUPPORTED,
+    DPK_FLAG_STRUCT_CACHED, DPK_FLAG_UNIT_SCALE, DPK_FLAG_PARAMS_CACHED, DPK_FLAG_LL_SUM_SPREAD, LL_SPREAD, tensors_key,
+    trust_versions,
 )
-
-
-def _buffers_key(*tensors) -> tuple:
-    return tuple((t.data_ptr(), t._version, tuple(t.shape)) if t is not None else None for t in tensors)
 
 
 class LeafContext:
@@ -29,33 +26,30 @@ class LeafContext:
 
     def workspace(self, device, mask, pad_mask, scale=None) -> Tuple[torch.Tensor, int]:
         lib = load_library()
-        n = lib.dpk_ratspn_workspace_bytes(self.D, self.R, self.d, self.I, self.depth, self.reps,
-                                           max(self.S, 1), max(self.C, 1))
-        if n < 0:
-            check(int(n), 'dpk_ratspn_workspace_bytes')
-        buf = self.ws.get(n, device)
-        key = _buffers_key(mask, pad_mask)
-        flags = DPK_FLAG_STRUCT_CACHED if self.ws.struct_key == key else 0
-        self.ws.struct_key = key
+        buf = self.ws.sized(lib.dpk_ratspn_workspace_bytes, self.D, self.R, self.d, self.I, self.depth, self.reps,
+                            max(self.S, 1), max(self.C, 1), device=device)
+        flags = self.ws.structure_flag(tensors_key(mask, pad_mask))
         # a frozen scale parameter is the reference's "scale == 1" configuration (optimize_scale=False);
         # only a hint: the kernels verify it on the device
         if scale is not None and not scale.requires_grad:
             flags |= DPK_FLAG_UNIT_SCALE
         return buf, flags
 
+    def fused_probe(self, x_ptr) -> tuple:
+        """Arguments of ``dpk_ratspn_forward_on_mfma`` in front of the flags."""
+        return (x_ptr, self.D, self.depth, self.reps, self.I, self.S, self.C, 0)
 
-def _params_flag(lib, lctx: 'LeafContext', x_ptr, flags: int, tensors) -> int:
-    """The cached-tables flag (``hip.cached_tables_flag``: checked on the device by default) when this fused call runs
-    on the MFMA route and the tables in the workspace were built by an earlier call on that route from parameters at the
-    same addresses with the same version counters (a structure rebuild invalidates them too)."""
-    if not lib.dpk_ratspn_forward_on_mfma(x_ptr, lctx.D, lctx.depth, lctx.reps, lctx.I, lctx.S, lctx.C, 0, flags):
-        lctx.ws.params_key = None
+
+def _params_flag(lctx: 'LeafContext', on_mfma, probe: tuple, flags: int, tensors) -> int:
+    """The cached-tables flag (``hip.cached_tables_flag``: checked on the device by default) when this call runs on the
+    MFMA route (the library's answer: ``on_mfma(*probe, flags)``) and the tables in the workspace were built by an earlier
+    call on that route from parameters at the same addresses with the same version counters (a structure rebuild
+    invalidates them too).  Every other route lays its own tables over them."""
+    ws = lctx.ws
+    if not on_mfma(*probe, flags):
+        ws.forget_tables()
         return 0
-    key = (_buffers_key(*tensors), lctx.ws.struct_key)
-    if lctx.ws.params_key == key and (flags & DPK_FLAG_STRUCT_CACHED):
-        return cached_tables_flag()
-    lctx.ws.params_key = key
-    return 0
+    return ws.tables_flag((tensors_key(*tensors), ws.struct_key), rebuilt=not (flags & DPK_FLAG_STRUCT_CACHED))
 
 
 def _pad_u8(pad_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -75,17 +69,12 @@ class GaussianLeafFn(torch.autograd.Function):
         out = torch.empty((B, lctx.R, lctx.I), dtype=torch.float32, device=x.device)
         pad = _pad_u8(pad_mask)
         ws, flags = lctx.workspace(x.device, mask, pad_mask, scale)
-        if lib.dpk_gaussian_leaf_forward_on_mfma(ptr(x), ptr(out), lctx.D, lctx.R, lctx.I, lctx.d, flags):
-            # MFMA route: its parameter tables survive between calls while loc / scale are unchanged
-            key = (_buffers_key(loc_c, scale_c), lctx.ws.struct_key)
-            if lctx.ws.params_key == key and (flags & DPK_FLAG_STRUCT_CACHED):
-                flags |= cached_tables_flag()
-            lctx.ws.params_key = key
-        else:
-            lctx.ws.params_key = None
-        check(lib.dpk_gaussian_leaf_forward(ptr(x), B, lctx.D, ptr(mask), ptr(pad), ptr(loc_c), ptr(scale_c),
+        # (MFMA route: its parameter tables survive between calls while loc / scale are unchanged)
+        flags |= _params_flag(lctx, lib.dpk_gaussian_leaf_forward_on_mfma, (ptr(x), ptr(out), lctx.D, lctx.R, lctx.I, lctx.d),
+                              flags, [loc_c, scale_c])
+        call(lib.dpk_gaussian_leaf_forward, ptr(x), B, lctx.D, ptr(mask), ptr(pad), ptr(loc_c), ptr(scale_c),
                                             lctx.R, lctx.I, lctx.d, ptr(out), ptr(ws), ws.numel(), flags,
-                                            stream_ptr(x.device)), 'dpk_gaussian_leaf_forward')
+                                            stream_ptr(x.device))
         ctx.save_for_backward(x, loc_c, scale_c, mask, pad_mask)
         ctx.lctx = lctx
         return out
@@ -101,10 +90,10 @@ class GaussianLeafFn(torch.autograd.Function):
         gloc = torch.empty_like(loc) if need_loc else None
         gscale = torch.empty_like(scale) if need_scale else None
         ws, flags = lctx.workspace(x.device, mask, pad_mask)
-        check(lib.dpk_gaussian_leaf_backward(ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
+        call(lib.dpk_gaussian_leaf_backward, ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
                                              ptr(_pad_u8(pad_mask)), ptr(loc), ptr(scale), lctx.R, lctx.I,
                                              lctx.d, ptr(gloc), ptr(gscale), ptr(gx), ptr(ws), ws.numel(),
-                                             flags, stream_ptr(x.device)), 'dpk_gaussian_leaf_backward')
+                                             flags, stream_ptr(x.device))
         return gx, gloc, gscale, None, None, None
 
 
@@ -119,10 +108,9 @@ class BernoulliLeafFn(torch.autograd.Function):
         B = x.shape[0]
         out = torch.empty((B, lctx.R, lctx.I), dtype=torch.float32, device=x.device)
         ws, flags = lctx.workspace(x.device, mask, pad_mask)
-        check(lib.dpk_bernoulli_leaf_forward(ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
+        call(lib.dpk_bernoulli_leaf_forward, ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
                                              ptr(logits_c), lctx.R, lctx.I, lctx.d, ptr(out), ptr(ws),
-                                             ws.numel(), flags, stream_ptr(x.device)),
-              'dpk_bernoulli_leaf_forward')
+                                             ws.numel(), flags, stream_ptr(x.device))
         ctx.save_for_backward(x, logits_c, mask, pad_mask)
         ctx.lctx = lctx
         return out
@@ -135,17 +123,16 @@ class BernoulliLeafFn(torch.autograd.Function):
         g = require_device_f32(g, 'grad')
         glog = torch.empty_like(logits) if ctx.needs_input_grad[1] else None
         ws, flags = lctx.workspace(x.device, mask, pad_mask)
-        check(lib.dpk_bernoulli_leaf_backward(ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
+        call(lib.dpk_bernoulli_leaf_backward, ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
                                               ptr(_pad_u8(pad_mask)), ptr(logits), lctx.R, lctx.I, lctx.d,
-                                              ptr(glog), ptr(ws), ws.numel(), flags, stream_ptr(x.device)),
-              'dpk_bernoulli_leaf_backward')
+                                              ptr(glog), ptr(ws), ws.numel(), flags, stream_ptr(x.device))
         gx = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            check(lib.dpk_bernoulli_leaf_backward_input(ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
+            call(lib.dpk_bernoulli_leaf_backward_input, ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask),
                                                         ptr(_pad_u8(pad_mask)), ptr(logits), lctx.R, lctx.I, lctx.d,
                                                         ptr(gx), ptr(ws), ws.numel(), flags | DPK_FLAG_STRUCT_CACHED,
-                                                        stream_ptr(x.device)), 'dpk_bernoulli_leaf_backward_input')
+                                                        stream_ptr(x.device))
         return gx, glog, None, None, None
 
 
@@ -166,9 +153,9 @@ class LeafDropoutFn(torch.autograd.Function):
         p1_c = require_device_f32(p1, 'scale') if p1 is not None else None
         B = x.shape[0]
         out = torch.empty((B, lctx.R, lctx.I), dtype=torch.float32, device=x.device)
-        check(lib.dpk_leaf_forward_dropout(dist, ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)), ptr(p0_c),
+        call(lib.dpk_leaf_forward_dropout, dist, ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)), ptr(p0_c),
                                            ptr(p1_c), lctx.R, lctx.I, lctx.d, float(rate), seed, ptr(out),
-                                           stream_ptr(x.device)), 'dpk_leaf_forward_dropout')
+                                           stream_ptr(x.device))
         ctx.save_for_backward(x, p0_c, p1_c, mask, pad_mask)
         ctx.meta = (lctx, dist, float(rate), seed)
         return out
@@ -185,10 +172,9 @@ class LeafDropoutFn(torch.autograd.Function):
         g0 = torch.empty_like(p0) if ctx.needs_input_grad[1] else None
         g1 = torch.empty_like(p1) if (p1 is not None and ctx.needs_input_grad[2]) else None
         ws, flags = lctx.workspace(x.device, mask, pad_mask)
-        check(lib.dpk_leaf_backward_dropout(dist, ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
+        call(lib.dpk_leaf_backward_dropout, dist, ptr(x), ptr(g), x.shape[0], lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
                                             ptr(p0), ptr(p1), lctx.R, lctx.I, lctx.d, rate, seed, ptr(g0), ptr(g1),
-                                            ptr(gx), ptr(ws), ws.numel(), flags, stream_ptr(x.device)),
-              'dpk_leaf_backward_dropout')
+                                            ptr(gx), ptr(ws), ws.numel(), flags, stream_ptr(x.device))
         return gx, g0, g1, None, None, None, None, None, None
 
 
@@ -201,8 +187,7 @@ class DropoutFillFn(torch.autograd.Function):
         lib = load_library()
         x = require_device_f32(x, 'x')
         out = torch.empty_like(x)
-        check(lib.dpk_dropout_fill(ptr(x), x.numel(), float(rate), seed, float('-inf'), ptr(out), stream_ptr(x.device)),
-              'dpk_dropout_fill')
+        call(lib.dpk_dropout_fill, ptr(x), x.numel(), float(rate), seed, float('-inf'), ptr(out), stream_ptr(x.device))
         ctx.meta = (float(rate), seed)
         return out
 
@@ -212,8 +197,7 @@ class DropoutFillFn(torch.autograd.Function):
         g = require_device_f32(g, 'grad')
         rate, seed = ctx.meta
         gx = torch.empty_like(g)
-        check(lib.dpk_dropout_fill(ptr(g), g.numel(), rate, seed, 0.0, ptr(gx), stream_ptr(g.device)),
-              'dpk_dropout_fill')
+        call(lib.dpk_dropout_fill, ptr(g), g.numel(), rate, seed, 0.0, ptr(gx), stream_ptr(g.device))
         return gx, None, None
 
 
@@ -226,7 +210,7 @@ class ProductFn(torch.autograd.Function):
         x = require_device_f32(x, 'x')
         B, R, N = x.shape
         out = torch.empty((B, R // 2, N * N), dtype=torch.float32, device=x.device)
-        check(lib.dpk_product_forward(ptr(x), B, R, N, ptr(out), stream_ptr(x.device)), 'dpk_product_forward')
+        call(lib.dpk_product_forward, ptr(x), B, R, N, ptr(out), stream_ptr(x.device))
         ctx.shape = (B, R, N)
         return out
 
@@ -236,17 +220,13 @@ class ProductFn(torch.autograd.Function):
         B, R, N = ctx.shape
         g = require_device_f32(g, 'grad')
         gx = torch.empty((B, R, N), dtype=torch.float32, device=g.device)
-        check(lib.dpk_product_backward(ptr(g), B, R, N, ptr(gx), stream_ptr(g.device)), 'dpk_product_backward')
+        call(lib.dpk_product_backward, ptr(g), B, R, N, ptr(gx), stream_ptr(g.device))
         return gx
 
 
 def _sum_ws(ws: Workspace, B, P, N, S, device):
-    lib = load_library()
-    n = lib.dpk_sum_workspace_bytes(B, P, N, S)
-    if n < 0:
-        check(int(n), 'dpk_sum_workspace_bytes')
-    ws.params_key = None   # the per-layer route lays its own tables over the folded route's cached ones
-    return ws.get(n, device)
+    ws.forget_tables()   # the per-layer route lays its own tables over the folded route's cached ones
+    return ws.sized(load_library().dpk_sum_workspace_bytes, B, P, N, S, device=device)
 
 
 class SumFn(torch.autograd.Function):
@@ -261,8 +241,8 @@ class SumFn(torch.autograd.Function):
         S = w.shape[1]
         out = torch.empty((B, P, S), dtype=torch.float32, device=x.device)
         buf = _sum_ws(ws, 0, P, N, S, x.device)      # (B sizes the backward's residual segment only)
-        check(lib.dpk_sum_forward(ptr(x), ptr(w), B, P, N, S, ptr(out), ptr(buf), buf.numel(),
-                                  stream_ptr(x.device)), 'dpk_sum_forward')
+        call(lib.dpk_sum_forward, ptr(x), ptr(w), B, P, N, S, ptr(out), ptr(buf), buf.numel(),
+                                  stream_ptr(x.device))
         ctx.save_for_backward(x, w, out)
         ctx.ws = ws
         return out
@@ -277,8 +257,8 @@ class SumFn(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         buf = _sum_ws(ctx.ws, B, P, N, S, x.device)
-        check(lib.dpk_sum_backward(ptr(x), ptr(w), ptr(out), ptr(g), B, P, N, S, ptr(gx), ptr(gw), ptr(buf),
-                                   buf.numel(), stream_ptr(x.device)), 'dpk_sum_backward')
+        call(lib.dpk_sum_backward, ptr(x), ptr(w), ptr(out), ptr(g), B, P, N, S, ptr(gx), ptr(gw), ptr(buf),
+                                   buf.numel(), stream_ptr(x.device))
         return gx, gw, None
 
 
@@ -295,8 +275,8 @@ class RootFn(torch.autograd.Function):
         x2 = x.reshape(B, M)
         out = torch.empty((B, C), dtype=torch.float32, device=x.device)
         buf = _sum_ws(ws, 0, 1, M, C, x.device)
-        check(lib.dpk_root_forward(ptr(x2), ptr(w), B, M, C, ptr(out), ptr(buf), buf.numel(),
-                                   stream_ptr(x.device)), 'dpk_root_forward')
+        call(lib.dpk_root_forward, ptr(x2), ptr(w), B, M, C, ptr(out), ptr(buf), buf.numel(),
+                                   stream_ptr(x.device))
         ctx.save_for_backward(x2, w, out)
         ctx.ws = ws
         ctx.in_shape = x.shape
@@ -312,8 +292,8 @@ class RootFn(torch.autograd.Function):
         gx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         buf = _sum_ws(ctx.ws, B, 1, M, C, x2.device)
-        check(lib.dpk_root_backward(ptr(x2), ptr(w), ptr(out), ptr(g), B, M, C, ptr(gx), ptr(gw), ptr(buf),
-                                    buf.numel(), stream_ptr(x2.device)), 'dpk_root_backward')
+        call(lib.dpk_root_backward, ptr(x2), ptr(w), ptr(out), ptr(g), B, M, C, ptr(gx), ptr(gw), ptr(buf),
+                                    buf.numel(), stream_ptr(x2.device))
         return (gx.reshape(ctx.in_shape) if gx is not None else None), gw, None
 
 
@@ -358,27 +338,27 @@ def _prodsum_backward(x, w, out, g, ws: Workspace, root: bool, need_gx: bool, ne
         buf = _sum_ws(ws, 0, P, N * N, S, x.device)
         rc = lib.dpk_prodsum_backward(ptr(x), ptr(w), ptr(out), ptr(g), B, R, N, S, int(root), ptr(gx), ptr(gw), ptr(buf),
                                       buf.numel(), st)
-        if rc != -4:
-            check(rc, 'dpk_prodsum_backward')
+        if rc != DPK_EUNSUPPORTED:
+            check(rc, lib.dpk_prodsum_backward)
             return gx, gw
     prod = torch.empty((B, P, N * N), dtype=torch.float32, device=x.device)
-    check(lib.dpk_product_forward(ptr(x), B, R, N, ptr(prod), st), 'dpk_product_forward')
+    call(lib.dpk_product_forward, ptr(x), B, R, N, ptr(prod), st)
     gprod = torch.empty_like(prod) if need_gx else None
     gw = torch.empty_like(w) if need_gw else None
     if root:
         M, C = P * N * N, w.shape[0]
         buf = _sum_ws(ws, B, 1, M, C, x.device)
-        check(lib.dpk_root_backward(ptr(prod), ptr(w), ptr(out), ptr(g), B, M, C, ptr(gprod), ptr(gw), ptr(buf),
-                                    buf.numel(), st), 'dpk_root_backward')
+        call(lib.dpk_root_backward, ptr(prod), ptr(w), ptr(out), ptr(g), B, M, C, ptr(gprod), ptr(gw), ptr(buf),
+                                    buf.numel(), st)
     else:
         S = w.shape[1]
         buf = _sum_ws(ws, B, P, N * N, S, x.device)
-        check(lib.dpk_sum_backward(ptr(prod), ptr(w), ptr(out), ptr(g), B, P, N * N, S, ptr(gprod), ptr(gw), ptr(buf),
-                                   buf.numel(), st), 'dpk_sum_backward')
+        call(lib.dpk_sum_backward, ptr(prod), ptr(w), ptr(out), ptr(g), B, P, N * N, S, ptr(gprod), ptr(gw), ptr(buf),
+                                   buf.numel(), st)
     gx = None
     if gprod is not None:
         gx = torch.empty_like(x)
-        check(lib.dpk_product_backward(ptr(gprod), B, R, N, ptr(gx), st), 'dpk_product_backward')
+        call(lib.dpk_product_backward, ptr(gprod), B, R, N, ptr(gx), st)
     return gx, gw
 
 
@@ -401,17 +381,13 @@ class RatSpnTrainFn(torch.autograd.Function):
         leaf_rel = torch.empty((B, lctx.R, lctx.I), dtype=torch.float32, device=dev)
         sum_rel = torch.empty((B, 2 * lctx.reps, lctx.S), dtype=torch.float32, device=dev)
         ws, flags = lctx.workspace(dev, mask, pad_mask, scale)
-        flags |= _params_flag(lib, lctx, ptr(x), flags, [loc_c, scale_c, w0_c, wr_c])
+        flags |= _params_flag(lctx, lib.dpk_ratspn_forward_on_mfma, lctx.fused_probe(ptr(x)), flags, [loc_c, scale_c, w0_c, wr_c])
         rc = lib.dpk_ratspn_forward_train(ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)), ptr(loc_c), ptr(scale_c),
                                           ptr(w0_c), ptr(wr_c), lctx.depth, lctx.reps, lctx.I, lctx.S, lctx.C, ptr(out),
                                           ptr(leaf_rel), ptr(sum_rel), ptr(out_rel), ptr(ws), ws.numel(), flags,
                                           stream_ptr(dev))
-        if rc:
-            lctx.ws.params_key = None
-            if rc == -4:  # DPK_EUNSUPPORTED
-                lctx.ws.struct_key = None
-                raise _TrainForwardUnsupported()
-        check(rc, 'dpk_ratspn_forward_train')
+        if lctx.ws.outcome(rc, lib.dpk_ratspn_forward_train, out, forget_structure=True) is None:
+            raise _TrainForwardUnsupported()
         ctx.save_for_backward(x, loc_c, scale_c, w0_c, wr_c, mask, pad_mask, leaf_rel, sum_rel, out_rel)
         ctx.leaf_lctx, ctx.ws0, ctx.wsr = leaf_lctx, ws0, wsr
         return out
@@ -430,10 +406,9 @@ class RatSpnTrainFn(torch.autograd.Function):
             lctx = ctx.leaf_lctx
             gloc = torch.empty_like(loc)
             ws, flags = lctx.workspace(x.device, mask, pad_mask)
-            check(lib.dpk_gaussian_leaf_backward(ptr(x), ptr(gleaf), x.shape[0], lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
+            call(lib.dpk_gaussian_leaf_backward, ptr(x), ptr(gleaf), x.shape[0], lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)),
                                                  ptr(loc), ptr(scale), lctx.R, lctx.I, lctx.d, ptr(gloc), None, None,
-                                                 ptr(ws), ws.numel(), flags, stream_ptr(x.device)),
-                  'dpk_gaussian_leaf_backward')
+                                                 ptr(ws), ws.numel(), flags, stream_ptr(x.device))
         return (None, gloc, None, gw0, gwr) + (None,) * 6
 
 
@@ -473,21 +448,14 @@ def ratspn_forward_fused(x, mask, pad_mask, loc, scale, sum_weights, root_weight
     B = x.shape[0]
     out = torch.empty((B, lctx.C), dtype=torch.float32, device=x.device)
     ws, flags = lctx.workspace(x.device, mask, pad_mask, scale)
-    flags |= _params_flag(lib, lctx, ptr(x), flags, [loc_c, scale_c] + sw + [rw])
+    flags |= _params_flag(lctx, lib.dpk_ratspn_forward_on_mfma, lctx.fused_probe(ptr(x)), flags, [loc_c, scale_c] + sw + [rw])
     if ll_acc is not None and ll_acc.numel() > LL_SPREAD:      # a spread slot: sixteen partial sums, then the count
         flags |= DPK_FLAG_LL_SUM_SPREAD
     rc = lib.dpk_ratspn_forward(ptr(x), B, lctx.D, ptr(mask), ptr(_pad_u8(pad_mask)), ptr(loc_c), ptr(scale_c),
                                 ptr(sw[0]) if len(sw) > 0 else None, ptr(sw[1]) if len(sw) > 1 else None,
                                 ptr(rw), lctx.depth, lctx.reps, lctx.I, lctx.S, lctx.C, ptr(out), None,
                                 ptr(ll_acc), ptr(ws), ws.numel(), flags, stream_ptr(x.device))
-    if rc == -4:  # DPK_EUNSUPPORTED
-        lctx.ws.struct_key = None
-        lctx.ws.params_key = None
-        return None
-    if rc:
-        lctx.ws.params_key = None
-    check(rc, 'dpk_ratspn_forward')
-    return out
+    return lctx.ws.outcome(rc, lib.dpk_ratspn_forward, out, forget_structure=True)
 
 
 class FusedForwardPlan:
@@ -526,15 +494,15 @@ class FusedForwardPlan:
         self.params = self.tensors[3:]
         # the first call also builds (or re-validates) the structure tables and tells whether the shape is covered
         self.args[-1] = stream_ptr(self.device)
-        self.args[-2] = flags | _params_flag(self.lib, lctx, self.args[0], flags, self.params)
+        self.probe = lctx.fused_probe(self.args[0])
+        self.args[-2] = flags | _params_flag(lctx, self.lib.dpk_ratspn_forward_on_mfma, self.probe, flags, self.params)
         rc = self.lib.dpk_ratspn_forward(*self.args)
-        self.supported = rc != -4
+        self.supported = rc != DPK_EUNSUPPORTED
         if self.supported:
-            check(rc, 'dpk_ratspn_forward')
+            check(rc, self.lib.dpk_ratspn_forward)
             self.base_flags = flags | DPK_FLAG_STRUCT_CACHED
         else:
-            lctx.ws.struct_key = None
-            lctx.ws.params_key = None
+            lctx.ws.forget_structure()
 
     def _addresses(self):
         return tuple(t.data_ptr() for t in self.tensors if t is not None) + (self.ws.data_ptr(),)
@@ -544,19 +512,19 @@ class FusedForwardPlan:
         # graph keeps the addresses): the module's cached structure key must still be the one this plan bound
         return (self.lctx.ws.buf is self.ws and self._addresses() == self.ptrs
                 and self.lctx.ws.struct_key == self.struct_key
-                and _buffers_key(*self._struct_tensors) == self.struct_key)
+                and tensors_key(*self._struct_tensors) == self.struct_key)
 
     def run(self, ll_acc: Optional[torch.Tensor] = None) -> torch.Tensor:
         args = self.args
         args[17] = None if ll_acc is None else ll_acc.data_ptr()
         args[-1] = torch.cuda.current_stream(self.device).cuda_stream
-        pf = _params_flag(self.lib, self.lctx, args[0], self.base_flags, self.params)
+        pf = _params_flag(self.lctx, self.lib.dpk_ratspn_forward_on_mfma, self.probe, self.base_flags, self.params)
         if pf and self.static_params:
             pf = DPK_FLAG_PARAMS_CACHED
         args[-2] = self.base_flags | pf | (DPK_FLAG_LL_SUM_SPREAD if ll_acc is not None and ll_acc.numel() > LL_SPREAD else 0)
         rc = self.lib.dpk_ratspn_forward(*args)
         if rc:
-            check(rc, 'dpk_ratspn_forward')
+            check(rc, self.lib.dpk_ratspn_forward)
         return self.out
 
 
@@ -568,26 +536,17 @@ def ll_accumulate(ll: torch.Tensor, acc: torch.Tensor):
     if acc.numel() > LL_SPREAD:
         acc = acc.view(-1)[LL_SPREAD - 1:LL_SPREAD + 1]
     assert acc.dtype == torch.float64 and acc.numel() == 2 and acc.is_cuda
-    check(lib.dpk_ll_accumulate(ptr(ll), ll.numel(), ptr(acc), stream_ptr(ll.device)), 'dpk_ll_accumulate')
+    call(lib.dpk_ll_accumulate, ptr(ll), ll.numel(), ptr(acc), stream_ptr(ll.device))
 
 
 def _prodsum_ws(ws: Workspace, R, N, S, device):
-    lib = load_library()
-    n = lib.dpk_prodsum_workspace_bytes(R, N, S)
-    if n < 0:
-        check(int(n), 'dpk_prodsum_workspace_bytes')
-    return ws.get(n, device)
+    return ws.sized(load_library().dpk_prodsum_workspace_bytes, R, N, S, device=device)
 
 
-def _upper_tables_flag(ws: Workspace, route: str, w: torch.Tensor) -> int:
-    """DPK_FLAG_PARAMS_CACHED when the layer's workspace still holds the softmax rows and MFMA fragments that the
-    same folded entry point built from this very weight tensor (address, shape, version counter).  The per-layer
-    operators sharing the workspace drop the key (_sum_ws), so does a replaced buffer (Workspace.get)."""
-    key = (route, w.data_ptr(), tuple(w.shape), w._version)
-    if ws.params_key == key:
-        return cached_tables_flag()
-    ws.params_key = key
-    return 0
+def _upper_tables_key(route: str, w: torch.Tensor) -> tuple:
+    """Key of the softmax rows and MFMA fragments that the folded entry point ``route`` builds from this very weight
+    tensor.  The per-layer operators sharing the workspace forget it (_sum_ws), so does a replaced buffer."""
+    return (route, tensors_key(w))
 
 
 def upper_tables_pair(sum_weight: torch.Tensor, ws0: Workspace, R0: int, N0: int, root_weight: torch.Tensor, ws1: Workspace,
@@ -600,16 +559,16 @@ def upper_tables_pair(sum_weight: torch.Tensor, ws0: Workspace, R0: int, N0: int
     w0, w1 = require_device_f32(sum_weight, 'sum weight'), require_device_f32(root_weight, 'root weight')
     S0, C = w0.shape[1], w1.shape[0]
     b0, b1 = _prodsum_ws(ws0, R0, N0, S0, device), _prodsum_ws(ws1, R1, N1, C, device)
-    key0 = ('prodsum', w0.data_ptr(), tuple(w0.shape), w0._version)
-    key1 = ('prodroot', w1.data_ptr(), tuple(w1.shape), w1._version)
-    if cached_tables_flag() == DPK_FLAG_PARAMS_CACHED and ws0.params_key == key0 and ws1.params_key == key1:
+    key0, key1 = _upper_tables_key('prodsum', w0), _upper_tables_key('prodroot', w1)
+    if trust_versions() and ws0.holds_tables(key0) and ws1.holds_tables(key1):
         return False     # (trusting the version counters and nothing moved: the layers skip their tables themselves)
     rc = lib.dpk_upper_tables_pair(ptr(w0), R0, N0, S0, ptr(b0), b0.numel(), ptr(w1), R1, N1, C, ptr(b1), b1.numel(),
                                    stream_ptr(device))
-    if rc == -4:
+    if rc == DPK_EUNSUPPORTED:
         return False
-    check(rc, 'dpk_upper_tables_pair')
-    ws0.params_key, ws1.params_key = key0, key1
+    check(rc, lib.dpk_upper_tables_pair)
+    ws0.tables_built(key0)
+    ws1.tables_built(key1)
     return True
 
 
@@ -623,15 +582,10 @@ def prodsum_forward(x: torch.Tensor, weight: torch.Tensor, ws: Workspace, tables
     S = w.shape[1]
     out = torch.empty((B, R // 2, S), dtype=torch.float32, device=x.device)
     buf = _prodsum_ws(ws, R, N, S, x.device)
-    flags = DPK_FLAG_PARAMS_CACHED if tables_current else _upper_tables_flag(ws, 'prodsum', w)
+    flags = DPK_FLAG_PARAMS_CACHED if tables_current else ws.tables_flag(_upper_tables_key('prodsum', w))
     rc = lib.dpk_prodsum_forward(ptr(x), ptr(w), B, R, N, S, ptr(out), ptr(buf), buf.numel(), flags,
                                  stream_ptr(x.device))
-    if rc:
-        ws.params_key = None
-    if rc == -4:
-        return None
-    check(rc, 'dpk_prodsum_forward')
-    return out
+    return ws.outcome(rc, lib.dpk_prodsum_forward, out)
 
 
 def prodroot_forward(x: torch.Tensor, weight: torch.Tensor, ws: Workspace, tables_current: bool = False) -> Optional[torch.Tensor]:
@@ -644,15 +598,10 @@ def prodroot_forward(x: torch.Tensor, weight: torch.Tensor, ws: Workspace, table
     C = w.shape[0]
     out = torch.empty((B, C), dtype=torch.float32, device=x.device)
     buf = _prodsum_ws(ws, R, N, C, x.device)
-    flags = DPK_FLAG_PARAMS_CACHED if tables_current else _upper_tables_flag(ws, 'prodroot', w)
+    flags = DPK_FLAG_PARAMS_CACHED if tables_current else ws.tables_flag(_upper_tables_key('prodroot', w))
     rc = lib.dpk_prodroot_forward(ptr(x), ptr(w), B, R, N, C, ptr(out), ptr(buf), buf.numel(), flags,
                                   stream_ptr(x.device))
-    if rc:
-        ws.params_key = None
-    if rc == -4:
-        return None
-    check(rc, 'dpk_prodroot_forward')
-    return out
+    return ws.outcome(rc, lib.dpk_prodroot_forward, out)
 
 
 def ratspn_topdown(mode: int, dist: int, n_samples: int, lctx: LeafContext, x: Optional[torch.Tensor], y: Optional[torch.Tensor],
@@ -694,10 +643,9 @@ def ratspn_topdown(mode: int, dist: int, n_samples: int, lctx: LeafContext, x: O
     p0d, p1d = dev(p0, 'p0'), (dev(p1, 'p1') if p1 is not None else None)
     out = torch.empty((B, lctx.D), dtype=torch.float32, device=device)
     choice = torch.empty((B, 1 + (1 << depth)), dtype=torch.int32, device=device) if want_choice else None
-    check(lib.dpk_ratspn_topdown(mode, dist, B, lctx.D, depth, lctx.reps, lctx.I, lctx.S, lctx.C, lctx.d, ptr(xd), ptr(yd),
+    call(lib.dpk_ratspn_topdown, mode, dist, B, lctx.D, depth, lctx.reps, lctx.I, lctx.S, lctx.C, lctx.d, ptr(xd), ptr(yd),
                                  ctypes.cast(act_arr, ctypes.c_void_p), ctypes.cast(logw_arr, ctypes.c_void_p), ptr(src),
-                                 ptr(p0d), ptr(p1d), seed & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(choice), stream_ptr(device)),
-          'dpk_ratspn_topdown')
+                                 ptr(p0d), ptr(p1d), seed & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(choice), stream_ptr(device))
     return (out, choice) if want_choice else out
 
 
@@ -710,7 +658,7 @@ class NegMeanFn(torch.autograd.Function):
         lib = load_library()
         x = require_device_f32(x, 'x')
         out = torch.empty((), dtype=torch.float32, device=x.device)
-        check(lib.dpk_neg_mean_forward(ptr(x), x.numel(), ptr(out), stream_ptr(x.device)), 'dpk_neg_mean_forward')
+        call(lib.dpk_neg_mean_forward, ptr(x), x.numel(), ptr(out), stream_ptr(x.device))
         ctx.shape = x.shape
         return out
 
@@ -719,7 +667,7 @@ class NegMeanFn(torch.autograd.Function):
         lib = load_library()
         g = require_device_f32(g, 'grad')
         gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        check(lib.dpk_neg_mean_backward(ptr(g), gx.numel(), ptr(gx), stream_ptr(g.device)), 'dpk_neg_mean_backward')
+        call(lib.dpk_neg_mean_backward, ptr(g), gx.numel(), ptr(gx), stream_ptr(g.device))
         return gx
 
 

@@ -10,60 +10,31 @@ from typing import Optional, Tuple
 
 import torch
 
-from deeprob.hip import (load_library, check, ptr, stream_ptr, require_device_f32, HipError,
-                         DPK_FLAG_PARAMS_CACHED, cached_tables_flag)
-
-
-def _versions(*tensors) -> tuple:
-    return tuple(None if t is None else (t.data_ptr(), t._version, tuple(t.shape)) for t in tensors)
-
-
-def _trusting() -> bool:
-    from deeprob import hip
-    return hip._trust_versions
+from deeprob.hip import (load_library, call, check, ptr, stream_ptr, require_device_f32, HipError, tensors_key,
+                         trust_versions, prepare_begin, prepare_commit, prepare_release, prepared, BnFoldArgs as _BnFoldArgs,
+                         PairsTablesArgs as _PairsTablesArgs, DPK_FLAG_PARAMS_CACHED, cached_tables_flag)
 
 
 # ---- one verification pass per flow forward (round 3) -----------------------------------------------------------------
 # NormalizingFlow._forward_fused calls flow1d_prepare once: every eval-mode BatchNormLayer1d is folded by ONE launch
 # (dpk_bn1d_fold_many, which also leaves the sum of the constant log-determinants) and the packed tables of every
 # alternating-mask coupling are fingerprinted / rebuilt by TWO launches (dpk_coupling1d_pairs_tables) -- instead of three
-# small launches per layer.  The per-layer operators below recognise the forward's token and skip their own launches.
-_prep_token = None
-
-
-class _BnFoldArgs(ctypes.Structure):          # dpk_bn1d_fold_args
-    _fields_ = [(n, ctypes.c_void_p) for n in ('weight', 'bias', 'running_var', 'running_mean', 'scale_in', 'shift_in',
-                                               'scale_out', 'shift_out', 'ldj_const')] + \
-               [('eps', ctypes.c_float), ('D', ctypes.c_int32), ('inverse', ctypes.c_int32), ('accumulate', ctypes.c_int32)]
-
-
-class _PairsTablesArgs(ctypes.Structure):     # dpk_pairs_tables_args
-    _fields_ = [(n, ctypes.c_void_p) for n in ('W1', 'b1', 'W2', 'b2', 'in_scale', 'in_shift', 'ws')] + \
-               [('ws_bytes', ctypes.c_int64), ('D', ctypes.c_int32), ('units', ctypes.c_int32),
-                ('masked_parity', ctypes.c_int32), ('affine', ctypes.c_int32), ('flags', ctypes.c_uint32)]
-
-
-def _prepared(obj) -> bool:
-    return _prep_token is not None and getattr(obj, '_prep_token', None) is _prep_token
-
-
-def flow1d_release():
-    global _prep_token
-    _prep_token = None
+# small launches per layer.  The per-layer operators below recognise the forward's token (hip.prepare_begin) and skip
+# their own launches: the couplings through Workspace.tables_flag, a folded batch norm by its ``_fold_token``, the sum of
+# the constants by the flow's ``_const_sum_token``.
+flow1d_release = prepare_release
 
 
 def flow1d_prepare(flow, layers, x: torch.Tensor):
     """Fold the batch norms and verify the coupling tables of one density evaluation in three launches (see above).
     Layers outside the batched entries' envelope are left to their own operators.  No-op when the version counters are
     trusted (nothing is launched per call then) or for host tensors (the operators raise)."""
-    global _prep_token
-    _prep_token = None
-    if _trusting() or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32 or len(layers) > 32:
+    token = prepare_begin()
+    if trust_versions() or not x.is_cuda or x.dim() != 2 or x.dtype != torch.float32 or len(layers) > 32:
         return
     from deeprob.flows.utils import BatchNormLayer1d
     lib = load_library()
     dev = x.device
-    token = object()
     # ---- batch norms whose input is not another batch norm's output (the fold chain restarts behind every coupling)
     bn_idx = [i for i, l in enumerate(layers) if isinstance(l, BatchNormLayer1d)]
     simple = [i for i in bn_idx if i == 0 or not isinstance(layers[i - 1], BatchNormLayer1d)]
@@ -74,7 +45,7 @@ def flow1d_prepare(flow, layers, x: torch.Tensor):
                    for t in (bn.weight, bn.bias, bn.running_var, bn.running_mean)):
             continue
         D = bn.in_features
-        key = (_versions(bn.weight, bn.bias, bn.running_var, bn.running_mean, None, None), False, float(bn.eps))
+        key = (tensors_key(bn.weight, bn.bias, bn.running_var, bn.running_mean, None, None), False, float(bn.eps))
         hit = getattr(bn, '_fold_cache', None)
         if hit is None or hit[0] != key:
             hit = (key, (torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)),
@@ -95,10 +66,9 @@ def flow1d_prepare(flow, layers, x: torch.Tensor):
                 flow._const_sum_cache = chit
             total = chit[1]
         arr = (_BnFoldArgs * len(entries))(*entries)
-        check(lib.dpk_bn1d_fold_many(len(entries), ctypes.cast(arr, ctypes.c_void_p), ptr(total), stream_ptr(dev)),
-              'dpk_bn1d_fold_many')
+        call(lib.dpk_bn1d_fold_many, len(entries), ctypes.cast(arr, ctypes.c_void_p), ptr(total), stream_ptr(dev))
         for bn, _ in folded.values():
-            bn._prep_token = token
+            bn._fold_token = token
         if total is not None:
             flow._const_sum_token = token
     # ---- couplings inside the column-pair kernel's envelope (the tests of coupling1d / coupling1d_logprob)
@@ -122,16 +92,15 @@ def flow1d_prepare(flow, layers, x: torch.Tensor):
             sc, sh = folded[i - 1][1][1]
         else:
             sc, sh = None, None
-        n = lib.dpk_coupling1d_pairs_workspace_bytes(D, units)
-        if n < 0:
-            continue
         pw = layer._ws_pairs
-        ws = pw.get(n, dev)
+        ws = pw.sized(lib.dpk_coupling1d_pairs_workspace_bytes, D, units, device=dev, or_none=True)
+        if ws is None:
+            continue
         w1, b1, w2, b2 = lin1.weight, lin1.bias, lin2.weight, lin2.bias
-        key = (_versions(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
+        key = (tensors_key(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
         if not _pairs_well_conditioned(pw, key, w1, w2, sc, parity):
             continue                # (the fp32-MFMA kernel takes this layer: no packed tables)
-        flags = cached_tables_flag() if pw.params_key == key else 0
+        flags = cached_tables_flag() if pw.holds_tables(key) else 0
         centries.append(_PairsTablesArgs(ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(sc), ptr(sh), ptr(ws), ws.numel(), D, units,
                                          parity, int(layer.affine), flags))
         marked.append((pw, key))
@@ -142,14 +111,11 @@ def flow1d_prepare(flow, layers, x: torch.Tensor):
             # nothing is known about any of these table sets now: the per-layer operators rebuild (round-3 advice: the keys
             # used to be recorded BEFORE the launch, and a failure left them claiming tables that were never built)
             for pw, _ in marked:
-                pw.params_key = None
-                pw._prep_token = None
-            check(rc, 'dpk_coupling1d_pairs_tables')
+                pw.forget_prepared()
+            check(rc, lib.dpk_coupling1d_pairs_tables)
         for pw, key in marked:
-            pw.params_key = key
-            pw._prep_token = token
-            pw._prep_key = key
-    _prep_token = token
+            pw.tables_built(key, token)
+    prepare_commit(token)
 
 
 # ---- accuracy guard of the split-f16 coupling kernels (round 4) --------------------------------------------------------
@@ -179,15 +145,6 @@ def _pairs_well_conditioned(pw, key, w1: torch.Tensor, w2: torch.Tensor, sc: Opt
     ok = gain == gain and gain <= PAIRS_GAIN_LIMIT
     pw._cond = (key, ok, gain)
     return ok
-
-
-def _tables_flags(pw, key) -> int:
-    """Flags of a column-pair call: tables verified by this forward's flow1d_prepare are taken as they are."""
-    if _prepared(pw) and getattr(pw, '_prep_key', None) == key:
-        return DPK_FLAG_PARAMS_CACHED
-    flags = cached_tables_flag() if pw.params_key == key else 0
-    pw.params_key = key
-    return flags
 
 
 def _no_graph(*tensors):
@@ -223,11 +180,8 @@ def coupling1d(x: torch.Tensor, layer, inverse: bool, in_affine: Optional[Tuple[
         # the reference's alternating masks: split-f16 MFMA kernel, packed tables kept while the weights (and the
         # folded input affine) are unchanged.  (Rows that are not 16-byte aligned -- a view at an odd storage offset --
         # keep the generic kernel below; the test comes first so that nothing of this branch leaks into that route.)
-        n = lib.dpk_coupling1d_pairs_workspace_bytes(D, units)
-        if n < 0:
-            check(int(n), 'dpk_coupling1d_pairs_workspace_bytes')
         pw = layer._ws_pairs
-        ws = pw.get(n, x.device)
+        ws = pw.sized(lib.dpk_coupling1d_pairs_workspace_bytes, D, units, device=x.device)
         out = torch.empty_like(x)
         if out.data_ptr() % 16 == 0:
             ldj_p = ldj if ldj is not None else torch.empty(B, dtype=torch.float32, device=x.device)
@@ -235,34 +189,31 @@ def coupling1d(x: torch.Tensor, layer, inverse: bool, in_affine: Optional[Tuple[
             act = layer.scale_act.weight if layer.affine else None
             w1, b1 = require_device_f32(lin1.weight, 'W1'), require_device_f32(lin1.bias, 'b1')
             w2, b2 = require_device_f32(lin2.weight, 'W2'), require_device_f32(lin2.bias, 'b2')
-            key = (_versions(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
+            key = (tensors_key(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
             # (accuracy guard: a badly conditioned layer keeps the fp32-MFMA kernel below)
             if _pairs_well_conditioned(pw, key, w1, w2, sc, parity):
-                flags = _tables_flags(pw, key)
+                flags = pw.tables_flag(key)
                 rc = lib.dpk_coupling1d_pairs_forward(
                     ptr(x), B, D, parity, ptr(w1), ptr(b1), ptr(w2), ptr(b2), units, ptr(act), ptr(sc), ptr(sh),
                     int(layer.affine), int(inverse), ptr(out), ptr(ldj_p), int(ldj is not None), ptr(ws), ws.numel(),
                     flags, stream_ptr(x.device))
                 if rc:
-                    pw.params_key = None        # (a failed call built nothing: the next one does not trust the tables)
-                check(rc, 'dpk_coupling1d_pairs_forward')
+                    pw.forget_tables()        # (a failed call built nothing: the next one does not trust the tables)
+                    check(rc, lib.dpk_coupling1d_pairs_forward)
                 return out, ldj_p
-    n = lib.dpk_coupling1d_workspace_bytes(D, units, n_masked, n_trans)
-    if n < 0:
-        check(int(n), 'dpk_coupling1d_workspace_bytes')
-    ws = layer._ws.get(n, x.device)
+    ws = layer._ws.sized(lib.dpk_coupling1d_workspace_bytes, D, units, n_masked, n_trans, device=x.device)
     out = torch.empty_like(x)
     accumulate = ldj is not None
     if ldj is None:
         ldj = torch.empty(B, dtype=torch.float32, device=x.device)
     sc, sh = in_affine if in_affine is not None else (None, None)
     act = layer.scale_act.weight if layer.affine else None
-    check(lib.dpk_coupling1d_forward(
+    call(lib.dpk_coupling1d_forward, 
         ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), n_masked, n_trans,
         ptr(require_device_f32(lin1.weight, 'W1')), ptr(require_device_f32(lin1.bias, 'b1')),
         ptr(require_device_f32(lin2.weight, 'W2')), ptr(require_device_f32(lin2.bias, 'b2')), units,
         ptr(act), ptr(sc), ptr(sh), int(layer.affine), int(inverse), ptr(out), ptr(ldj), int(accumulate),
-        ptr(ws), ws.numel(), stream_ptr(x.device)), 'dpk_coupling1d_forward')
+        ptr(ws), ws.numel(), stream_ptr(x.device))
     return out, ldj
 
 
@@ -283,32 +234,26 @@ def coupling1d_logprob(x: torch.Tensor, layer, in_affine, ildj: Optional[torch.T
     parity = layer._pair_parity()
     if parity is None or units not in (32, 64, 96, 128) or D % 8 != 0 or x.data_ptr() % 16 != 0 or base_loc.numel() != D:
         return None
-    n = lib.dpk_coupling1d_pairs_workspace_bytes(D, units)
-    if n < 0:
-        return None
     pw = layer._ws_pairs
-    ws = pw.get(n, x.device)
+    ws = pw.sized(lib.dpk_coupling1d_pairs_workspace_bytes, D, units, device=x.device, or_none=True)
+    if ws is None:
+        return None
     sc, sh = in_affine if in_affine is not None else (None, None)
     osc, osh = out_affine if out_affine is not None else (None, None)
     act = layer.scale_act.weight if layer.affine else None
     w1, b1 = require_device_f32(lin1.weight, 'W1'), require_device_f32(lin1.bias, 'b1')
     w2, b2 = require_device_f32(lin2.weight, 'W2'), require_device_f32(lin2.bias, 'b2')
-    key = (_versions(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
+    key = (tensors_key(w1, b1, w2, b2, sc, sh), parity, bool(layer.affine))
     if not _pairs_well_conditioned(pw, key, w1, w2, sc, parity):
         return None             # (accuracy guard: the caller chains the fp32-MFMA coupling and the base density)
-    flags = _tables_flags(pw, key)
+    flags = pw.tables_flag(key)
     ll = torch.empty(B, dtype=torch.float32, device=x.device)
     rc = lib.dpk_coupling1d_pairs_logprob(
         ptr(x), B, D, parity, ptr(w1), ptr(b1), ptr(w2), ptr(b2), units, ptr(act), ptr(sc), ptr(sh), int(layer.affine),
         ptr(osc), ptr(osh), ptr(require_device_f32(base_loc.reshape(-1), 'loc')),
         ptr(require_device_f32(base_scale.reshape(-1), 'scale')), ptr(ildj), ptr(ildj_const), ptr(ll), ptr(ws),
         ws.numel(), flags, stream_ptr(x.device))
-    if rc:
-        pw.params_key = None
-    if rc == -4:
-        return None
-    check(rc, 'dpk_coupling1d_pairs_logprob')
-    return ll
+    return pw.outcome(rc, lib.dpk_coupling1d_pairs_logprob, ll)
 
 
 def _mlp_args(layer):
@@ -330,10 +275,7 @@ KEEP_ACTIVATIONS_BYTES = 1 << 30
 
 
 def _mlp_backward_bytes(B: int, n_hidden: int, widths) -> int:
-    n = load_library().dpk_coupling1d_mlp_workspace_bytes(B, n_hidden, widths, 1)
-    if n < 0:
-        check(int(n), 'dpk_coupling1d_mlp_workspace_bytes')
-    return int(n)
+    return int(call(load_library().dpk_coupling1d_mlp_workspace_bytes, B, n_hidden, widths, 1))
 
 
 def _coupling1d_mlp(x: torch.Tensor, layer, inverse: bool, keep: bool = False):
@@ -346,16 +288,13 @@ def _coupling1d_mlp(x: torch.Tensor, layer, inverse: bool, keep: bool = False):
     if keep:
         ws = torch.empty(_mlp_backward_bytes(B, n_hidden, widths), dtype=torch.uint8, device=x.device)
     else:
-        n = lib.dpk_coupling1d_mlp_workspace_bytes(B, n_hidden, widths, 0)
-        if n < 0:
-            check(int(n), 'dpk_coupling1d_mlp_workspace_bytes')
-        ws = layer._ws.get(n, x.device)
+        ws = layer._ws.sized(lib.dpk_coupling1d_mlp_workspace_bytes, B, n_hidden, widths, 0, device=x.device)
     out = torch.empty_like(x)
     ldj = torch.empty(B, dtype=torch.float32, device=x.device)
     act = layer.scale_act.weight if layer.affine else None
-    check(lib.dpk_coupling1d_mlp_forward(ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), n_hidden, Wp, bp, widths,
+    call(lib.dpk_coupling1d_mlp_forward, ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), n_hidden, Wp, bp, widths,
                                          ptr(act), int(layer.affine), int(inverse), ptr(out), ptr(ldj), ptr(ws),
-                                         ws.numel(), stream_ptr(x.device)), 'dpk_coupling1d_mlp_forward')
+                                         ws.numel(), stream_ptr(x.device))
     del alive
     return (out, ldj, ws) if keep else (out, ldj)
 
@@ -371,7 +310,7 @@ def bn1d_fold(bn, inverse: bool, in_affine=None, ldj_const: Optional[torch.Tenso
     D = bn.in_features
     dev = bn.weight.device
     s_in, h_in = in_affine if in_affine is not None else (None, None)
-    key = (_versions(bn.weight, bn.bias, bn.running_var, bn.running_mean, s_in, h_in), bool(inverse), float(bn.eps))
+    key = (tensors_key(bn.weight, bn.bias, bn.running_var, bn.running_mean, s_in, h_in), bool(inverse), float(bn.eps))
     hit = getattr(bn, '_fold_cache', None)
     fresh = hit is None or hit[0] != key
     if fresh:
@@ -381,16 +320,16 @@ def bn1d_fold(bn, inverse: bool, in_affine=None, ldj_const: Optional[torch.Tenso
         # (s_in / h_in are kept alive with the entry: their addresses are part of the key)
         hit = (key, (sc, sh), own, (s_in, h_in))
         bn._fold_cache = hit
-    if (fresh or not _trusting()) and not (not fresh and not inverse and in_affine is None and _prepared(bn)):
+    if (fresh or not trust_versions()) and not (not fresh and not inverse and in_affine is None
+                                                and prepared(getattr(bn, '_fold_token', None))):
         # The fold is one D-element kernel: it runs on every call (into the SAME tensors), so that a write through
         # `.data` of a statistic or parameter -- which moves no version counter -- is folded in; the coupling behind it
         # fingerprints these tensors on the device.  With hip.trust_version_counters(True) it runs on a key change only.
         (sc, sh), own = hit[1], hit[2]
-        check(lib.dpk_bn1d_fold(ptr(require_device_f32(bn.weight, 'weight')), ptr(require_device_f32(bn.bias, 'bias')),
+        call(lib.dpk_bn1d_fold, ptr(require_device_f32(bn.weight, 'weight')), ptr(require_device_f32(bn.bias, 'bias')),
                                 ptr(require_device_f32(bn.running_var, 'running_var')),
                                 ptr(require_device_f32(bn.running_mean, 'running_mean')), float(bn.eps), D,
-                                int(inverse), ptr(s_in), ptr(h_in), ptr(sc), ptr(sh), ptr(own), 0, stream_ptr(dev)),
-              'dpk_bn1d_fold')
+                                int(inverse), ptr(s_in), ptr(h_in), ptr(sc), ptr(sh), ptr(own), 0, stream_ptr(dev))
     if isinstance(ldj_const, list):      # the caller sums the layers' constants itself (sum_constants below)
         ldj_const.append(hit[2])
         return hit[1], ldj_const
@@ -411,7 +350,7 @@ def sum_constants(owner, consts) -> Optional[torch.Tensor]:
     if hit is None or hit[0] != key:
         hit = (key, torch.stack([t.reshape(()) for t in consts]).sum().reshape(1), list(consts))   # (keeps them alive)
         owner._const_sum_cache = hit
-    elif not _trusting() and not (_prep_token is not None and getattr(owner, '_const_sum_token', None) is _prep_token):
+    elif not trust_versions() and not prepared(getattr(owner, '_const_sum_token', None)):
         # (bn1d_fold rewrites the constants in place on every call: the total follows them, into the same tensor)
         torch.sum(torch.stack([t.reshape(()) for t in consts]), dim=0, keepdim=True, out=hit[1])
     return hit[1]
@@ -422,8 +361,7 @@ def affine1d(x: torch.Tensor, affine) -> torch.Tensor:
     x = require_device_f32(x, 'x')
     out = torch.empty_like(x)
     B, D = x.shape
-    check(lib.dpk_affine1d_forward(ptr(x), ptr(affine[0]), ptr(affine[1]), B, D, ptr(out), stream_ptr(x.device)),
-          'dpk_affine1d_forward')
+    call(lib.dpk_affine1d_forward, ptr(x), ptr(affine[0]), ptr(affine[1]), B, D, ptr(out), stream_ptr(x.device))
     return out
 
 
@@ -434,9 +372,9 @@ def normal_base_logprob(u: torch.Tensor, affine, loc, scale, ildj, ildj_const) -
     B, D = u.shape
     out = torch.empty(B, dtype=torch.float32, device=u.device)
     sc, sh = affine if affine is not None else (None, None)
-    check(lib.dpk_normal_base_logprob(ptr(u), ptr(sc), ptr(sh), ptr(require_device_f32(loc, 'loc')),
+    call(lib.dpk_normal_base_logprob, ptr(u), ptr(sc), ptr(sh), ptr(require_device_f32(loc, 'loc')),
                                       ptr(require_device_f32(scale, 'scale')), ptr(ildj), ptr(ildj_const), B, D,
-                                      ptr(out), stream_ptr(u.device)), 'dpk_normal_base_logprob')
+                                      ptr(out), stream_ptr(u.device))
     return out
 
 
@@ -472,14 +410,11 @@ class CouplingFn(torch.autograd.Function):
         gW2 = torch.empty_like(W2) if need[3] else None
         gb2 = torch.empty_like(b2) if need[4] else None
         gact = torch.empty_like(act) if (act is not None and need[5]) else None
-        n = lib.dpk_coupling1d_backward_workspace_bytes(B, D, units, int(layer.affine))
-        if n < 0:
-            check(int(n), 'dpk_coupling1d_backward_workspace_bytes')
-        ws = layer._ws_bwd.get(n, x.device)
-        check(lib.dpk_coupling1d_backward(
+        ws = layer._ws_bwd.sized(lib.dpk_coupling1d_backward_workspace_bytes, B, D, units, int(layer.affine), device=x.device)
+        call(lib.dpk_coupling1d_backward, 
             ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), ptr(W1), ptr(b1), ptr(W2), ptr(b2), units, ptr(act),
             int(layer.affine), ptr(gu), ptr(gildj), ptr(gx), ptr(gW1), ptr(gb1), ptr(gW2), ptr(gb2), ptr(gact),
-            ptr(ws), ws.numel(), stream_ptr(x.device)), 'dpk_coupling1d_backward')
+            ptr(ws), ws.numel(), stream_ptr(x.device))
         return gx, gW1, gb1, gW2, gb2, gact, None
 
 
@@ -525,9 +460,9 @@ class CouplingMlpFn(torch.autograd.Function):
         ctx.kept = None   # a second backward through the same node evaluates the conditioner again
         ws = kept if kept is not None else layer._ws_bwd.get(_mlp_backward_bytes(B, n - 1, widths), x.device)
         fn = lib.dpk_coupling1d_mlp_backward_inverse if ctx.inverse else lib.dpk_coupling1d_mlp_backward
-        check(fn(ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), n - 1, Wp, bp, widths, ptr(act),
-                 int(layer.affine), ptr(gu), ptr(gildj), ptr(gx), gWp, gbp, ptr(gact), int(kept is not None), ptr(ws),
-                 ws.numel(), stream_ptr(x.device)), 'dpk_coupling1d_mlp_backward')
+        call(fn, ptr(x), B, D, ptr(layer.mask), ptr(layer.inv_mask), n - 1, Wp, bp, widths, ptr(act),
+             int(layer.affine), ptr(gu), ptr(gildj), ptr(gx), gWp, gbp, ptr(gact), int(kept is not None), ptr(ws),
+             ws.numel(), stream_ptr(x.device))
         grads = []
         for gw, gb in zip(gws, gbs):
             grads += [gw, gb]
@@ -574,8 +509,7 @@ class BatchNormFn(torch.autograd.Function):
             from deeprob import parallel
             world = torch.distributed.get_world_size(group)
             mom = torch.empty(2 * D + 1, dtype=torch.float32, device=dev)
-            check(lib.dpk_bn1d_local_moments(ptr(x) if B else None, B, D, ptr(mom), stream_ptr(dev)),
-                  'dpk_bn1d_local_moments')
+            call(lib.dpk_bn1d_local_moments, ptr(x) if B else None, B, D, ptr(mom), stream_ptr(dev))
             table = parallel.bn_gather_moments(mom, group)
             n_total = int(round(float(table[:, 0].sum().item())))
             u = torch.empty_like(x)
@@ -583,11 +517,11 @@ class BatchNormFn(torch.autograd.Function):
             mean = torch.empty(D, dtype=torch.float32, device=dev)
             var = torch.empty(D, dtype=torch.float32, device=dev)
             ws = bn._ws.get(8 * D + 256, dev)
-            check(lib.dpk_bn1d_sync_forward(ptr(x) if B else None, B, D, ptr(require_device_f32(weight, 'weight')),
+            call(lib.dpk_bn1d_sync_forward, ptr(x) if B else None, B, D, ptr(require_device_f32(weight, 'weight')),
                                             ptr(require_device_f32(bias, 'bias')), ptr(table), world,
                                             ptr(bn.running_var), ptr(bn.running_mean), float(bn.momentum),
                                             float(bn.eps), ptr(u) if B else None, ptr(ldj), ptr(mean), ptr(var), ptr(ws),
-                                            ws.numel(), stream_ptr(dev)), 'dpk_bn1d_sync_forward')
+                                            ws.numel(), stream_ptr(dev))
             ctx.save_for_backward(x, weight, mean, var)
             ctx.bn, ctx.train, ctx.sync = bn, True, (group, n_total)
             return u, ldj.repeat(B)
@@ -598,11 +532,10 @@ class BatchNormFn(torch.autograd.Function):
             mean = torch.empty(D, dtype=torch.float32, device=dev)
             var = torch.empty(D, dtype=torch.float32, device=dev)
             ws = bn._ws.get(8 * D + 256, dev)
-            check(lib.dpk_bn1d_train_forward(ptr(x), B, D, ptr(require_device_f32(weight, 'weight')),
+            call(lib.dpk_bn1d_train_forward, ptr(x), B, D, ptr(require_device_f32(weight, 'weight')),
                                              ptr(require_device_f32(bias, 'bias')), ptr(bn.running_var),
                                              ptr(bn.running_mean), float(bn.momentum), float(bn.eps), ptr(u), ptr(ldj),
-                                             ptr(mean), ptr(var), ptr(ws), ws.numel(), stream_ptr(dev)),
-                  'dpk_bn1d_train_forward')
+                                             ptr(mean), ptr(var), ptr(ws), ws.numel(), stream_ptr(dev))
         else:
             affine, ldj = bn1d_fold(bn, inverse=False)
             u = affine1d(x, affine)
@@ -626,19 +559,18 @@ class BatchNormFn(torch.autograd.Function):
             from deeprob import parallel
             group, n_total = ctx.sync
             sums = torch.empty(2 * D + 1, dtype=torch.float32, device=x.device)
-            check(lib.dpk_bn1d_backward_sums(ptr(x) if B else None, ptr(gu) if B else None, ptr(gildj) if B else None,
+            call(lib.dpk_bn1d_backward_sums, ptr(x) if B else None, ptr(gu) if B else None, ptr(gildj) if B else None,
                                              B, D, ptr(mean), ptr(var), float(bn.eps), ptr(sums),
-                                             stream_ptr(x.device)), 'dpk_bn1d_backward_sums')
+                                             stream_ptr(x.device))
             sums_x = parallel.bn_reduce_sums(sums, B, n_total, group)
-            check(lib.dpk_bn1d_sync_backward(ptr(x) if B else None, ptr(gu) if B else None, B, n_total, D, ptr(weight),
+            call(lib.dpk_bn1d_sync_backward, ptr(x) if B else None, ptr(gu) if B else None, B, n_total, D, ptr(weight),
                                              ptr(mean), ptr(var), float(bn.eps), ptr(sums_x), ptr(sums),
-                                             ptr(gx) if B else None, ptr(gw), ptr(gb), stream_ptr(x.device)),
-                  'dpk_bn1d_sync_backward')
+                                             ptr(gx) if B else None, ptr(gw), ptr(gb), stream_ptr(x.device))
             return gx, gw, gb, None
         ws = bn._ws.get(4 * (2 * D + 64) + 256, x.device)
-        check(lib.dpk_bn1d_backward(ptr(x), ptr(gu), ptr(gildj), B, D, ptr(weight), ptr(mean), ptr(var),
+        call(lib.dpk_bn1d_backward, ptr(x), ptr(gu), ptr(gildj), B, D, ptr(weight), ptr(mean), ptr(var),
                                     float(bn.eps), int(ctx.train), ptr(gx), ptr(gw), ptr(gb), ptr(ws), ws.numel(),
-                                    stream_ptr(x.device)), 'dpk_bn1d_backward')
+                                    stream_ptr(x.device))
         return gx, gw, gb, None
 
 
@@ -668,9 +600,9 @@ class BatchNormInverseFn(torch.autograd.Function):
         gw = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
         gb = torch.empty_like(bias) if ctx.needs_input_grad[2] else None
         ws = bn._ws.get(4 * (5 * D + 64) + 256, u.device)
-        check(lib.dpk_bn1d_inverse_backward(ptr(u), ptr(gx), ptr(gldj), B, D, ptr(weight), ptr(bias),
+        call(lib.dpk_bn1d_inverse_backward, ptr(u), ptr(gx), ptr(gldj), B, D, ptr(weight), ptr(bias),
                                             ptr(bn.running_var), float(bn.eps), ptr(gu), ptr(gw), ptr(gb), ptr(ws),
-                                            ws.numel(), stream_ptr(u.device)), 'dpk_bn1d_inverse_backward')
+                                            ws.numel(), stream_ptr(u.device))
         return gu, gw, gb, None
 
 
@@ -693,6 +625,5 @@ class NormalBaseFn(torch.autograd.Function):
         g = require_device_f32(g, 'grad')
         B, D = u.shape
         gu = torch.empty_like(u)
-        check(lib.dpk_normal_base_backward(ptr(u), ptr(loc), ptr(scale), ptr(g), B, D, ptr(gu), stream_ptr(u.device)),
-              'dpk_normal_base_backward')
+        call(lib.dpk_normal_base_backward, ptr(u), ptr(loc), ptr(scale), ptr(g), B, D, ptr(gu), stream_ptr(u.device))
         return gu, None, None

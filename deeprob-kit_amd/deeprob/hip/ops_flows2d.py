@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr, require_device_f32, HipError
+from deeprob.hip import load_library, call, trust_versions, ptr, stream_ptr, require_device_f32, HipError
 
 
 def graph_route(x, *modules) -> bool:
@@ -65,8 +65,7 @@ def conv_tables(conv, bn=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         tensors += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
     key = _key(*tensors)
     hit = getattr(conv, '_hip_tables', None)
-    from deeprob import hip
-    if hit is not None and hit[0] == key and hip._trust_versions:
+    if hit is not None and hit[0] == key and trust_versions():
         return hit[1], hit[2]
     lib = load_library()
     v = require_device_f32(p.weight_v.detach(), 'weight_v')
@@ -88,8 +87,8 @@ def conv_tables(conv, bn=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         wpack = torch.empty(lib.dpk_conv2d_pack_floats(cout, cin, ks), dtype=torch.float32, device=v.device)
         if bn is not None:
             pre = torch.empty(2 * cin, dtype=torch.float32, device=v.device)
-    check(lib.dpk_conv2d_prepare(ptr(v), ptr(g), cout, cin, ks, ptr(bnp[0]), ptr(bnp[1]), ptr(bnp[2]), ptr(bnp[3]),
-                                 eps, ptr(wpack), ptr(pre), stream_ptr(v.device)), 'dpk_conv2d_prepare')
+    call(lib.dpk_conv2d_prepare, ptr(v), ptr(g), cout, cin, ks, ptr(bnp[0]), ptr(bnp[1]), ptr(bnp[2]), ptr(bnp[3]),
+                                 eps, ptr(wpack), ptr(pre), stream_ptr(v.device))
     conv._hip_tables = (key, wpack, pre)
     return wpack, pre
 
@@ -123,9 +122,9 @@ def conv2d(x: torch.Tensor, conv, bn=None, in_mask: Optional[torch.Tensor] = Non
     mask = None if in_mask is None else require_device_f32(in_mask, 'mask')
     if mask is not None and mask.numel() != H * W:
         raise HipError("conv2d: mask must have H*W = {} entries".format(H * W))
-    check(lib.dpk_conv2d_forward(ptr(x), x.stride(0), B, cin, H, W, ptr(wpack), cout, ks, ptr(pre), ptr(mask),
+    call(lib.dpk_conv2d_forward, ptr(x), x.stride(0), B, cin, H, W, ptr(wpack), cout, ks, ptr(pre), ptr(mask),
                                  ptr(bias), ptr(res), 0 if res is None else res.stride(0), ptr(out), out.stride(0),
-                                 stream_ptr(x.device)), 'dpk_conv2d_forward')
+                                 stream_ptr(x.device))
     return out
 
 
@@ -140,9 +139,9 @@ def coupling2d(x: torch.Tensor, z: torch.Tensor, layer, inverse: bool,
     ldj_out = torch.empty(B, dtype=torch.float32, device=x.device)
     scale = require_device_f32(layer.scale_act.weight.detach(), 'scale_act.weight').view(-1) if layer.affine else None
     inv_mask = None if layer.channelwise else require_device_f32(layer.inv_mask, 'inv_mask')
-    check(lib.dpk_coupling2d_transform(ptr(x), ptr(z), ptr(scale), ptr(inv_mask), B, C, H, W, int(layer.affine),
+    call(lib.dpk_coupling2d_transform, ptr(x), ptr(z), ptr(scale), ptr(inv_mask), B, C, H, W, int(layer.affine),
                                        int(layer.reverse), int(inverse), ptr(ldj), ptr(out), ptr(ldj_out),
-                                       stream_ptr(x.device)), 'dpk_coupling2d_transform')
+                                       stream_ptr(x.device))
     return out, ldj_out
 
 
@@ -155,8 +154,8 @@ def bn2d(x: torch.Tensor, layer, inverse: bool, ldj: Optional[torch.Tensor] = No
     ldj_out = torch.empty(B, dtype=torch.float32, device=x.device)
     w, b, m, v = (require_device_f32(t.detach(), 'batch norm').view(-1)
                   for t in (layer.weight, layer.bias, layer.running_mean, layer.running_var))
-    check(lib.dpk_bn2d_bijector(ptr(x), ptr(w), ptr(b), ptr(m), ptr(v), float(layer.eps), B, C, H, W, int(inverse),
-                                ptr(ldj), ptr(out), ptr(ldj_out), stream_ptr(x.device)), 'dpk_bn2d_bijector')
+    call(lib.dpk_bn2d_bijector, ptr(x), ptr(w), ptr(b), ptr(m), ptr(v), float(layer.eps), B, C, H, W, int(inverse),
+                                ptr(ldj), ptr(out), ptr(ldj_out), stream_ptr(x.device))
     return out, ldj_out
 
 
@@ -197,8 +196,7 @@ def space_to_depth(x: torch.Tensor, table: torch.Tensor, split: Optional[int] = 
     ca = 4 * C if split is None else split
     a = torch.empty((B, ca, H // 2, W // 2), dtype=torch.float32, device=x.device)
     b = None if split is None else torch.empty((B, 4 * C - ca, H // 2, W // 2), dtype=torch.float32, device=x.device)
-    check(lib.dpk_space_to_depth(ptr(x), B, C, H, W, ptr(table), ptr(a), ca, ptr(b), stream_ptr(x.device)),
-          'dpk_space_to_depth')
+    call(lib.dpk_space_to_depth, ptr(x), B, C, H, W, ptr(table), ptr(a), ca, ptr(b), stream_ptr(x.device))
     return a if split is None else (a, b)
 
 
@@ -218,6 +216,5 @@ def depth_to_space(a: torch.Tensor, table: torch.Tensor, b: Optional[torch.Tenso
         raise HipError("unsqueeze: the channel count {} is not a multiple of 4".format(total))
     C = total // 4
     out = torch.empty((B, C, 2 * h, 2 * w), dtype=torch.float32, device=a.device)
-    check(lib.dpk_depth_to_space(ptr(a), ca, ptr(b), B, C, 2 * h, 2 * w, ptr(table), ptr(out), stream_ptr(a.device)),
-          'dpk_depth_to_space')
+    call(lib.dpk_depth_to_space, ptr(a), ca, ptr(b), B, C, 2 * h, 2 * w, ptr(table), ptr(out), stream_ptr(a.device))
     return out

@@ -19,7 +19,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr, require_device_f32, HipError
+from deeprob.hip import load_library, call, ptr, stream_ptr, require_device_f32, HipError
 from deeprob.hip import ops_flows2d as ev
 
 
@@ -74,8 +74,7 @@ class ChannelStatsFn(torch.autograd.Function):
         if B * H * W == 0:
             raise HipError("batch statistics of an empty batch")
         sums = torch.zeros(2 * C, dtype=torch.float64, device=x.device)
-        check(lib.dpk_channel_stats(ptr(x), x.stride(0), B, C, H, W, 1, ptr(sums), stream_ptr(x.device)),
-              'dpk_channel_stats')
+        call(lib.dpk_channel_stats, ptr(x), x.stride(0), B, C, H, W, 1, ptr(sums), stream_ptr(x.device))
         n = float(B * H * W)
         ctx.group, ctx.weight = group, 1.0
         if group is not None:
@@ -102,8 +101,8 @@ class ChannelStatsFn(torch.autograd.Function):
             g = _sync_stat_grads(ctx.group, ctx.weight, torch.cat([dmean, dvar]))
             dmean, dvar = g[:C].contiguous(), g[C:].contiguous()
         dx = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
-        check(lib.dpk_channel_stats_backward(ptr(x), x.stride(0), B, C, H, W, ptr(mean), ptr(dmean), ptr(dvar), 0,
-                                             ptr(dx), stream_ptr(x.device)), 'dpk_channel_stats_backward')
+        call(lib.dpk_channel_stats_backward, ptr(x), x.stride(0), B, C, H, W, ptr(mean), ptr(dmean), ptr(dvar), 0,
+                                             ptr(dx), stream_ptr(x.device))
         return dx, None
 
 
@@ -117,8 +116,7 @@ class ChannelAffineFn(torch.autograd.Function):
         ab = require_device_f32(ab, 'ab')
         B, C, H, W = x.shape
         out = torch.empty_like(x)
-        check(lib.dpk_channel_affine_forward(ptr(x), B, C, H, W, ptr(ab), ptr(out), stream_ptr(x.device)),
-              'dpk_channel_affine_forward')
+        call(lib.dpk_channel_affine_forward, ptr(x), B, C, H, W, ptr(ab), ptr(out), stream_ptr(x.device))
         ctx.save_for_backward(x, ab)
         return out
 
@@ -130,8 +128,8 @@ class ChannelAffineFn(torch.autograd.Function):
         g = _grad_image(g)
         dx = torch.empty_like(x)
         dab = torch.zeros(2 * C, dtype=torch.float64, device=x.device)
-        check(lib.dpk_channel_affine_backward(ptr(x), x.stride(0), ptr(g), B, C, H, W, ptr(ab), 0, None, ptr(dx),
-                                              ptr(dab), stream_ptr(x.device)), 'dpk_channel_affine_backward')
+        call(lib.dpk_channel_affine_backward, ptr(x), x.stride(0), ptr(g), B, C, H, W, ptr(ab), 0, None, ptr(dx),
+                                              ptr(dab), stream_ptr(x.device))
         return dx, dab.float()
 
 
@@ -140,8 +138,8 @@ def _pack(w: torch.Tensor) -> torch.Tensor:
     lib = load_library()
     cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
     wpack = torch.empty(lib.dpk_conv2d_pack_floats(cout, cin, ks), dtype=torch.float32, device=w.device)
-    check(lib.dpk_conv2d_prepare(ptr(w), None, cout, cin, ks, None, None, None, None, 0.0, ptr(wpack), None,
-                                 stream_ptr(w.device)), 'dpk_conv2d_prepare')
+    call(lib.dpk_conv2d_prepare, ptr(w), None, cout, cin, ks, None, None, None, None, 0.0, ptr(wpack), None,
+                                 stream_ptr(w.device))
     return wpack
 
 
@@ -149,9 +147,9 @@ def _conv(x, wpack, cout, ks, pre, mask, bias, res):
     lib = load_library()
     B, cin, H, W = x.shape
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    check(lib.dpk_conv2d_forward(ptr(x), x.stride(0), B, cin, H, W, ptr(wpack), cout, ks, ptr(pre), ptr(mask),
+    call(lib.dpk_conv2d_forward, ptr(x), x.stride(0), B, cin, H, W, ptr(wpack), cout, ks, ptr(pre), ptr(mask),
                                  ptr(bias), ptr(res), 0 if res is None else res.stride(0), ptr(out), out.stride(0),
-                                 stream_ptr(x.device)), 'dpk_conv2d_forward')
+                                 stream_ptr(x.device))
     return out
 
 
@@ -191,18 +189,17 @@ class Conv2dFn(torch.autograd.Function):
             else:
                 dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
                 dab = None if pre is None else torch.zeros(2 * cin, dtype=torch.float64, device=dev)
-                check(lib.dpk_channel_affine_backward(ptr(x), x.stride(0), ptr(dh), B, cin, H, W, ptr(pre),
+                call(lib.dpk_channel_affine_backward, ptr(x), x.stride(0), ptr(dh), B, cin, H, W, ptr(pre),
                                                       int(pre is not None), ptr(mask), ptr(dx), ptr(dab),
-                                                      stream_ptr(dev)), 'dpk_channel_affine_backward')
+                                                      stream_ptr(dev))
                 dpre = None if dab is None else dab.float()
         if ctx.needs_input_grad[1]:
             dw = torch.zeros_like(w)
-            check(lib.dpk_conv2d_backward_weight(ptr(x), x.stride(0), ptr(g), B, cin, cout, H, W, ks, ptr(pre),
-                                                 ptr(mask), ptr(dw), stream_ptr(dev)), 'dpk_conv2d_backward_weight')
+            call(lib.dpk_conv2d_backward_weight, ptr(x), x.stride(0), ptr(g), B, cin, cout, H, W, ks, ptr(pre),
+                                                 ptr(mask), ptr(dw), stream_ptr(dev))
         if ctx.has_bias and ctx.needs_input_grad[2]:
             sums = torch.zeros(cout, dtype=torch.float64, device=dev)
-            check(lib.dpk_channel_stats(ptr(g), g.stride(0), B, cout, H, W, 0, ptr(sums), stream_ptr(dev)),
-                  'dpk_channel_stats')
+            call(lib.dpk_channel_stats, ptr(g), g.stride(0), B, cout, H, W, 0, ptr(sums), stream_ptr(dev))
             dbias = sums.float()
         return dx, dw, dbias, dpre, None, (g if ctx.has_res else None)
 
@@ -230,7 +227,7 @@ class BnConv2dFn(torch.autograd.Function):
         dev = x.device
         st = stream_ptr(dev)
         sums = torch.zeros(2 * cin, dtype=torch.float64, device=dev)
-        check(lib.dpk_channel_stats(ptr(x), x.stride(0), B, cin, H, W, 1, ptr(sums), st), 'dpk_channel_stats')
+        call(lib.dpk_channel_stats, ptr(x), x.stride(0), B, cin, H, W, 1, ptr(sums), st)
         pre = torch.empty(2 * cin, dtype=torch.float32, device=dev)
         stat = torch.empty(2 * cin, dtype=torch.float32, device=dev)
         bn.num_batches_tracked.add_(1)
@@ -239,9 +236,8 @@ class BnConv2dFn(torch.autograd.Function):
         ctx.group, ctx.weight = getattr(bn, 'sync_group', None), 1.0
         if ctx.group is not None:       # statistics of the whole sharded batch (deeprob.parallel.synchronize_batchnorm)
             n_elems, ctx.weight = _sync_counts(ctx.group, B, H * W, sums)
-        check(lib.dpk_bn2d_fold_train(ptr(sums), n_elems, cin, ptr(gamma), ptr(beta), float(bn.eps), float(momentum),
-                                      ptr(bn.running_mean), ptr(bn.running_var), ptr(pre), ptr(stat), st),
-              'dpk_bn2d_fold_train')
+        call(lib.dpk_bn2d_fold_train, ptr(sums), n_elems, cin, ptr(gamma), ptr(beta), float(bn.eps), float(momentum),
+                                      ptr(bn.running_mean), ptr(bn.running_var), ptr(pre), ptr(stat), st)
         bias = None if bias is None else require_device_f32(bias, 'bias')
         mask = None if mask is None else require_device_f32(mask, 'mask')
         res = None if res is None else ev._image(res, 'res')
@@ -263,24 +259,23 @@ class BnConv2dFn(torch.autograd.Function):
         dh = _conv(g, _pack(wt), cin, ks, None, None, None, None)
         dx = torch.empty((B, cin, H, W), dtype=torch.float32, device=dev)
         dab = torch.zeros(2 * cin, dtype=torch.float64, device=dev)
-        check(lib.dpk_channel_affine_backward(ptr(x), x.stride(0), ptr(dh), B, cin, H, W, ptr(pre), 1, ptr(mask), ptr(dx),
-                                              ptr(dab), st), 'dpk_channel_affine_backward')
+        call(lib.dpk_channel_affine_backward, ptr(x), x.stride(0), ptr(dh), B, cin, H, W, ptr(pre), 1, ptr(mask), ptr(dx),
+                                              ptr(dab), st)
         small = torch.empty(4 * cin, dtype=torch.float32, device=dev)     # dgamma | dbeta | dmean | dvar
         dgamma, dbeta, dstat = small[:cin], small[cin:2 * cin], small[2 * cin:]
-        check(lib.dpk_bn2d_fold_backward(ptr(dab), cin, ptr(gamma), ptr(stat), ptr(dgamma), ptr(dbeta), ptr(dstat), st),
-              'dpk_bn2d_fold_backward')
+        call(lib.dpk_bn2d_fold_backward, ptr(dab), cin, ptr(gamma), ptr(stat), ptr(dgamma), ptr(dbeta), ptr(dstat), st)
         if ctx.group is not None:
             dstat = _sync_stat_grads(ctx.group, ctx.weight, dstat)
-        check(lib.dpk_channel_stats_backward(ptr(x), x.stride(0), B, cin, H, W, ptr(stat), ptr(dstat), ptr(dstat[cin:]),
-                                             1, ptr(dx), st), 'dpk_channel_stats_backward')
+        call(lib.dpk_channel_stats_backward, ptr(x), x.stride(0), B, cin, H, W, ptr(stat), ptr(dstat), ptr(dstat[cin:]),
+                                             1, ptr(dx), st)
         dw = dbias = None
         if ctx.needs_input_grad[3]:
             dw = torch.zeros_like(w)
-            check(lib.dpk_conv2d_backward_weight(ptr(x), x.stride(0), ptr(g), B, cin, cout, H, W, ks, ptr(pre), ptr(mask),
-                                                 ptr(dw), st), 'dpk_conv2d_backward_weight')
+            call(lib.dpk_conv2d_backward_weight, ptr(x), x.stride(0), ptr(g), B, cin, cout, H, W, ks, ptr(pre), ptr(mask),
+                                                 ptr(dw), st)
         if ctx.has_bias and ctx.needs_input_grad[4]:
             sums = torch.zeros(cout, dtype=torch.float64, device=dev)
-            check(lib.dpk_channel_stats(ptr(g), g.stride(0), B, cout, H, W, 0, ptr(sums), st), 'dpk_channel_stats')
+            call(lib.dpk_channel_stats, ptr(g), g.stride(0), B, cout, H, W, 0, ptr(sums), st)
             dbias = sums.float()
         return dx, dgamma, dbeta, dw, dbias, None, (g if ctx.has_res else None), None
 
@@ -363,9 +358,8 @@ class CouplingTransformFn(torch.autograd.Function):
         out = torch.empty_like(x)
         ldj = torch.empty(B, dtype=torch.float32, device=x.device)
         sc = None if scale is None else require_device_f32(scale, 'scale_act.weight').view(-1)
-        check(lib.dpk_coupling2d_transform(ptr(x), ptr(z), ptr(sc), ptr(inv_mask), B, C, H, W, int(affine), int(reverse),
-                                           0, None, ptr(out), ptr(ldj), stream_ptr(x.device)),
-              'dpk_coupling2d_transform')
+        call(lib.dpk_coupling2d_transform, ptr(x), ptr(z), ptr(sc), ptr(inv_mask), B, C, H, W, int(affine), int(reverse),
+                                           0, None, ptr(out), ptr(ldj), stream_ptr(x.device))
         ctx.save_for_backward(x, z, sc, inv_mask)
         ctx.affine, ctx.reverse = affine, reverse
         ctx.scale_shape = None if scale is None else scale.shape
@@ -381,10 +375,9 @@ class CouplingTransformFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dz = torch.empty_like(z)
         dscale = None if sc is None else torch.zeros(sc.numel(), dtype=torch.float64, device=x.device)
-        check(lib.dpk_coupling2d_transform_backward(ptr(x), ptr(z), ptr(sc), ptr(inv_mask), B, C, H, W, int(ctx.affine),
+        call(lib.dpk_coupling2d_transform_backward, ptr(x), ptr(z), ptr(sc), ptr(inv_mask), B, C, H, W, int(ctx.affine),
                                                     int(ctx.reverse), ptr(gout), ptr(gldj), ptr(dx), ptr(dz),
-                                                    ptr(dscale), stream_ptr(x.device)),
-              'dpk_coupling2d_transform_backward')
+                                                    ptr(dscale), stream_ptr(x.device))
         return dx, dz, (None if dscale is None else dscale.float().reshape(ctx.scale_shape)), None, None, None
 
 

@@ -26,7 +26,7 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr, require_device_f32, HipError
+from deeprob.hip import load_library, call, ptr, stream_ptr, require_device_f32, HipError
 
 FUSED_MAX_UNITS = 256
 SAMPLE_MAX_UNITS = 128
@@ -76,10 +76,7 @@ def _chain_arrays(W, M, b):
 
 
 def _chain_bytes(B: int, D: int, widths, mode: int) -> int:
-    n = load_library().dpk_maf_chain_workspace_bytes(B, D, len(widths) - 1, widths, mode)
-    if n < 0:
-        check(int(n), 'dpk_maf_chain_workspace_bytes')
-    return int(n)
+    return int(call(load_library().dpk_maf_chain_workspace_bytes, B, D, len(widths) - 1, widths, mode))
 
 
 def _check_input(x: torch.Tensor, layer, name: str) -> torch.Tensor:
@@ -190,9 +187,8 @@ def density_chain(x: torch.Tensor, layer, ws: torch.Tensor = None) -> Tuple[torc
     u = torch.empty_like(x)
     ildj = torch.empty(B, dtype=torch.float32, device=x.device)
     act_w = require_device_f32(layer.scale_act.weight, 'scale_act.weight')
-    check(lib.dpk_maf_density_chain(ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
-                                    ptr(u), ptr(ildj), ptr(ws), ws.numel(), stream_ptr(x.device)),
-          'dpk_maf_density_chain')
+    call(lib.dpk_maf_density_chain, ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
+                                    ptr(u), ptr(ildj), ptr(ws), ws.numel(), stream_ptr(x.device))
     return u, ildj
 
 
@@ -213,10 +209,7 @@ def density_fused(x: torch.Tensor, layer, in_affine=None, ildj: torch.Tensor = N
     B, D = x.shape
     lins, W, M, b = _params(layer)
     units = W[0].shape[0]
-    n = lib.dpk_maf_density_workspace_bytes(D, units)
-    if n < 0:
-        check(int(n), 'dpk_maf_density_workspace_bytes')
-    ws = layer._ws.get(n, x.device)
+    ws = layer._ws.sized(lib.dpk_maf_density_workspace_bytes, D, units, device=x.device)
     i_ord, h_ord, o_ord = _orders(layer, M[0], M[1])
     u = torch.empty_like(x)
     accumulate = ildj is not None
@@ -224,10 +217,10 @@ def density_fused(x: torch.Tensor, layer, in_affine=None, ildj: torch.Tensor = N
         ildj = torch.empty(B, dtype=torch.float32, device=x.device)
     sc, sh = in_affine if in_affine is not None else (None, None)
     act_w = require_device_f32(layer.scale_act.weight, 'scale_act.weight')
-    check(lib.dpk_maf_density_forward(ptr(x), B, D, ptr(W[0]), ptr(M[0]), ptr(b[0]), ptr(W[1]), ptr(M[1]), ptr(b[1]),
+    call(lib.dpk_maf_density_forward, ptr(x), B, D, ptr(W[0]), ptr(M[0]), ptr(b[0]), ptr(W[1]), ptr(M[1]), ptr(b[1]),
                                       units, _activation(layer), ptr(act_w), ptr(sc), ptr(sh), ptr(i_ord), ptr(h_ord),
                                       ptr(o_ord), ptr(u), ptr(ildj), int(accumulate), ptr(ws), ws.numel(),
-                                      stream_ptr(x.device)), 'dpk_maf_density_forward')
+                                      stream_ptr(x.device))
     return u, ildj
 
 
@@ -272,10 +265,9 @@ def _chain_backward(layer, x, act_w, params, gu, gildj, gZ, ws, need):
     gu = require_device_f32(gu, 'grad_u') if gu is not None else None
     gildj = require_device_f32(gildj, 'grad_ildj') if gildj is not None else None
     gZ = require_device_f32(gZ, 'grad_z') if gZ is not None else None
-    check(lib.dpk_maf_density_chain_backward(ptr(x), B, D, n - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
+    call(lib.dpk_maf_density_chain_backward, ptr(x), B, D, n - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
                                              ptr(gu), ptr(gildj), ptr(gZ), ptr(gx), gWp, gbp, ptr(gact), int(holds),
-                                             ptr(ws), ws.numel(), stream_ptr(x.device)),
-          'dpk_maf_density_chain_backward')
+                                             ptr(ws), ws.numel(), stream_ptr(x.device))
     grads = []
     for gw, gb in zip(gws, gbs):
         grads += [gw, gb]
@@ -336,8 +328,8 @@ class MafConditionerFn(torch.autograd.Function):
         Wp, Mp, bp, widths = _chain_arrays(W, M, b)
         ws = torch.empty(_chain_bytes(B, D, widths, CHAIN_BACKWARD), dtype=torch.uint8, device=x.device)
         z = torch.empty(B, 2 * D, dtype=torch.float32, device=x.device)
-        check(lib.dpk_maf_conditioner_forward(ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(z),
-                                              ptr(ws), ws.numel(), stream_ptr(x.device)), 'dpk_maf_conditioner_forward')
+        call(lib.dpk_maf_conditioner_forward, ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(z),
+                                              ptr(ws), ws.numel(), stream_ptr(x.device))
         ctx.save_for_backward(x, *params)
         ctx.layer, ctx.ws = layer, ws
         return z
@@ -362,8 +354,8 @@ def conditioner(x: torch.Tensor, layer) -> torch.Tensor:
     Wp, Mp, bp, widths = _chain_arrays(W, M, b)
     ws = layer._ws.get(_chain_bytes(B, D, widths, CHAIN_CONDITIONER), x.device)
     z = torch.empty(B, 2 * D, dtype=torch.float32, device=x.device)
-    check(lib.dpk_maf_conditioner_forward(ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(z),
-                                          ptr(ws), ws.numel(), stream_ptr(x.device)), 'dpk_maf_conditioner_forward')
+    call(lib.dpk_maf_conditioner_forward, ptr(x), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(z),
+                                          ptr(ws), ws.numel(), stream_ptr(x.device))
     return z
 
 
@@ -411,17 +403,14 @@ def sample_deep_kernel(u: torch.Tensor, layer) -> Tuple[torch.Tensor, torch.Tens
     B, D = u.shape
     lins, W, M, b = _params(layer)
     Wp, Mp, bp, widths = _chain_arrays(W, M, b)
-    n = lib.dpk_maf_sample_deep_workspace_bytes(D, len(W) - 1, widths)
-    if n < 0:
-        check(int(n), 'dpk_maf_sample_deep_workspace_bytes')
-    ws = layer._ws_sample.get(n, u.device)
+    ws = layer._ws_sample.sized(lib.dpk_maf_sample_deep_workspace_bytes, D, len(W) - 1, widths, device=u.device)
     ev_ptr, ev = deep_schedule(layer)
     x = torch.empty_like(u)
     ldj = torch.empty(B, dtype=torch.float32, device=u.device)
     act_w = require_device_f32(layer.scale_act.weight, 'scale_act.weight')
-    check(lib.dpk_maf_sample_deep_forward(ptr(u), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
+    call(lib.dpk_maf_sample_deep_forward, ptr(u), B, D, len(W) - 1, Wp, Mp, bp, widths, _activation(layer), ptr(act_w),
                                           ptr(_step_order(layer, u.device)), ptr(ev_ptr), ptr(ev), ptr(x), ptr(ldj),
-                                          ptr(ws), ws.numel(), stream_ptr(u.device)), 'dpk_maf_sample_deep_forward')
+                                          ptr(ws), ws.numel(), stream_ptr(u.device))
     return x, ldj
 
 
@@ -431,16 +420,13 @@ def sample_kernel(u: torch.Tensor, layer) -> Tuple[torch.Tensor, torch.Tensor]:
     B, D = u.shape
     lins, W, M, b = _params(layer)
     units = W[0].shape[0]
-    n = lib.dpk_maf_sample_workspace_bytes(D, units)
-    if n < 0:
-        check(int(n), 'dpk_maf_sample_workspace_bytes')
-    ws = layer._ws_sample.get(n, u.device)
+    ws = layer._ws_sample.sized(lib.dpk_maf_sample_workspace_bytes, D, units, device=u.device)
     x = torch.empty_like(u)
     ldj = torch.empty(B, dtype=torch.float32, device=u.device)
     act_w = require_device_f32(layer.scale_act.weight, 'scale_act.weight')
-    check(lib.dpk_maf_sample_forward(ptr(u), B, D, ptr(W[0]), ptr(M[0]), ptr(b[0]), ptr(W[1]), ptr(M[1]), ptr(b[1]),
+    call(lib.dpk_maf_sample_forward, ptr(u), B, D, ptr(W[0]), ptr(M[0]), ptr(b[0]), ptr(W[1]), ptr(M[1]), ptr(b[1]),
                                      units, _activation(layer), ptr(act_w), ptr(_step_order(layer, u.device)), ptr(x),
-                                     ptr(ldj), ptr(ws), ws.numel(), stream_ptr(u.device)), 'dpk_maf_sample_forward')
+                                     ptr(ldj), ptr(ws), ws.numel(), stream_ptr(u.device))
     return x, ldj
 
 
@@ -463,14 +449,11 @@ class MaskedLinearFn(torch.autograd.Function):
         lib = load_library()
         B, fin = x.shape
         fout = W.shape[0]
-        n = lib.dpk_masked_linear_workspace_bytes(fin, fout)
-        if n < 0:
-            check(int(n), 'dpk_masked_linear_workspace_bytes')
-        ws = torch.empty(n, dtype=torch.uint8, device=x.device)
+        ws = torch.empty(call(lib.dpk_masked_linear_workspace_bytes, fin, fout), dtype=torch.uint8, device=x.device)
         y = torch.empty(B, fout, dtype=torch.float32, device=x.device)
         mask = require_device_f32(lin.mask, 'mask')
-        check(lib.dpk_masked_linear_forward(ptr(x), B, fin, fout, ptr(W), ptr(mask), ptr(b), ptr(y), ptr(ws), ws.numel(),
-                                            stream_ptr(x.device)), 'dpk_masked_linear_forward')
+        call(lib.dpk_masked_linear_forward, ptr(x), B, fin, fout, ptr(W), ptr(mask), ptr(b), ptr(y), ptr(ws), ws.numel(),
+                                            stream_ptr(x.device))
         ctx.save_for_backward(x, W, mask)
         ctx.has_b = b is not None
         return y
@@ -487,8 +470,8 @@ class MaskedLinearFn(torch.autograd.Function):
         gW = torch.empty_like(W) if need[1] else None
         gb = torch.empty(fout, dtype=torch.float32, device=x.device) if (need[2] and ctx.has_b) else None
         ws = torch.empty(lib.dpk_masked_linear_workspace_bytes(fin, fout), dtype=torch.uint8, device=x.device)
-        check(lib.dpk_masked_linear_backward(ptr(x), B, fin, fout, ptr(W), ptr(mask), ptr(gy), ptr(gx), ptr(gW), ptr(gb),
-                                             ptr(ws), ws.numel(), stream_ptr(x.device)), 'dpk_masked_linear_backward')
+        call(lib.dpk_masked_linear_backward, ptr(x), B, fin, fout, ptr(W), ptr(mask), ptr(gy), ptr(gx), ptr(gW), ptr(gb),
+                                             ptr(ws), ws.numel(), stream_ptr(x.device))
         return gx, gW, gb, None
 
 

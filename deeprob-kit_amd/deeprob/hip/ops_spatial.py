@@ -7,9 +7,10 @@ import ctypes
 
 import torch
 
-from deeprob.hip import (load_library, check, ptr, stream_ptr, require_device_f32, Workspace, DPK_FLAG_PARAMS_CACHED,
-                         DPK_FLAG_IN_PIXEL_MAJOR, DPK_FLAG_OUT_PIXEL_MAJOR,
-                         cached_tables_flag)
+from deeprob.hip import (load_library, call, check, ptr, stream_ptr, require_device_f32, Workspace, tensors_key,
+                         trust_versions, prepare_begin, prepare_commit, prepare_release, DPK_EUNSUPPORTED,
+                         DPK_FLAG_PARAMS_CACHED, DPK_FLAG_IN_PIXEL_MAJOR, DPK_FLAG_OUT_PIXEL_MAJOR,
+                         SpatialTablesArgs as _SpatialTablesArgs)
 
 
 class SpatialGaussianFn(torch.autograd.Function):
@@ -27,12 +28,11 @@ class SpatialGaussianFn(torch.autograd.Function):
         K = loc_c.shape[0]
         out = torch.empty((B, K, H, W), dtype=torch.float32, device=x.device)
         if rate > 0.0:
-            check(lib.dpk_spatial_gaussian_forward_dropout(ptr(x), ptr(loc_c), ptr(scale_c), B, K, C, H, W, float(rate),
-                                                           seed, ptr(out), stream_ptr(x.device)),
-                  'dpk_spatial_gaussian_forward_dropout')
+            call(lib.dpk_spatial_gaussian_forward_dropout, ptr(x), ptr(loc_c), ptr(scale_c), B, K, C, H, W, float(rate),
+                                                           seed, ptr(out), stream_ptr(x.device))
         else:
-            check(lib.dpk_spatial_gaussian_forward(ptr(x), ptr(loc_c), ptr(scale_c), B, K, C, H, W, ptr(out),
-                                                   stream_ptr(x.device)), 'dpk_spatial_gaussian_forward')
+            call(lib.dpk_spatial_gaussian_forward, ptr(x), ptr(loc_c), ptr(scale_c), B, K, C, H, W, ptr(out),
+                                                   stream_ptr(x.device))
         ctx.save_for_backward(x, loc_c, scale_c)
         ctx.drop = (float(rate), seed)
         return out
@@ -48,9 +48,8 @@ class SpatialGaussianFn(torch.autograd.Function):
         gl = torch.empty_like(loc) if ctx.needs_input_grad[1] else None
         gs = torch.empty_like(scale) if ctx.needs_input_grad[2] else None
         rate, seed = ctx.drop
-        check(lib.dpk_spatial_gaussian_backward_dropout(ptr(x), ptr(g), ptr(loc), ptr(scale), B, K, C, H, W, rate, seed,
-                                                        ptr(gl), ptr(gs), ptr(gx), stream_ptr(x.device)),
-              'dpk_spatial_gaussian_backward_dropout')
+        call(lib.dpk_spatial_gaussian_backward_dropout, ptr(x), ptr(g), ptr(loc), ptr(scale), B, K, C, H, W, rate, seed,
+                                                        ptr(gl), ptr(gs), ptr(gx), stream_ptr(x.device))
         return gx, gl, gs, None, None
 
 
@@ -75,8 +74,7 @@ class SpatialProductFn(torch.autograd.Function):
             raise ValueError(f"expected input [B, {layer.in_features}], got {tuple(x.shape)}")
         B = x.shape[0]
         out = torch.empty((B,) + tuple(layer.out_features), dtype=torch.float32, device=x.device)
-        check(lib.dpk_spatial_product_forward(ptr(x), B, *geom, ptr(out), stream_ptr(x.device)),
-              'dpk_spatial_product_forward')
+        call(lib.dpk_spatial_product_forward, ptr(x), B, *geom, ptr(out), stream_ptr(x.device))
         ctx.geom = geom
         ctx.in_shape = x.shape
         return out
@@ -86,17 +84,12 @@ class SpatialProductFn(torch.autograd.Function):
         lib = load_library()
         g = require_device_f32(g, 'grad')
         gin = torch.empty(ctx.in_shape, dtype=torch.float32, device=g.device)
-        check(lib.dpk_spatial_product_backward(ptr(g), ctx.in_shape[0], *ctx.geom, ptr(gin), stream_ptr(g.device)),
-              'dpk_spatial_product_backward')
+        call(lib.dpk_spatial_product_backward, ptr(g), ctx.in_shape[0], *ctx.geom, ptr(gin), stream_ptr(g.device))
         return gin, None
 
 
 def _spatial_sum_ws(ws: Workspace, Cin, Cout, H, W, device):
-    lib = load_library()
-    n = lib.dpk_spatial_sum_workspace_bytes(Cin, Cout, H, W)
-    if n < 0:
-        check(int(n), 'dpk_spatial_sum_workspace_bytes')
-    return ws.get(n, device)
+    return ws.sized(load_library().dpk_spatial_sum_workspace_bytes, Cin, Cout, H, W, device=device)
 
 
 class SpatialSumFn(torch.autograd.Function):
@@ -113,9 +106,9 @@ class SpatialSumFn(torch.autograd.Function):
         Cout = w.shape[0]
         out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
         buf = _spatial_sum_ws(ws, Cin, Cout, H, W, x.device)
-        ws.params_key = None   # (the folded eval route caches its tables in the same workspace)
-        check(lib.dpk_spatial_sum_forward(ptr(x), ptr(w), B, Cin, Cout, H, W, ptr(out), ptr(buf), buf.numel(),
-                                          stream_ptr(x.device)), 'dpk_spatial_sum_forward')
+        ws.forget_tables()   # (the folded eval route caches its tables in the same workspace)
+        call(lib.dpk_spatial_sum_forward, ptr(x), ptr(w), B, Cin, Cout, H, W, ptr(out), ptr(buf), buf.numel(),
+                                          stream_ptr(x.device))
         ctx.save_for_backward(x, w, out)
         ctx.ws = ws
         return out
@@ -130,44 +123,33 @@ class SpatialSumFn(torch.autograd.Function):
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         buf = _spatial_sum_ws(ctx.ws, Cin, Cout, H, W, x.device)
-        ctx.ws.params_key = None
-        check(lib.dpk_spatial_sum_backward(ptr(x), ptr(w), ptr(out), ptr(g), B, Cin, Cout, H, W, ptr(gx), ptr(gw),
-                                           ptr(buf), buf.numel(), stream_ptr(x.device)),
-              'dpk_spatial_sum_backward')
+        ctx.ws.forget_tables()
+        call(lib.dpk_spatial_sum_backward, ptr(x), ptr(w), ptr(out), ptr(g), B, Cin, Cout, H, W, ptr(gx), ptr(gw),
+                                           ptr(buf), buf.numel(), stream_ptr(x.device))
         return gx, gw, None
 
 
 # ---- one table launch per DgcSpn.forward (round 3) ----------------------------------------------------------------------
 # DgcSpn.forward (evaluation) calls tables_prepare once with the levels its loop is about to take: their softmaxed-weight
 # tables (and the root's log-softmax rows) are rebuilt by ONE launch (dpk_spatial_tables) -- rebuilding is the check of
-# these tables, see _tables_flag -- and the level operators below recognise the forward's token and pass
+# these tables, see _tables_key -- and the level operators below recognise the forward's token (hip.prepare_begin) and pass
 # DPK_FLAG_PARAMS_CACHED instead of launching a softmax kernel each.
-_prep_token = None
+tables_release = prepare_release
 
 
-class _SpatialTablesArgs(ctypes.Structure):     # dpk_spatial_tables_args
-    _fields_ = [('sum_weight', ctypes.c_void_p), ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_int64),
-                ('root_weight', ctypes.c_void_p), ('C', ctypes.c_int32), ('Cout', ctypes.c_int32), ('OHW', ctypes.c_int32),
-                ('K', ctypes.c_int32), ('M', ctypes.c_int32)]
-
-
-def _weights_key(route, *weights):
-    return (route,) + tuple((w.data_ptr(), tuple(w.shape), w._version) for w in weights)
-
-
-def tables_release():
-    global _prep_token
-    _prep_token = None
+def _tables_key(route: str, *weights) -> tuple:
+    """Key of the softmaxed-weight tables the entry point ``route`` builds from these very tensors.  Workspace.tables_flag
+    turns it into the cached-tables flag (checked on the device by default, so that a write through ``weight.data`` is
+    seen), or DPK_FLAG_PARAMS_CACHED when this forward's tables_prepare rebuilt them."""
+    return (route, tensors_key(*weights))
 
 
 def tables_prepare(levels, x: torch.Tensor):
     """levels: [('prodsum', product layer, sum layer)] ... optionally ending with ('sumprodroot', product layer, sum
     layer, last product layer, root layer) -- what DgcSpn.forward is about to evaluate through spatial_prodsum /
     spatial_sumprodroot.  No-op when the version counters are trusted (unchanged tables are not rebuilt then)."""
-    global _prep_token
-    _prep_token = None
-    from deeprob import hip
-    if hip._trust_versions or not x.is_cuda or not levels or len(levels) > 8:
+    token = prepare_begin()
+    if trust_versions() or not x.is_cuda or not levels or len(levels) > 8:
         return
     lib = load_library()
     dev, B = x.device, x.shape[0]
@@ -184,7 +166,7 @@ def tables_prepare(levels, x: torch.Tensor):
         if lv[0] == 'prodsum':
             ws = sm._ws
             buf = _spatial_sum_ws(ws, C, Cout, OH, OW, dev)
-            key = _weights_key('prodsum', w)
+            key = _tables_key('prodsum', w)
             entries.append(_SpatialTablesArgs(ptr(w), ptr(buf), buf.numel(), None, C, Cout, OH * OW, 0, 0))
         else:
             prod6, root = lv[3], lv[4]
@@ -197,45 +179,28 @@ def tables_prepare(levels, x: torch.Tensor):
                 continue
             g5 = (ctypes.c_int32 * 10)(OH, OW, kh, kw, sh, sw, dh, dw, pt, pl)
             g6 = (ctypes.c_int32 * 10)(OH6, OW6, kh6, kw6, sh6, sw6, dh6, dw6, pt6, pl6)
-            n = lib.dpk_spatial_sumprodroot_workspace_bytes_batch(B, C, H, W, g5, Cout, g6, K)
-            if n < 0:   # (DPK_EUNSUPPORTED: outside dpk_spatial_sumprodroot_forward's envelope -- the library's answer, no copy of its constants here)
+            buf = root._ws3.sized(lib.dpk_spatial_sumprodroot_workspace_bytes_batch, B, C, H, W, g5, Cout, g6, K, device=dev,
+                                  or_none=True)
+            if buf is None:   # (DPK_EUNSUPPORTED: outside dpk_spatial_sumprodroot_forward's envelope -- the library's answer, no copy of its constants here)
                 # outside the last-level kernel (wide models): the forward will run this level through spatial_prodsum --
                 # its tables join this launch instead of costing one of their own
                 ws = sm._ws
                 buf = _spatial_sum_ws(ws, C, Cout, OH, OW, dev)
-                key = _weights_key('prodsum', w)
+                key = _tables_key('prodsum', w)
                 entries.append(_SpatialTablesArgs(ptr(w), ptr(buf), buf.numel(), None, C, Cout, OH * OW, 0, 0))
                 marked.append((ws, key))
                 continue
             ws = root._ws3
-            buf = ws.get(n, dev)
-            key = _weights_key('sumprodroot', w, wr)
+            key = _tables_key('sumprodroot', w, wr)
             entries.append(_SpatialTablesArgs(ptr(w), ptr(buf), buf.numel(), ptr(wr), C, Cout, OH * OW, K, wr.shape[1]))
         marked.append((ws, key))
     if not entries:
         return
     arr = (_SpatialTablesArgs * len(entries))(*entries)
-    check(lib.dpk_spatial_tables(len(entries), ctypes.cast(arr, ctypes.c_void_p), stream_ptr(dev)), 'dpk_spatial_tables')
-    token = object()
+    call(lib.dpk_spatial_tables, len(entries), ctypes.cast(arr, ctypes.c_void_p), stream_ptr(dev))
     for ws, key in marked:
-        ws.params_key = key
-        ws._prep_token = token
-        ws._prep_key = key
-    _prep_token = token
-
-
-def _tables_flag(ws: Workspace, route: str, *weights) -> int:
-    """The cached-tables flag (``hip.cached_tables_flag``: checked on the device by default, so that a write through
-    ``weight.data`` is seen) when the workspace's softmaxed-weight tables were built by an earlier call of the same entry
-    point from these very tensors (address, shape, version counter; Workspace.get() drops the key when the buffer is
-    replaced)."""
-    key = (route,) + tuple((w.data_ptr(), tuple(w.shape), w._version) for w in weights)
-    if _prep_token is not None and getattr(ws, '_prep_token', None) is _prep_token and getattr(ws, '_prep_key', None) == key:
-        return DPK_FLAG_PARAMS_CACHED      # rebuilt by this forward's tables_prepare
-    if ws.params_key == key:
-        return cached_tables_flag()
-    ws.params_key = key
-    return 0
+        ws.tables_built(key, token)
+    prepare_commit(token)
 
 
 def _is_pixel_major(x: torch.Tensor) -> bool:
@@ -291,18 +256,13 @@ def spatial_prodsum(x, prod_layer, weight, ws: Workspace, out_pixel_major: bool 
     else:
         out = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device)
     buf = _spatial_sum_ws(ws, C, Cout, OH, OW, x.device)
-    flags = _tables_flag(ws, 'prodsum', w) | (DPK_FLAG_IN_PIXEL_MAJOR if in_pm else 0) | \
+    flags = ws.tables_flag(_tables_key('prodsum', w)) | (DPK_FLAG_IN_PIXEL_MAJOR if in_pm else 0) | \
         (DPK_FLAG_OUT_PIXEL_MAJOR if out_pixel_major else 0)
     rc = lib.dpk_spatial_prodsum_forward(ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), Cout,
                                          ptr(out), ptr(buf), buf.numel(), flags, stream_ptr(x.device))
-    if rc == -4 and (in_pm or out_pixel_major):      # (e.g. a misaligned view: the plain layout once more)
+    if rc == DPK_EUNSUPPORTED and (in_pm or out_pixel_major):      # (e.g. a misaligned view: the plain layout once more)
         return spatial_prodsum(x.contiguous(), prod_layer, weight, ws)
-    if rc:
-        ws.params_key = None
-    if rc == -4:  # DPK_EUNSUPPORTED
-        return None
-    check(rc, 'dpk_spatial_prodsum_forward')
-    return out
+    return ws.outcome(rc, lib.dpk_spatial_prodsum_forward, out)
 
 
 def spatial_leaf_prodsum(x, leaf_layer, prod_layer, weight, ws: Workspace, out_pixel_major: bool = False):
@@ -327,17 +287,12 @@ def spatial_leaf_prodsum(x, leaf_layer, prod_layer, weight, ws: Workspace, out_p
     else:
         out = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device)
     buf = _spatial_sum_ws(ws, C, Cout, OH, OW, x.device)
-    flags = _tables_flag(ws, 'prodsum', w) | (DPK_FLAG_OUT_PIXEL_MAJOR if out_pixel_major else 0)
+    flags = ws.tables_flag(_tables_key('prodsum', w)) | (DPK_FLAG_OUT_PIXEL_MAJOR if out_pixel_major else 0)
     rc = lib.dpk_spatial_leaf_prodsum_forward(ptr(x), ptr(loc), ptr(scale), B, Cx, K, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt,
                                               pl, ptr(w), Cout, ptr(out), ptr(buf), buf.numel(), flags, stream_ptr(x.device))
-    if rc == -4 and out_pixel_major:     # (not on the streaming route: the plain layout once more)
+    if rc == DPK_EUNSUPPORTED and out_pixel_major:     # (not on the streaming route: the plain layout once more)
         return spatial_leaf_prodsum(x, leaf_layer, prod_layer, weight, ws)
-    if rc:
-        ws.params_key = None
-    if rc == -4:  # DPK_EUNSUPPORTED
-        return None
-    check(rc, 'dpk_spatial_leaf_prodsum_forward')
-    return out
+    return ws.outcome(rc, lib.dpk_spatial_leaf_prodsum_forward, out)
 
 
 class SpatialProdSumFn(torch.autograd.Function):
@@ -355,10 +310,9 @@ class SpatialProdSumFn(torch.autograd.Function):
         B, Cout = x.shape[0], w.shape[0]
         out = torch.empty((B, Cout, OH, OW), dtype=torch.float32, device=x.device)
         buf = _spatial_sum_ws(ws, C, Cout, OH, OW, x.device)
-        flags = _tables_flag(ws, 'prodsum', w)   # (same tables as the evaluation route builds)
-        check(lib.dpk_spatial_prodsum_forward(ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), Cout,
-                                              ptr(out), ptr(buf), buf.numel(), flags, stream_ptr(x.device)),
-              'dpk_spatial_prodsum_forward')
+        flags = ws.tables_flag(_tables_key('prodsum', w))   # (same tables as the evaluation route builds)
+        call(lib.dpk_spatial_prodsum_forward, ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), Cout,
+                                              ptr(out), ptr(buf), buf.numel(), flags, stream_ptr(x.device))
         ctx.save_for_backward(x, w, out)
         ctx.geom, ctx.ws = geom, ws
         return out
@@ -377,12 +331,12 @@ class SpatialProdSumFn(torch.autograd.Function):
         # the forward's tables (softmax(W), log softmax(W)) are still there unless the weight or the workspace changed.
         # "Believed current -- check on the device" becomes "current" here: the gradient wanted is that of the function the
         # forward evaluated, with the tables IT used (a rebuild was five softmax launches per DGC-SPN step, 42 us of 840)
-        flags = _tables_flag(ctx.ws, 'prodsum', w)
+        flags = ctx.ws.tables_flag(_tables_key('prodsum', w))
         if flags:
             flags = DPK_FLAG_PARAMS_CACHED
-        check(lib.dpk_spatial_prodsum_backward(ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), Cout,
+        call(lib.dpk_spatial_prodsum_backward, ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), Cout,
                                                ptr(out), ptr(g), ptr(gprod), ptr(gx), ptr(gw), ptr(buf), buf.numel(),
-                                               flags, stream_ptr(x.device)), 'dpk_spatial_prodsum_backward')
+                                               flags, stream_ptr(x.device))
         return gx, gw, None, None
 
 
@@ -412,16 +366,13 @@ def spatial_prodroot(x, prod_layer, weight, ws: Workspace):
     B, K = x.shape[0], w.shape[0]
     if w.shape[1] != C * OH * OW:
         raise ValueError("root weight does not match the product layer's output")
-    n = lib.dpk_spatial_prodroot_workspace_bytes(C, OH, OW, K)
-    if n < 0:
-        check(int(n), 'dpk_spatial_prodroot_workspace_bytes')
-    buf = ws.get(n, x.device)
+    buf = ws.sized(lib.dpk_spatial_prodroot_workspace_bytes, C, OH, OW, K, device=x.device)
     out = torch.empty((B, K), dtype=torch.float32, device=x.device)
     rc = lib.dpk_spatial_prodroot_forward(ptr(x), B, C, H, W, OH, OW, kh, kw, sh, sw, dh, dw, pt, pl, ptr(w), K,
                                           ptr(out), ptr(buf), buf.numel(), stream_ptr(x.device))
-    if rc == -4:  # DPK_EUNSUPPORTED
+    if rc == DPK_EUNSUPPORTED:
         return None
-    check(rc, 'dpk_spatial_prodroot_forward')
+    check(rc, lib.dpk_spatial_prodroot_forward)
     return out
 
 
@@ -451,20 +402,14 @@ def spatial_sumprodroot(x, prod5, sum_weight, prod6, root_weight, ws: Workspace)
     g6 = (ctypes.c_int32 * 10)(OH6, OW6, kh6, kw6, sh6, sw6, dh6, dw6, pt6, pl6)
     B = x.shape[0]
     n = lib.dpk_spatial_sumprodroot_workspace_bytes_batch(B, C, H, W, g5, Cout, g6, K)
-    if n == -4:  # DPK_EUNSUPPORTED: outside the fused kernel's envelope
+    if n == DPK_EUNSUPPORTED:  # outside the fused kernel's envelope
         return None
-    if n < 0:
-        check(int(n), 'dpk_spatial_sumprodroot_workspace_bytes_batch')
+    check(n, lib.dpk_spatial_sumprodroot_workspace_bytes_batch)
     buf = ws.get(n, x.device)
     out = torch.empty((B, K), dtype=torch.float32, device=x.device)
-    flags = _tables_flag(ws, 'sumprodroot', w5, wr) | (DPK_FLAG_IN_PIXEL_MAJOR if in_pm else 0)
+    flags = ws.tables_flag(_tables_key('sumprodroot', w5, wr)) | (DPK_FLAG_IN_PIXEL_MAJOR if in_pm else 0)
     rc = lib.dpk_spatial_sumprodroot_forward(ptr(x), B, C, H, W, g5, ptr(w5), Cout, g6, ptr(wr), K, ptr(out), ptr(buf),
                                              buf.numel(), flags, stream_ptr(x.device))
-    if rc == -4 and in_pm:
+    if rc == DPK_EUNSUPPORTED and in_pm:
         return spatial_sumprodroot(x.contiguous(), prod5, sum_weight, prod6, root_weight, ws)
-    if rc:
-        ws.params_key = None
-    if rc == -4:  # DPK_EUNSUPPORTED
-        return None
-    check(rc, 'dpk_spatial_sumprodroot_forward')
-    return out
+    return ws.outcome(rc, lib.dpk_spatial_sumprodroot_forward, out)

@@ -16,14 +16,9 @@ from typing import Iterable
 
 import torch
 
-from deeprob.hip import load_library, check, HipError
+from deeprob.hip import load_library, call, HipError, AdamTensor as _AdamTensor
 
 MAX_TENSORS = 96
-
-
-class _AdamTensor(ctypes.Structure):       # dpk_adam_tensor
-    _fields_ = [('param', ctypes.c_void_p), ('grad', ctypes.c_void_p), ('exp_avg', ctypes.c_void_p),
-                ('exp_avg_sq', ctypes.c_void_p), ('numel', ctypes.c_int64)]
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -126,10 +121,9 @@ class FusedAdam(torch.optim.Optimizer):
             entries = updated
             b1, b2 = group['betas']
             dev = group['params'][0].device
-            check(lib.dpk_adam_step(len(entries), ctypes.cast(arr, ctypes.c_void_p), float(group['lr']), float(b1), float(b2),
+            call(lib.dpk_adam_step, len(entries), ctypes.cast(arr, ctypes.c_void_p), float(group['lr']), float(b1), float(b2),
                                     float(group['eps']), float(group['weight_decay']), int(bool(group['maximize'])),
-                                    step_t.data_ptr(), ticket.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                  'dpk_adam_step')
+                                    step_t.data_ptr(), ticket.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
             # (the kernel wrote through raw pointers: tell autograd -- and the table caches keyed on version counters)
             torch.autograd.graph.increment_version(touched + [step_t])
             del keep

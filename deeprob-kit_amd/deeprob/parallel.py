@@ -154,11 +154,11 @@ class ShardedLogLikelihood:
         if acc is None:
             acc = self._acc_slot(x.device)
         if kernel_events is not None:
-            from deeprob.hip import load_library, check
+            from deeprob.hip import load_library, call
             # (start, stop): raw hipEvent_t handles or torch.cuda.Event objects; either may be None (a run of
             # launches bracketed by the start of its first and the stop of its last)
             h0, h1 = (None if e is None else (e if isinstance(e, int) else e.cuda_event) for e in kernel_events)
-            check(load_library().dpk_profile_next_kernel(h0, h1), 'dpk_profile_next_kernel')
+            call(load_library().dpk_profile_next_kernel, h0, h1)
         from deeprob.hip import ops
         fused = getattr(self.model, '_forward_fused', None)
         ll = None

@@ -5,7 +5,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr, require_device_f32
+from deeprob.hip import load_library, call, ptr, stream_ptr, require_device_f32
 from deeprob.spn.structure.io import FlatSpn
 
 
@@ -33,6 +33,5 @@ def eval_backward(root: FlatSpn, lls: Union[np.ndarray, torch.Tensor]) -> Union[
     B, dev = ld.shape[1], ld.device
     grads = torch.empty_like(ld)
     rec = root.circuit(dev)
-    check(lib.dpk_flat_spn_backward(ptr(ld), ptr(grads), B, ctypes.addressof(rec), stream_ptr(dev)),
-          'dpk_flat_spn_backward')
+    call(lib.dpk_flat_spn_backward, ptr(ld), ptr(grads), B, ctypes.addressof(rec), stream_ptr(dev))
     return grads.cpu().numpy() if as_numpy else grads

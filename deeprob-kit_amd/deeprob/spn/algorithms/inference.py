@@ -10,7 +10,7 @@ from typing import Tuple, Union
 import numpy as np
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr, require_device_f32, HipError
+from deeprob.hip import load_library, call, ptr, stream_ptr, require_device_f32, HipError
 from deeprob.spn.structure.io import FlatSpn
 
 
@@ -45,17 +45,15 @@ def log_likelihood(root: FlatSpn, x: Union[np.ndarray, torch.Tensor], return_res
     table = torch.empty((root.n_nodes, B), dtype=torch.float32, device=dev) if return_results else None
     ws = None
     if table is None:
-        n = lib.dpk_flat_spn_workspace_bytes(B, root.n_nodes, root.n_slots)
-        if n < 0:
-            check(int(n), 'dpk_flat_spn_workspace_bytes')
+        n = call(lib.dpk_flat_spn_workspace_bytes, B, root.n_nodes, root.n_slots)
         if n > 0:
             ws = torch.empty(int(n), dtype=torch.uint8, device=dev)
-    check(lib.dpk_flat_spn_forward(ptr(xd), B, D, root.n_nodes, root.root, ptr(a['order']), ptr(a['kind']),
+    call(lib.dpk_flat_spn_forward, ptr(xd), B, D, root.n_nodes, root.root, ptr(a['order']), ptr(a['kind']),
                                    ptr(a['arg0']), ptr(a['arg1']), ptr(a['arg2']), ptr(a['par0']), ptr(a['par1']),
                                    ptr(a['child_index']), ptr(a['child_weight']), ptr(a['cat_value']),
                                    ptr(a['cat_logp']), root.n_slots, ptr(a['node_slot']), ptr(a['child_slot']),
                                    ptr(out), ptr(table), ptr(ws),
-                                   0 if ws is None else ws.numel(), stream_ptr(dev)), 'dpk_flat_spn_forward')
+                                   0 if ws is None else ws.numel(), stream_ptr(dev))
     if as_numpy:
         out = out.cpu().numpy()
         table = None if table is None else table.cpu().numpy()
@@ -90,12 +88,10 @@ def top_down(root: FlatSpn, x: Union[np.ndarray, torch.Tensor], inplace: bool, m
     B, D = xd.shape
     dev = xd.device
     rec = root.circuit(dev)
-    n = lib.dpk_flat_spn_topdown_workspace_bytes(B, ctypes.addressof(rec))
-    if n < 0:
-        check(int(n), 'dpk_flat_spn_topdown_workspace_bytes')
+    n = call(lib.dpk_flat_spn_topdown_workspace_bytes, B, ctypes.addressof(rec))
     ws = torch.empty(int(n), dtype=torch.uint8, device=dev) if n > 0 else None
-    check(lib.dpk_flat_spn_topdown(ptr(xd), B, D, ctypes.addressof(rec), mode, seed, ptr(ws),
-                                   0 if ws is None else ws.numel(), stream_ptr(dev)), 'dpk_flat_spn_topdown')
+    call(lib.dpk_flat_spn_topdown, ptr(xd), B, D, ctypes.addressof(rec), mode, seed, ptr(ws),
+                                   0 if ws is None else ws.numel(), stream_ptr(dev))
     if not as_numpy:
         return xd
     out = xd.cpu().numpy()

@@ -6,7 +6,7 @@ from typing import Optional, Union
 import numpy as np
 import torch
 
-from deeprob.hip import load_library, check, ptr, stream_ptr
+from deeprob.hip import load_library, call, ptr, stream_ptr
 from deeprob.spn.structure.io import FlatSpn, KIND
 from deeprob.utils.random import RandomState, check_random_state
 
@@ -83,9 +83,7 @@ def expectation_maximization(
     index = torch.from_numpy(draw_batches(random_state, n_samples, batch_size, num_iter)).to(dev)
     root.refresh()                                   # the device copies hold what the host holds
     rec = root.circuit(dev)
-    n = lib.dpk_flat_spn_em_step_workspace_bytes(batch_size, ctypes.addressof(rec))
-    if n < 0:
-        check(int(n), 'dpk_flat_spn_em_step_workspace_bytes')
+    n = call(lib.dpk_flat_spn_em_step_workspace_bytes, batch_size, ctypes.addressof(rec))
     ws = torch.empty(max(int(n), 1), dtype=torch.uint8, device=dev)
     mean_ll = torch.zeros(num_iter, dtype=torch.float64, device=dev)
     bar = None
@@ -98,9 +96,9 @@ def expectation_maximization(
             bar = None
     stream = stream_ptr(dev)
     for it in range(num_iter):
-        check(lib.dpk_flat_spn_em_step(ptr(xd), n_samples, D, index.data_ptr() + 4 * it * batch_size, batch_size,
+        call(lib.dpk_flat_spn_em_step, ptr(xd), n_samples, D, index.data_ptr() + 4 * it * batch_size, batch_size,
                                        ctypes.addressof(rec), float(step_size), mean_ll.data_ptr() + 8 * it, ptr(ws),
-                                       ws.numel(), stream), 'dpk_flat_spn_em_step')
+                                       ws.numel(), stream)
         if verbose:
             text = 'Batch Avg. LL: {:.4f}'.format(float(mean_ll[it]))
             if bar is not None:

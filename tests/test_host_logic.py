@@ -126,7 +126,8 @@ def test_top_down_passes_on_cpu():
 
 def test_c_abi_exports_every_declared_symbol():
     """Every function declared in include/deeprob_hip.h is exported by the built library, and the ctypes
-    table binds exactly that set (no compute call: there is no GPU here)."""
+    table binds exactly that set (no compute call: there is no GPU here).  The table is generated from the same header:
+    tests/test_hip_binding.py anchors it to prototypes written out by hand and to the library's own symbol table."""
     from deeprob import hip
     header = open(os.path.join(ROOT, 'include', 'deeprob_hip.h')).read()
     header = re.sub(r'/\*.*?\*/', '', header, flags=re.S)
