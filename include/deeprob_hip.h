@@ -25,6 +25,32 @@
  *     arms a thread-local, one-shot pair of events;
  *   - scratch memory is handed in by the caller (`ws`, `ws_bytes`); the
  *     matching *_workspace_bytes() query gives the required size;
+ *   - the buffer contract of every entry point that launches work (tested on
+ *     poisoned, guard-banded memory: tests/test_buffer_contract_gpu.py):
+ *     1. where it writes: only its output arguments, over their documented
+ *        extent, and the first *_workspace_bytes(...) bytes of `ws`; a caller
+ *        that passed a larger `ws_bytes` allows writes within `ws_bytes`;
+ *     2. how much it writes: every element of every output, for every legal
+ *        shape, ragged tails and B = 1 included;
+ *     3. what it reads: nothing it does depends on what `ws` or the outputs
+ *        held on entry, except
+ *        (a) what a flag vouches for: the tables in `ws` under
+ *            DPK_FLAG_STRUCT_CACHED / DPK_FLAG_PARAMS_CACHED /
+ *            DPK_FLAG_PARAMS_VERIFY (and the control words next to them, which
+ *            a call with flags = 0 initialises), the forward's activations
+ *            under `ws_holds_forward`;
+ *        (b) arguments documented as accumulated into or updated in place:
+ *            `ldj` / `ildj` with accumulate_ldj / accumulate_ildj, `ldj_const`
+ *            with `accumulate`, `ll_sum` (dpk_ratspn_forward), `acc`
+ *            (dpk_ll_accumulate), the fp64 `sums` / `dab` / `dscale` and the
+ *            `dw` that "the caller zeroed" (RealNVP-2D training), `dx` of
+ *            dpk_channel_stats_backward with accumulate = 1, running_mean /
+ *            running_var of the training batch norms, param / exp_avg /
+ *            exp_avg_sq / step / ticket of dpk_adam_step, the circuit
+ *            parameters under dpk_flat_spn_em_step, and x of
+ *            dpk_flat_spn_topdown (completed in place);
+ *     4. what it leaves alone: its `const` inputs and, in evaluation, the
+ *        model's parameters and buffers;
  *   - the return value is 0 on success and a negative DPK_E* code otherwise;
  *     dpk_last_error() returns a thread-local message for the last failure.
  *     No C++ exception crosses the boundary.
