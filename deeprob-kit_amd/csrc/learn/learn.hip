@@ -1,0 +1,458 @@
+// libdeeprob_learn.so: the statistics of LearnSPN for discrete data, segmented over the tasks of one generation
+// (include/deeprob_learn.h).  Built with -ffp-contract=off: the float64 expressions below are evaluated operation by
+// operation, in the order the header states, so that a host restatement in the same order reproduces them.
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../../include/deeprob_learn.h"
+
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "libdeeprob_learn is written for gfx950 (MI355X)"
+#endif
+
+namespace {
+
+thread_local char g_error[512] = "";
+
+void set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+
+#define DPL_REQUIRE(cond, ...)        \
+    do {                              \
+        if (!(cond)) {                \
+            set_error(__VA_ARGS__);   \
+            return DPL_EINVAL;        \
+        }                             \
+    } while (0)
+
+#define DPL_LAUNCH(what, ...)                                          \
+    do {                                                               \
+        (void)hipGetLastError();                                       \
+        hipLaunchKernelGGL(__VA_ARGS__);                               \
+        hipError_t e__ = hipGetLastError();                            \
+        if (e__ != hipSuccess) {                                       \
+            set_error("%s: %s", (what), hipGetErrorString(e__));       \
+            return DPL_ELAUNCH;                                        \
+        }                                                              \
+    } while (0)
+
+constexpr int kThreads = 256;
+constexpr int kMaxGrid = 2147483647;
+constexpr double kEps32 = 1.1920928955078125e-07;   // np.finfo(np.float32).eps (gvs.py:193)
+
+// ---- column counts ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void column_counts_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ item_col, const int64_t *__restrict__ item_row_off, const int32_t *__restrict__ item_n,
+    int kmax, int32_t *__restrict__ counts) {
+    __shared__ int cnt[DPL_MAX_K];
+    const int64_t item = blockIdx.x;
+    if (threadIdx.x < DPL_MAX_K) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const uint8_t *col = x + (int64_t)item_col[item] * n_rows;
+    const int32_t *rows = row_index + item_row_off[item];
+    const int n = item_n[item];
+    if (kmax <= 2) {
+        // binary data: count the ones in registers, one LDS add per thread
+        int ones = 0, seen = 0;
+        for (int r = threadIdx.x; r < n; r += kThreads) {
+            const int v = col[rows[r]];
+            ones += (v == 1);
+            seen += (v <= 1);
+        }
+        if (seen) {
+            atomicAdd(&cnt[0], seen - ones);
+            if (ones) atomicAdd(&cnt[1], ones);
+        }
+    } else {
+        for (int r = threadIdx.x; r < n; r += kThreads) {
+            const int v = col[rows[r]];
+            if (v < kmax) atomicAdd(&cnt[v], 1);
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < kmax) counts[item * kmax + threadIdx.x] = cnt[threadIdx.x];
+}
+
+// ---- G statistics ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void pair_g_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ pair_col_i, const int32_t *__restrict__ pair_col_j, const int64_t *__restrict__ pair_row_off,
+    const int32_t *__restrict__ pair_n, const int32_t *__restrict__ pair_ki, const int32_t *__restrict__ pair_kj,
+    double *__restrict__ g) {
+    __shared__ int joint[DPL_MAX_K * DPL_MAX_K];
+    __shared__ double term[DPL_MAX_K * DPL_MAX_K];
+    __shared__ double m1[DPL_MAX_K], m2[DPL_MAX_K];
+    const int64_t q = blockIdx.x;
+    const int ki = pair_ki[q], kj = pair_kj[q], n = pair_n[q], cells = ki * kj;
+    joint[threadIdx.x] = 0;     // (kThreads == DPL_MAX_K * DPL_MAX_K)
+    __syncthreads();
+    const uint8_t *ci = x + (int64_t)pair_col_i[q] * n_rows, *cj = x + (int64_t)pair_col_j[q] * n_rows;
+    const int32_t *rows = row_index + pair_row_off[q];
+    if (cells <= 4) {
+        // binary pairs: the (up to) four cells in registers, one LDS add per thread and cell
+        int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+        for (int r = threadIdx.x; r < n; r += kThreads) {
+            const int row = rows[r];
+            const int a = ci[row], b = cj[row];
+            const int cell = (a < ki && b < kj) ? a * kj + b : -1;
+            c0 += (cell == 0);
+            c1 += (cell == 1);
+            c2 += (cell == 2);
+            c3 += (cell == 3);
+        }
+        if (c0) atomicAdd(&joint[0], c0);
+        if (c1) atomicAdd(&joint[1], c1);
+        if (c2) atomicAdd(&joint[2], c2);
+        if (c3) atomicAdd(&joint[3], c3);
+    } else {
+        for (int r = threadIdx.x; r < n; r += kThreads) {
+            const int row = rows[r];
+            const int a = ci[row], b = cj[row];
+            if (a < ki && b < kj) atomicAdd(&joint[a * kj + b], 1);
+        }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < ki) {
+        double s = 0.0;
+        for (int b = 0; b < kj; ++b) s = (b == 0) ? ((double)joint[t * kj] + kEps32) : s + ((double)joint[t * kj + b] + kEps32);
+        m1[t] = s;
+    }
+    if (t >= 64 && t < 64 + kj) {      // (the second wave: no divergence with the rows above)
+        const int b = t - 64;
+        double s = 0.0;
+        for (int a = 0; a < ki; ++a) s = (a == 0) ? ((double)joint[b] + kEps32) : s + ((double)joint[a * kj + b] + kEps32);
+        m2[b] = s;
+    }
+    __syncthreads();
+    if (t < cells) {
+        const int a = t / kj, b = t - a * kj;
+        const double h = (double)joint[t] + kEps32;
+        const double e = m1[a] * m2[b] / (double)n;
+        term[t] = h * log(h / e);
+    }
+    __syncthreads();
+    if (t == 0) {
+        double s = term[0];
+        for (int c = 1; c < cells; ++c) s += term[c];
+        g[q] = 2.0 * s;
+    }
+}
+
+// ---- stable partition of row segments -------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void partition_rows_kernel(
+    const int32_t *__restrict__ row_index, const int64_t *__restrict__ child_src_off, const int32_t *__restrict__ child_src_n,
+    const int64_t *__restrict__ child_label_off, const int32_t *__restrict__ child_label,
+    const int64_t *__restrict__ child_dst_off, const int32_t *__restrict__ child_dst_n, const uint8_t *__restrict__ labels,
+    int32_t *__restrict__ out_index) {
+    __shared__ int wave_count[kThreads / 64];
+    const int64_t c = blockIdx.x;
+    const int32_t *src = row_index + child_src_off[c];
+    int32_t *dst = out_index + child_dst_off[c];
+    const int n = child_src_n[c], want = child_label[c], cap = child_dst_n[c];
+    if (want < 0) {
+        for (int r = threadIdx.x; r < n && r < cap; r += kThreads) dst[r] = src[r];
+        return;
+    }
+    const uint8_t *lab = labels + child_label_off[c];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int r0 = 0; r0 < n; r0 += kThreads) {      // (n is block-uniform: every thread takes every trip)
+        const int r = r0 + threadIdx.x;
+        const bool keep = r < n && (int)lab[r] == want;
+        const unsigned long long mask = __ballot(keep);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_count[wave] = __popcll(mask);
+        __syncthreads();
+        int off = base, total = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) {
+            const int cw = wave_count[w];
+            if (w < wave) off += cw;
+            total += cw;
+        }
+        if (keep && off + before < cap) dst[off + before] = src[r];
+        base += total;
+        __syncthreads();
+    }
+}
+
+// ---- k-means ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void kmeans_init_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int64_t *__restrict__ task_row_off,
+    const int64_t *__restrict__ task_cent_off, const int32_t *__restrict__ seeds, int n_rc, int kmax,
+    double *__restrict__ cent) {
+    const int t = blockIdx.x, rc = blockIdx.y;
+    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0;
+    const int row = row_index[task_row_off[t] + seeds[(int64_t)t * n_rc + rc]];
+    double *out = cent + task_cent_off[t] + (int64_t)rc * ncols * kmax;
+    for (int e = threadIdx.x; e < ncols * kmax; e += kThreads) {
+        const int p = e / kmax, k = e - p * kmax;
+        const int v = x[(int64_t)col_index[c0 + p] * n_rows + row];
+        out[e] = (v == k) ? 1.0 : 0.0;
+    }
+}
+
+// squared distance of a row to one centroid: columns in order, values in order, one multiply and one add per feature
+__device__ __forceinline__ double sq_dist(const uint8_t *__restrict__ x, int64_t n_rows, int row,
+                                          const int32_t *__restrict__ cols, const int32_t *__restrict__ ks, int ncols,
+                                          int kmax, const double *__restrict__ cen) {
+    double d = 0.0;
+    for (int p = 0; p < ncols; ++p) {
+        const int v = x[(int64_t)cols[p] * n_rows + row], K = ks[p];
+        const double *f = cen + (int64_t)p * kmax;
+        if (K <= 2) {
+            const double u = (double)v - f[1];      // (kmax >= 2)
+            d += u * u;
+        } else {
+            for (int k = 0; k < K; ++k) {
+                const double u = ((v == k) ? 1.0 : 0.0) - f[k];
+                d += u * u;
+            }
+        }
+    }
+    return d;
+}
+
+__global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int32_t *__restrict__ col_k,
+    const int64_t *__restrict__ task_row_off, const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off,
+    const int64_t *__restrict__ task_lab_off, const int32_t *__restrict__ block_task, const int32_t *__restrict__ block_row0,
+    int n_clusters, int kmax, const double *__restrict__ cent, uint8_t *__restrict__ labels, int64_t n_lab, int first,
+    int32_t *__restrict__ changed) {
+    const int t = block_task[blockIdx.x], rs = blockIdx.y;
+    const int i = block_row0[blockIdx.x] + threadIdx.x;
+    if (i >= task_n[t]) return;
+    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0;
+    const int row = row_index[task_row_off[t] + i];
+    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols * kmax;
+    double best = 0.0;
+    int arg = 0;
+    for (int c = 0; c < n_clusters; ++c) {
+        const double d = sq_dist(x, n_rows, row, col_index + c0, col_k + c0, ncols, kmax, cen + (int64_t)c * ncols * kmax);
+        if (c == 0 || d < best) {
+            best = d;
+            arg = c;
+        }
+    }
+    uint8_t *slot = labels + (int64_t)rs * n_lab + task_lab_off[t] + i;
+    if (first || *slot != (uint8_t)arg) {
+        *slot = (uint8_t)arg;
+        *changed = 1;       // (every writer stores the same value)
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void kmeans_update_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int64_t *__restrict__ task_row_off,
+    const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off, const int64_t *__restrict__ task_lab_off,
+    const int32_t *__restrict__ item_task, const int32_t *__restrict__ item_p, int n_clusters, int kmax,
+    const uint8_t *__restrict__ labels, int64_t n_lab, double *__restrict__ cent) {
+    __shared__ int cnt[DPL_MAX_CLUSTERS * DPL_MAX_K];
+    const int t = item_task[blockIdx.x], p = item_p[blockIdx.x], rs = blockIdx.y;
+    if (threadIdx.x < DPL_MAX_CLUSTERS * DPL_MAX_K) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0, n = task_n[t];
+    const uint8_t *col = x + (int64_t)col_index[c0 + p] * n_rows;
+    const int32_t *rows = row_index + task_row_off[t];
+    const uint8_t *lab = labels + (int64_t)rs * n_lab + task_lab_off[t];
+    for (int r = threadIdx.x; r < n; r += kThreads) {
+        const int v = col[rows[r]], c = lab[r];
+        if (v < kmax && c < n_clusters) atomicAdd(&cnt[c * kmax + v], 1);
+    }
+    __syncthreads();
+    const int e = threadIdx.x;
+    if (e < n_clusters * kmax) {
+        const int c = e / kmax, k = e - c * kmax;
+        int size = 0;
+        for (int v = 0; v < kmax; ++v) size += cnt[c * kmax + v];
+        if (size > 0)
+            cent[task_cent_off[t] + (((int64_t)rs * n_clusters + c) * ncols + p) * kmax + k] = (double)cnt[e] / (double)size;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void kmeans_inertia_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int32_t *__restrict__ col_k,
+    const int64_t *__restrict__ task_row_off, const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off,
+    const int64_t *__restrict__ task_lab_off, int n_restarts, int n_clusters, int kmax, const double *__restrict__ cent,
+    const uint8_t *__restrict__ labels, int64_t n_lab, double *__restrict__ inertia, int32_t *__restrict__ sizes) {
+    __shared__ double part[kThreads];
+    __shared__ int cnt[DPL_MAX_CLUSTERS];
+    const int t = blockIdx.x, rs = blockIdx.y;
+    if (threadIdx.x < DPL_MAX_CLUSTERS) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0, n = task_n[t];
+    const int32_t *rows = row_index + task_row_off[t];
+    const uint8_t *lab = labels + (int64_t)rs * n_lab + task_lab_off[t];
+    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols * kmax;
+    double s = 0.0;
+    int mine[DPL_MAX_CLUSTERS];
+#pragma unroll
+    for (int c = 0; c < DPL_MAX_CLUSTERS; ++c) mine[c] = 0;
+    for (int r = threadIdx.x; r < n; r += kThreads) {
+        int c = lab[r];
+        if (c >= n_clusters) c = 0;
+        s += sq_dist(x, n_rows, rows[r], col_index + c0, col_k + c0, ncols, kmax, cen + (int64_t)c * ncols * kmax);
+#pragma unroll
+        for (int k = 0; k < DPL_MAX_CLUSTERS; ++k) mine[k] += (k == c);
+    }
+    part[threadIdx.x] = s;
+#pragma unroll
+    for (int k = 0; k < DPL_MAX_CLUSTERS; ++k)
+        if (mine[k]) atomicAdd(&cnt[k], mine[k]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = part[0];
+        for (int l = 1; l < kThreads; ++l) total += part[l];
+        inertia[(int64_t)t * n_restarts + rs] = total;
+    }
+    if ((int)threadIdx.x < n_clusters) sizes[((int64_t)t * n_restarts + rs) * n_clusters + threadIdx.x] = cnt[threadIdx.x];
+}
+
+bool common_ok(const void *x, int64_t n_rows, int n_cols, const void *row_index, int64_t n_index, const char *who) {
+    if (x == nullptr || row_index == nullptr) {
+        set_error("%s: null data or row index", who);
+        return false;
+    }
+    if (n_rows < 1 || n_rows > 2147483647ll || n_cols < 1 || n_index < 1) {
+        set_error("%s: n_rows = %lld, n_cols = %d, n_index = %lld out of domain", who, (long long)n_rows, n_cols, (long long)n_index);
+        return false;
+    }
+    return true;
+}
+
+bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
+    if (n_restarts < 1 || n_restarts > 65535 || n_clusters < 1 || n_clusters > DPL_MAX_CLUSTERS || kmax < 2 || kmax > DPL_MAX_K ||
+        n_restarts * n_clusters > 65535) {
+        set_error("%s: n_restarts = %d, n_clusters = %d (<= %d), kmax = %d (2..%d) out of domain", who, n_restarts, n_clusters,
+                  DPL_MAX_CLUSTERS, kmax, DPL_MAX_K);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *dpl_last_error(void) { return g_error; }
+int dpl_abi_version(void) { return 1; }
+
+int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,
+                      int kmax, int32_t *counts, void *stream) {
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_column_counts")) return DPL_EINVAL;
+    DPL_REQUIRE(item_col && item_row_off && item_n && counts, "dpl_column_counts: null argument");
+    DPL_REQUIRE(n_items >= 1 && n_items <= kMaxGrid, "dpl_column_counts: n_items = %lld out of domain", (long long)n_items);
+    DPL_REQUIRE(kmax >= 2 && kmax <= DPL_MAX_K, "dpl_column_counts: kmax = %d outside 2..%d", kmax, DPL_MAX_K);
+    DPL_LAUNCH("dpl_column_counts", column_counts_kernel, dim3((unsigned)n_items), dim3(kThreads), 0, (hipStream_t)stream, x,
+               n_rows, row_index, item_col, item_row_off, item_n, kmax, counts);
+    return DPL_OK;
+}
+
+int dpl_pair_g(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+               const int32_t *pair_col_i, const int32_t *pair_col_j, const int64_t *pair_row_off, const int32_t *pair_n,
+               const int32_t *pair_ki, const int32_t *pair_kj, int64_t n_pairs, double *g, void *stream) {
+    static_assert(kThreads == DPL_MAX_K * DPL_MAX_K, "one thread per joint cell");
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_pair_g")) return DPL_EINVAL;
+    DPL_REQUIRE(pair_col_i && pair_col_j && pair_row_off && pair_n && pair_ki && pair_kj && g, "dpl_pair_g: null argument");
+    DPL_REQUIRE(n_pairs >= 1 && n_pairs <= kMaxGrid, "dpl_pair_g: n_pairs = %lld out of domain", (long long)n_pairs);
+    DPL_LAUNCH("dpl_pair_g", pair_g_kernel, dim3((unsigned)n_pairs), dim3(kThreads), 0, (hipStream_t)stream, x, n_rows,
+               row_index, pair_col_i, pair_col_j, pair_row_off, pair_n, pair_ki, pair_kj, g);
+    return DPL_OK;
+}
+
+int dpl_partition_rows(const int32_t *row_index, int64_t n_index, const int64_t *child_src_off, const int32_t *child_src_n,
+                       const int64_t *child_label_off, const int32_t *child_label, const int64_t *child_dst_off,
+                       const int32_t *child_dst_n, int64_t n_children, const uint8_t *labels, int64_t n_labels,
+                       int32_t *out_index, int64_t n_out, void *stream) {
+    DPL_REQUIRE(row_index && child_src_off && child_src_n && child_label_off && child_label && child_dst_off && child_dst_n &&
+                    out_index, "dpl_partition_rows: null argument");
+    DPL_REQUIRE(n_index >= 1 && n_out >= 1 && n_labels >= 0 && n_children >= 1 && n_children <= kMaxGrid,
+                "dpl_partition_rows: n_index = %lld, n_out = %lld, n_children = %lld out of domain", (long long)n_index,
+                (long long)n_out, (long long)n_children);
+    DPL_LAUNCH("dpl_partition_rows", partition_rows_kernel, dim3((unsigned)n_children), dim3(kThreads), 0, (hipStream_t)stream,
+               row_index, child_src_off, child_src_n, child_label_off, child_label, child_dst_off, child_dst_n, labels,
+               out_index);
+    return DPL_OK;
+}
+
+int dpl_kmeans_init(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                    const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                    const int32_t *task_n, const int64_t *task_cent_off, const int32_t *seeds, int n_tasks,
+                    int n_restarts, int n_clusters, int kmax, double *cent, int64_t n_cent, void *stream) {
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_kmeans_init")) return DPL_EINVAL;
+    if (!kmeans_ok(n_restarts, n_clusters, kmax, "dpl_kmeans_init")) return DPL_EINVAL;
+    DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && seeds && cent,
+                "dpl_kmeans_init: null argument");
+    DPL_REQUIRE(n_tasks >= 1 && n_cent >= 1, "dpl_kmeans_init: n_tasks = %d, n_cent = %lld out of domain", n_tasks,
+                (long long)n_cent);
+    DPL_LAUNCH("dpl_kmeans_init", kmeans_init_kernel, dim3((unsigned)n_tasks, (unsigned)(n_restarts * n_clusters)),
+               dim3(kThreads), 0, (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, task_row_off,
+               task_cent_off, seeds, n_restarts * n_clusters, kmax, cent);
+    return DPL_OK;
+}
+
+int dpl_kmeans_assign(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *task_col_off, const int32_t *col_index, const int32_t *col_k,
+                      const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_cent_off,
+                      const int64_t *task_lab_off, const int32_t *block_task, const int32_t *block_row0, int64_t n_blocks,
+                      int n_restarts, int n_clusters, int kmax, const double *cent, uint8_t *labels, int64_t n_lab,
+                      int first, int32_t *changed, void *stream) {
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_kmeans_assign")) return DPL_EINVAL;
+    if (!kmeans_ok(n_restarts, n_clusters, kmax, "dpl_kmeans_assign")) return DPL_EINVAL;
+    DPL_REQUIRE(task_col_off && col_index && col_k && task_row_off && task_n && task_cent_off && task_lab_off && block_task &&
+                    block_row0 && cent && labels && changed, "dpl_kmeans_assign: null argument");
+    DPL_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxGrid && n_lab >= 1, "dpl_kmeans_assign: n_blocks = %lld, n_lab = %lld out of domain",
+                (long long)n_blocks, (long long)n_lab);
+    DPL_LAUNCH("dpl_kmeans_assign", kmeans_assign_kernel, dim3((unsigned)n_blocks, (unsigned)n_restarts), dim3(kThreads), 0,
+               (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, col_k, task_row_off, task_n, task_cent_off,
+               task_lab_off, block_task, block_row0, n_clusters, kmax, cent, labels, n_lab, first, changed);
+    return DPL_OK;
+}
+
+int dpl_kmeans_update(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                      const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off,
+                      const int32_t *item_task, const int32_t *item_p, int64_t n_items, int n_restarts, int n_clusters,
+                      int kmax, const uint8_t *labels, int64_t n_lab, double *cent, void *stream) {
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_kmeans_update")) return DPL_EINVAL;
+    if (!kmeans_ok(n_restarts, n_clusters, kmax, "dpl_kmeans_update")) return DPL_EINVAL;
+    DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && task_lab_off && item_task && item_p &&
+                    labels && cent, "dpl_kmeans_update: null argument");
+    DPL_REQUIRE(n_items >= 1 && n_items <= kMaxGrid && n_lab >= 1, "dpl_kmeans_update: n_items = %lld, n_lab = %lld out of domain",
+                (long long)n_items, (long long)n_lab);
+    DPL_LAUNCH("dpl_kmeans_update", kmeans_update_kernel, dim3((unsigned)n_items, (unsigned)n_restarts), dim3(kThreads), 0,
+               (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, task_row_off, task_n, task_cent_off,
+               task_lab_off, item_task, item_p, n_clusters, kmax, labels, n_lab, cent);
+    return DPL_OK;
+}
+
+int dpl_kmeans_inertia(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                       const int32_t *task_col_off, const int32_t *col_index, const int32_t *col_k,
+                       const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_cent_off,
+                       const int64_t *task_lab_off, int n_tasks, int n_restarts, int n_clusters, int kmax,
+                       const double *cent, const uint8_t *labels, int64_t n_lab, double *inertia, int32_t *sizes,
+                       void *stream) {
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_kmeans_inertia")) return DPL_EINVAL;
+    if (!kmeans_ok(n_restarts, n_clusters, kmax, "dpl_kmeans_inertia")) return DPL_EINVAL;
+    DPL_REQUIRE(task_col_off && col_index && col_k && task_row_off && task_n && task_cent_off && task_lab_off && cent &&
+                    labels && inertia && sizes, "dpl_kmeans_inertia: null argument");
+    DPL_REQUIRE(n_tasks >= 1 && n_lab >= 1, "dpl_kmeans_inertia: n_tasks = %d, n_lab = %lld out of domain", n_tasks,
+                (long long)n_lab);
+    DPL_LAUNCH("dpl_kmeans_inertia", kmeans_inertia_kernel, dim3((unsigned)n_tasks, (unsigned)n_restarts), dim3(kThreads), 0,
+               (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, col_k, task_row_off, task_n, task_cent_off,
+               task_lab_off, n_restarts, n_clusters, kmax, cent, labels, n_lab, inertia, sizes);
+    return DPL_OK;
+}
+
+}  // extern "C"

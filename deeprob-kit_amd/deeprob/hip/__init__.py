@@ -31,7 +31,7 @@ _SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_
             'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
 
 
-def _ctype(decl: str, named: bool, where: str):
+def _ctype(decl: str, named: bool, where: str, header: str = 'deeprob_hip.h'):
     """ctypes type of ``[const] type [*...] [name]``: every pointer is a ``c_void_p``, a scalar must be a known word."""
     if '*' in decl:
         return ctypes.c_void_p
@@ -39,19 +39,21 @@ def _ctype(decl: str, named: bool, where: str):
     if named and len(words) > 1:
         words = words[:-1]
     if len(words) != 1 or words[0] not in _SCALARS:
-        raise HipError("deeprob_hip.h: cannot read the type of '{}' in {}".format(decl.strip(), where))
+        raise HipError("{}: cannot read the type of '{}' in {}".format(header, decl.strip(), where))
     return _SCALARS[words[0]]
 
 
-def parse_header(text: str):
+def parse_header(text: str, prefix: str = 'dpk', header: str = 'deeprob_hip.h'):
     """``(signatures, constants, structs)`` of a header text: ``{name: (restype, argtypes)}``, ``{DPK_NAME: int}`` and
-    ``{struct name: [(field, ctype)]}``.  Raises HipError on anything it does not understand -- it never guesses."""
+    ``{struct name: [(field, ctype)]}``.  Raises HipError on anything it does not understand -- it never guesses.
+    ``prefix``: what the entry points (lower case) and constants (upper case) of this header begin with; ``header``: its
+    name in error messages."""
     text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
     constants = {}
-    for m in re.finditer(r'^#define\s+(DPK_\w+)[ \t]+(.*)$', text, re.M):
+    for m in re.finditer(r'^#define\s+(' + prefix.upper() + r'_\w+)[ \t]+(.*)$', text, re.M):
         value = re.fullmatch(r'\(?(-?\d+)u?\)?', m.group(2).strip())
         if value is None:
-            raise HipError("deeprob_hip.h: cannot read the value '{}' of {}".format(m.group(2).strip(), m.group(1)))
+            raise HipError("{}: cannot read the value '{}' of {}".format(header, m.group(2).strip(), m.group(1)))
         constants[m.group(1)] = int(value.group(1))
     text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
     structs = {}
@@ -61,7 +63,7 @@ def parse_header(text: str):
             first, *more = line.split(',')
             base = re.sub(r'[\s\*]*\w+\s*$', '', first)          # the type words in front of the first declarator
             for d in [first[len(base):]] + more:
-                fields.append((d.replace('*', '').strip(), _ctype(base + ' ' + d, True, 'struct ' + m.group(2))))
+                fields.append((d.replace('*', '').strip(), _ctype(base + ' ' + d, True, 'struct ' + m.group(2), header)))
         structs[m.group(2)] = fields
     text = re.sub(r'typedef\s+struct\s*\w*\s*\{.*?\}\s*\w+\s*;', '', text, flags=re.S)
     text = re.sub(r'extern\s+"C"\s*\{', '', text)
@@ -69,17 +71,17 @@ def parse_header(text: str):
     for stmt in filter(None, (s.strip() for s in text.split(';'))):
         if stmt == '}':            # (closes extern "C")
             continue
-        m = re.fullmatch(r'(.+?)\b(dpk_\w+)\s*\((.*)\)', stmt, re.S)
+        m = re.fullmatch(r'(.+?)\b(' + prefix + r'_\w+)\s*\((.*)\)', stmt, re.S)
         if m is None:
-            raise HipError("deeprob_hip.h: not a prototype: '{}'".format(stmt))
+            raise HipError("{}: not a prototype: '{}'".format(header, stmt))
         ret, name, params = m.group(1), m.group(2), m.group(3).strip()
         if '*' in ret:
             if re.sub(r'\s+', ' ', ret).strip() != 'const char *':
-                raise HipError("deeprob_hip.h: cannot read the return type '{}' of {}".format(ret.strip(), name))
+                raise HipError("{}: cannot read the return type '{}' of {}".format(header, ret.strip(), name))
             restype = ctypes.c_char_p
         else:
-            restype = _ctype(ret, False, name)
-        argtypes = [] if params == 'void' else [_ctype(p, True, name) for p in params.split(',')]
+            restype = _ctype(ret, False, name, header)
+        argtypes = [] if params == 'void' else [_ctype(p, True, name, header) for p in params.split(',')]
         signatures[name] = (restype, argtypes)
     return signatures, constants, structs
 

@@ -1,1 +1,3 @@
 from .em import expectation_maximization
+from .learnspn import learn_spn
+from .wrappers import learn_estimator, learn_classifier, compute_data_domains

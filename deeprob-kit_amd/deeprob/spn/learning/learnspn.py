@@ -1,0 +1,452 @@
+"""LearnSPN (reference deeprob/spn/learning/learnspn.py:41-222) for discrete data, with the statistics of every task on
+the HIP device and the task queue, every random draw and the graph on the host.  Returns a
+:class:`deeprob.spn.structure.io.FlatSpn`.
+
+The reference pops one task at a time from a FIFO queue.  The queue is breadth first, so the tasks of one GENERATION
+(one depth of the task tree, a retry counting as a child) are consecutive in it and their children follow in the same
+order; a generation is processed here as a whole: column counts of all its tasks in one launch, the operations decided
+from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the G
+statistics of all column-splitting tasks in one launch, the k-means of all row-splitting tasks together, and one
+partition launch that writes the next generation's row-index array.  See DESIGN.md, "LearnSPN on the device".
+"""
+from collections import deque
+from typing import List, Optional, Union
+
+import numpy as np
+
+from deeprob.spn.structure.leaf import LeafType, Bernoulli, Categorical
+
+#: what ``get_learn_leaf_method`` / ``get_split_rows_method`` / ``get_split_cols_method`` of the reference know
+#: (learning/leaf.py:31-37, splitting/rows.py:54-68, splitting/cols.py:58-76) and what is built here
+KNOWN_LEAF, BUILT_LEAF = ('mle', 'isotonic', 'binary-clt'), ('mle',)
+KNOWN_ROWS, BUILT_ROWS = ('kmeans', 'kmeans_mb', 'dbscan', 'wald', 'gmm', 'rdc', 'random'), ('kmeans', 'random')
+KNOWN_COLS = ('gvs', 'rgvs', 'wrgvs', 'ebvs', 'ebvs_ae', 'gbvs', 'gbvs_ag', 'rdc', 'random')
+BUILT_COLS = ('gvs', 'rgvs', 'random')
+KMEANS_RESTARTS = 5
+#: launches + host reads + uploads per generation, outside the Lloyd loop
+LAUNCHES_PER_GENERATION = 14
+
+_last_info = {}
+
+
+def last_info() -> dict:
+    """What the last ``learn_spn`` recorded: ``generations``, ``launches`` (kernel launches, host reads and uploads outside
+    the Lloyd loop), ``lloyd_launches``, ``tasks_per_generation`` and the split of ``launches``."""
+    return dict(_last_info)
+
+
+def _method(name, known, built, unknown_msg, what):
+    if not isinstance(name, str):
+        raise NotImplementedError("a custom {} function is not built on the HIP path (built: {})".format(what, ', '.join(built)))
+    if name not in known:
+        raise ValueError(unknown_msg.format(name))
+    if name not in built:
+        raise NotImplementedError("{} '{}' is not built on the HIP path (built: {})".format(what, name, ', '.join(built)))
+    return name
+
+
+def _kwargs(given, allowed, what):
+    out = dict(allowed)
+    for k, v in (given or {}).items():
+        if k not in allowed:
+            raise TypeError("{} got an unexpected keyword argument '{}'".format(what, k))
+        out[k] = v
+    return out
+
+
+def check_random_state(random_state):
+    """reference utils/random.py: None, a seed or a RandomState."""
+    if random_state is None:
+        return np.random.RandomState()
+    if isinstance(random_state, (int, np.integer)):
+        return np.random.RandomState(int(random_state))
+    if isinstance(random_state, np.random.RandomState):
+        return random_state
+    raise ValueError("The random state must be either None, a seed integer or a Numpy RandomState")
+
+
+def check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs, split_rows_kwargs,
+                    split_cols_kwargs, min_rows_slice, min_cols_slice):
+    """The argument checks of ``learn_spn`` in the reference's order (learnspn.py:80-96), then what this path does not
+    build; returns ``(leaf kwargs, rows kwargs, cols kwargs)`` with the defaults filled in.  Touches no device."""
+    if len(distributions) == 0:
+        raise ValueError("The list of distribution classes must be non-empty")
+    if len(domains) == 0:
+        raise ValueError("The list of domains must be non-empty")
+    if min_rows_slice <= 0:
+        raise ValueError("The minimum number of samples required to split horizontally must be positive")
+    if min_cols_slice <= 0:
+        raise ValueError("The minimum number of samples required to split vertically must be positive")
+    if len(data.shape) != 2:
+        raise ValueError("The data must be a matrix of samples by features")
+    n_samples, n_features = data.shape
+    if len(distributions) != n_features or len(domains) != n_features:
+        raise ValueError("Each data column should correspond to a random variable having a distribution and a domain")
+    _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
+    _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
+    _method(split_cols, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
+    leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
+    rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
+    cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
+    if leaf_kw['alpha'] < 0.0:
+        raise ValueError("The Laplace smoothing factor must be non-negative")
+    from deeprob.hip import learn as L
+    if split_rows == 'kmeans' and not 1 <= int(rows_kw['n']) <= L.DPL_MAX_CLUSTERS:
+        raise ValueError("k-means on the HIP path takes 1..{} clusters".format(L.DPL_MAX_CLUSTERS))
+    for dist in distributions:
+        if getattr(dist, 'LEAF_TYPE', None) != LeafType.DISCRETE or dist not in (Bernoulli, Categorical):
+            raise NotImplementedError("{} leaves are not built by learn_spn on the HIP path (built: Bernoulli, Categorical)"
+                                      .format(getattr(dist, '__name__', dist)))
+    for i, (dist, dom) in enumerate(zip(distributions, domains)):
+        if not isinstance(dom, list) or len(dom) == 0 or [int(v) for v in dom] != list(range(len(dom))) \
+                or any(v != int(v) for v in dom):
+            raise ValueError("The domain of variable {} must be list(range(K)), got {}".format(i, dom))
+        if len(dom) > L.DPL_MAX_K:
+            raise ValueError("The domain of variable {} has {} values, at most {} are built".format(i, len(dom), L.DPL_MAX_K))
+        if dist is Bernoulli and list(dom) != [0, 1]:
+            raise ValueError("The domain of the Bernoulli variable {} must be [0, 1], got {}".format(i, dom))
+    return leaf_kw, rows_kw, cols_kw
+
+
+def _to_device(data, ks):
+    """The data as uint8 domain positions, column major, on the device (one upload); ValueError on NaN or on a value
+    outside its domain; HipError for a CPU tensor."""
+    import torch
+    from deeprob.hip import HipError, learn as L
+    if isinstance(data, torch.Tensor):
+        if not data.is_cuda:
+            raise HipError("data lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no "
+                           "CPU fallback); pass a numpy array or a device tensor".format(data.device))
+        if data.is_floating_point() and bool(torch.isnan(data).any()):
+            raise ValueError("The data contains NaN: learn_spn needs complete data")
+        kt = torch.as_tensor(ks, device=data.device).to(data.dtype)
+        if bool(((data < 0) | (data >= kt) | (data != data.round() if data.is_floating_point() else False)).any()):
+            raise ValueError("The data holds values outside the domains")
+        x = data.t().contiguous().to(torch.uint8)
+    else:
+        data = np.asarray(data)
+        if np.issubdtype(data.dtype, np.floating) and np.isnan(data).any():
+            raise ValueError("The data contains NaN: learn_spn needs complete data")
+        if ((data < 0) | (data >= np.asarray(ks)[None, :]) | (data != np.round(data))).any():
+            raise ValueError("The data holds values outside the domains")
+        if not torch.cuda.is_available():
+            raise HipError("learn_spn needs a HIP device (there is no CPU fallback)")
+        x = torch.from_numpy(np.ascontiguousarray(data.T).astype(np.uint8)).cuda()
+    return L.DeviceData(x.reshape(-1), data.shape[0], data.shape[1])
+
+
+class _Task:
+    __slots__ = ('parent', 'row_off', 'n', 'scope', 'no_cols_split', 'no_rows_split', 'is_first', 'op', 'counts', 'draw',
+                 'child_src')
+
+    def __init__(self, parent, n, scope, no_cols_split=False, no_rows_split=False, is_first=False):
+        self.parent, self.n, self.scope = parent, n, scope
+        self.no_cols_split, self.no_rows_split, self.is_first = no_cols_split, no_rows_split, is_first
+        self.row_off = 0
+
+
+def new_node(cls, scope, **kw):
+    return dict({'class': cls, 'scope': list(scope), 'children': []}, **kw)
+
+
+def mle_leaf(dist, var, counts, n, alpha):
+    """learning/leaf.py:64-68 with structure/leaf.py:162 (Bernoulli) / :261-264 (Categorical) from the column's counts."""
+    if dist is Bernoulli:
+        return new_node('Bernoulli', [var], params={'p': (float(counts[1]) + alpha) / (n + 2 * alpha)})
+    k = len(counts)
+    probs = np.empty(k, np.float32)
+    for i in range(k):
+        probs[i] = (int(counts[i]) + alpha) / (n + k * alpha)
+    return new_node('Categorical', [var], params={'categories': list(range(k)), 'probabilities': [float(q) for q in probs]})
+
+
+def naive_factorization(distributions, scope, counts, n, alpha):
+    node = new_node('Product', scope)
+    for i, s in enumerate(scope):
+        node['children'].append(mle_leaf(distributions[s], s, counts[i], n, alpha))
+    return node
+
+
+def topological_order(root):
+    """Kahn's algorithm as the reference runs it (structure/node.py:212-246): the order ``assign_ids`` numbers in."""
+    outgoing, seen, queue = {id(root): 0}, {id(root)}, deque([root])
+    while queue:                                   # (bfs, node.py:175-189)
+        node = queue.popleft()
+        for c in node['children']:
+            outgoing[id(c)] = outgoing.get(id(c), 0) + 1
+            if id(c) not in seen:
+                seen.add(id(c))
+                queue.append(c)
+    ordering, queue = [], deque([root])
+    while queue:
+        node = queue.popleft()
+        ordering.append(node)
+        for c in node['children']:
+            outgoing[id(c)] -= 1
+            if outgoing[id(c)] == 0:
+                queue.append(c)
+    if sum(outgoing.values()) != 0:
+        raise ValueError("SPN structure is not a directed acyclic graph (DAG)")
+    return ordering
+
+
+def to_flat(root):
+    """``assign_ids`` (node.py:156-172), then the flat circuit."""
+    from deeprob.spn.structure.io import FlatSpn
+    order = topological_order(root)
+    ids = {id(n): i for i, n in enumerate(order)}
+    nodes, children = {}, {}
+    for i, n in enumerate(order):
+        rec = {'class': n['class'], 'scope': list(n['scope'])}
+        if n['class'] == 'Sum':
+            rec['weights'] = [float(w) for w in np.asarray(n['weights'], np.float32)]
+        if 'params' in n:
+            rec['params'] = n['params']
+        nodes[i] = rec
+        children[i] = [ids[id(c)] for c in n['children']]
+    return FlatSpn(nodes, children)
+
+
+def component(adjacent, start):
+    """The connected component of ``start``: what the greedy loop of gvs.py:31-50 collects, whatever order its sets
+    iterate in."""
+    seen, queue = {start}, deque([start])
+    while queue:
+        f = queue.popleft()
+        for o in np.flatnonzero(adjacent[f]):
+            if int(o) not in seen:
+                seen.add(int(o))
+                queue.append(int(o))
+    return seen
+
+
+def learn_spn(
+    data,
+    distributions: list,
+    domains: List[Union[list, tuple]],
+    learn_leaf: str = 'mle',
+    split_rows: str = 'kmeans',
+    split_cols: str = 'rdc',
+    learn_leaf_kwargs: dict = None,
+    split_rows_kwargs: dict = None,
+    split_cols_kwargs: dict = None,
+    min_rows_slice: int = 256,
+    min_cols_slice: int = 2,
+    random_state=None,
+    verbose: bool = True
+):
+    """
+    Learn the structure and parameters of a SPN given some training data and several hyperparameters
+    (reference learnspn.py:41-222), on the HIP device.
+
+    Built: discrete data with ``Bernoulli`` (domain ``[0, 1]``) and ``Categorical`` leaves, every domain
+    ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``; ``split_rows`` in ``'kmeans'``, ``'random'``;
+    ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``.  Every other name the reference knows, custom callables and
+    continuous distributions raise ``NotImplementedError`` before any device work -- so does the default
+    ``split_cols='rdc'``: pass ``split_cols='gvs'``.  ``'kmeans'`` is this project's own k-means, not
+    scikit-learn's: the same kind of split, not the same labels.
+
+    :param data: The training data: a numpy array or a tensor on a HIP device, complete (no NaN).
+    :param distributions: A list of distribution classes of ``deeprob.spn.structure.leaf`` (one for each feature).
+    :param domains: A list of domains (one for each feature), each ``list(range(K))``.
+    :param learn_leaf: The method to use to learn a distribution leaf node: 'mle'.
+    :param split_rows: The rows splitting method: 'kmeans' or 'random'.
+    :param split_cols: The columns splitting method: 'gvs', 'rgvs' or 'random'.
+    :param learn_leaf_kwargs: The parameters of the learn leaf method (``alpha``).
+    :param split_rows_kwargs: The parameters of the rows splitting method (``n`` | ``a``, ``b``).
+    :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b``).
+    :param min_rows_slice: The minimum number of samples required to split horizontally.
+    :param min_cols_slice: The minimum number of features required to split vertically.
+    :param random_state: The random state. It can be either None, a seed integer or a Numpy RandomState.
+    :param verbose: Accepted for compatibility (no progress bar is drawn).
+    :return: A learned valid SPN, as a FlatSpn.
+    :raises ValueError: If a parameter is out of scope, the data holds NaN or a domain is not ``range(K)``.
+    :raises NotImplementedError: For what the reference knows and this path does not build.
+    :raises HipError: If the data is a CPU tensor or the native library is missing.
+    """
+    leaf_kw, rows_kw, cols_kw = check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols,
+                                                learn_leaf_kwargs, split_rows_kwargs, split_cols_kwargs, min_rows_slice,
+                                                min_cols_slice)
+    random_state = check_random_state(random_state)
+    import torch
+    from deeprob.hip import learn as L
+    L.load_library()
+    ks_all = [len(d) for d in domains]
+    dev_data = _to_device(data, ks_all)
+    device = dev_data.device
+    n_total, n_features = dev_data.n_rows, dev_data.n_cols
+    kmax = max(2, max(ks_all))
+    alpha = float(leaf_kw['alpha'])
+    L.reset_counters()
+    row_index = torch.arange(n_total, dtype=torch.int32, device=device)
+
+    tmp_node = new_node('Product', range(n_features))
+    generation = [_Task(tmp_node, n_total, list(range(n_features)), is_first=True)]
+    tasks_per_generation, lloyd_iterations = [], 0
+    while generation:
+        tasks_per_generation.append(len(generation))
+        # ---- column counts of every task, the operation of every task (learnspn.py:130-147) -------------------------
+        item_col, item_off, item_n = [], [], []
+        for t in generation:
+            item_col += t.scope
+            item_off += [t.row_off] * len(t.scope)
+            item_n += [t.n] * len(t.scope)
+        counts = L.read(L.column_counts(dev_data, row_index, item_col, item_off, item_n, kmax))
+        o = 0
+        for t in generation:
+            t.counts = [counts[o + i, :ks_all[s]] for i, s in enumerate(t.scope)]
+            o += len(t.scope)
+            zero_var = np.array([int(c.max()) == t.n for c in t.counts])     # a constant column: np.var == 0
+            t.draw = zero_var
+            if zero_var.all():
+                t.op = 'naive'
+            elif zero_var.any():
+                t.op = 'rem'
+            elif t.no_rows_split or len(t.scope) < min_cols_slice or t.n < min_rows_slice:
+                t.op = 'leaf'
+            elif t.no_cols_split or t.is_first:
+                t.op = 'rows'
+            else:
+                t.op = 'cols'
+        # ---- the draws, in queue order (gvs.py:30, 76, 89; random.py:31-32, 56-57; k-means seeds) ---------------------
+        for t in generation:
+            nf = len(t.scope)
+            if t.op == 'rows' and split_rows == 'random':
+                p = random_state.beta(rows_kw['a'], rows_kw['b'])
+                t.draw = random_state.binomial(1, p, size=t.n)
+            elif t.op == 'rows':
+                c = int(rows_kw['n'])
+                if t.n < c:
+                    raise ValueError("n_samples={} should be >= n_clusters={}".format(t.n, c))
+                t.draw = np.stack([random_state.choice(t.n, c, replace=False) for _ in range(KMEANS_RESTARTS)])
+            elif t.op == 'cols' and split_cols == 'random':
+                p = random_state.beta(cols_kw['a'], cols_kw['b'])
+                t.draw = random_state.binomial(1, p, size=nf)
+            elif t.op == 'cols':
+                k = int(max(np.sqrt(nf), 2))
+                if split_cols == 'gvs' or k == nf:
+                    t.draw = (np.arange(nf), random_state.randint(0, nf), None)
+                else:
+                    perm = random_state.permutation(np.arange(nf))[:k]
+                    start = random_state.randint(0, k)
+                    t.draw = (perm, start, random_state.rand())
+        # ---- G statistics of every gvs / rgvs task --------------------------------------------------------------------
+        gvs_tasks = [t for t in generation if t.op == 'cols' and split_cols != 'random']
+        pc = {k: [] for k in ('ci', 'cj', 'off', 'n', 'ki', 'kj')}
+        for t in gvs_tasks:
+            sub = [t.scope[i] for i in t.draw[0]]
+            for a in range(len(sub)):
+                for b in range(a + 1, len(sub)):
+                    pc['ci'].append(sub[a])
+                    pc['cj'].append(sub[b])
+                    pc['off'].append(t.row_off)
+                    pc['n'].append(t.n)
+                    pc['ki'].append(ks_all[sub[a]])
+                    pc['kj'].append(ks_all[sub[b]])
+        g_all = L.read(L.pair_g(dev_data, row_index, pc['ci'], pc['cj'], pc['off'], pc['n'], pc['ki'], pc['kj'])) \
+            if pc['ci'] else np.zeros(0)
+        # ---- k-means of every row-splitting task ----------------------------------------------------------------------
+        km_tasks = [t for t in generation if t.op == 'rows' and split_rows == 'kmeans']
+        km_labels, km_result = None, {}
+        if km_tasks:
+            batch = L.KMeansBatch(dev_data, row_index,
+                                  [(t.row_off, t.n, t.scope, [ks_all[s] for s in t.scope], t.draw) for t in km_tasks],
+                                  KMEANS_RESTARTS, int(rows_kw['n']), kmax)
+            inertia, sizes, km_labels, iters = batch.run()
+            lloyd_iterations += iters
+            for i, t in enumerate(km_tasks):
+                best = int(np.argmin(inertia[i]))              # the lowest inertia, the first one on a tie
+                km_result[id(t)] = (best * batch.n_lab + batch.lab_off[i], sizes[i, best])
+        # ---- the nodes and the children of every task, in queue order (learnspn.py:149-210) -------------------------
+        children, host_labels, n_host_labels, g_pos = [], [], 0, 0
+
+        def child(task, parent_task, label_off=0, label=-1):
+            task.child_src = (parent_task.row_off, parent_task.n, label_off, label)
+            children.append(task)
+
+        for t in generation:
+            scope, nf = t.scope, len(t.scope)
+            if t.op == 'rem':
+                zero_var = t.draw
+                node = new_node('Product', scope)
+                rem = [i for i in range(nf) if zero_var[i]]
+                node['children'].append(naive_factorization(distributions, [scope[i] for i in rem],
+                                                            [t.counts[i] for i in rem], t.n, alpha))
+                child(_Task(node, t.n, [scope[i] for i in range(nf) if not zero_var[i]], is_first=t.is_first), t)
+                t.parent['children'].append(node)
+            elif t.op == 'leaf':
+                if nf == 1:
+                    t.parent['children'].append(mle_leaf(distributions[scope[0]], scope[0], t.counts[0], t.n, alpha))
+                else:
+                    t.parent['children'].append(naive_factorization(distributions, scope, t.counts, t.n, alpha))
+            elif t.op == 'naive':
+                t.parent['children'].append(naive_factorization(distributions, scope, t.counts, t.n, alpha))
+            elif t.op == 'rows':
+                if split_rows == 'random':
+                    labels = t.draw.astype(np.uint8)
+                    sizes_t = np.bincount(labels, minlength=2)
+                    label_off = n_host_labels
+                    host_labels.append(labels)
+                    n_host_labels += t.n
+                else:
+                    label_off, sizes_t = km_result[id(t)]
+                present = [c for c in range(len(sizes_t)) if sizes_t[c] > 0]
+                if len(present) == 1:
+                    child(_Task(t.parent, t.n, scope, no_cols_split=False, no_rows_split=True), t)
+                    continue
+                node = new_node('Sum', scope, weights=[int(sizes_t[c]) / t.n for c in present])
+                for c in present:
+                    child(_Task(node, int(sizes_t[c]), scope), t, label_off, c)
+                t.parent['children'].append(node)
+            else:
+                if split_cols == 'random':
+                    clusters = np.asarray(t.draw)
+                else:
+                    sub, start, coin = t.draw
+                    k = len(sub)
+                    n_pairs = k * (k - 1) // 2
+                    g = g_all[g_pos:g_pos + n_pairs]
+                    g_pos += n_pairs
+                    adjacent = np.zeros((k, k), bool)
+                    q = 0
+                    for a in range(k):
+                        for b in range(a + 1, k):
+                            dof = (ks_all[scope[sub[a]]] - 1) * (ks_all[scope[sub[b]]] - 1)
+                            dependent = not (g[q] < 2.0 * dof * cols_kw['p'])         # gvs.py:203-205, :42
+                            adjacent[a, b] = adjacent[b, a] = dependent
+                            q += 1
+                    part = np.zeros(k, np.int64)
+                    part[list(component(adjacent, int(start)))] = 1
+                    if coin is None:
+                        clusters = part
+                    else:
+                        clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
+                        clusters[sub] = part
+                present = np.unique(clusters)
+                if len(present) == 1:
+                    child(_Task(t.parent, t.n, scope, no_cols_split=True, no_rows_split=False), t)
+                    continue
+                node = new_node('Product', scope)
+                for c in present:
+                    child(_Task(node, t.n, [scope[i] for i in range(nf) if clusters[i] == c]), t)
+                t.parent['children'].append(node)
+        # ---- the next generation's row index ----------------------------------------------------------------------------
+        if children:
+            off = 0
+            for c in children:
+                c.row_off = off
+                off += c.n
+            if host_labels:
+                km_labels = L.upload(device, labels=np.concatenate(host_labels))['labels']
+            src = np.array([c.child_src for c in children], np.int64)
+            row_index = L.partition_rows(row_index, src[:, 0], src[:, 1], src[:, 2], src[:, 3], [c.row_off for c in children],
+                                         [c.n for c in children], None if km_labels is None else km_labels.reshape(-1), off)
+        generation = children
+
+    c = L.COUNTERS
+    _last_info.clear()
+    _last_info.update(generations=len(tasks_per_generation), launches=c['kernels'] + c['reads'] + c['uploads'],
+                      kernels=c['kernels'], reads=c['reads'], uploads=c['uploads'],
+                      lloyd_launches=c['lloyd_kernels'] + c['lloyd_reads'], lloyd_iterations=lloyd_iterations,
+                      tasks_per_generation=tasks_per_generation, launches_per_generation=LAUNCHES_PER_GENERATION)
+    return to_flat(tmp_node['children'][0])

@@ -1,0 +1,134 @@
+/*
+ * deeprob_learn.h -- C ABI of libdeeprob_learn.so (gfx950 / MI355X): the device side of LearnSPN
+ * (deeprob.spn.learning.learnspn.learn_spn) for discrete data.
+ *
+ * The reference is Python on numpy (deeprob/spn/learning/learnspn.py:121-222); the statistics it
+ * gathers per task -- column histograms (leaf.py:162, 263; learnspn.py:132), the joint histograms
+ * of the G-test (splitting/gvs.py:178-208) and the clustering of rows (splitting/cluster.py:41-65)
+ * -- are what the entry points below compute, for ALL tasks of one generation of the task queue in
+ * one launch each.  The task loop itself, every random draw and the graph stay on the host
+ * (deeprob/spn/learning/learnspn.py of this package).
+ *
+ * Data layout
+ *   - `x` is the training set as uint8 DOMAIN POSITIONS (value v of a variable with domain
+ *     range(K) is stored as v), COLUMN MAJOR: x[col * n_rows + row].  A task reads a few columns
+ *     over a subset of rows, so a column is one contiguous run and an unused column costs nothing;
+ *   - `row_index` is the generation's row-index array: a task owns the segment
+ *     [row_off, row_off + n) of it, its rows in increasing order of the original row number;
+ *   - every pointer is a DEVICE pointer; `stream` is a hipStream_t passed as void*; kernels are
+ *     enqueued asynchronously on it and no entry point synchronises or allocates.
+ *
+ * Buffer contract (the one of include/deeprob_hip.h, repeated):
+ *   1. an entry point writes only its output arguments, over their documented extent;
+ *   2. it writes every element of every output, for every legal shape (n = 1, one column, ragged
+ *      tails included);
+ *   3. nothing it does depends on what the outputs held on entry, except the arguments documented
+ *      as updated in place: `labels` and `changed` of dpl_kmeans_assign, `cent` of
+ *      dpl_kmeans_update;
+ *   4. it leaves its `const` inputs alone.
+ * There is no workspace.  Index arrays handed in are trusted to lie inside the arrays they index,
+ * a value x >= the K stated for its column is not counted.  Counts are exact integers (LDS integer
+ * atomics); no floating-point value is accumulated atomically, every float64 sum has a fixed order.
+ *
+ * The return value is 0 on success and a negative DPL_E* code otherwise; dpl_last_error() returns
+ * a thread-local message for the last failure.
+ */
+#ifndef DEEPROB_LEARN_H
+#define DEEPROB_LEARN_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define DPL_OK 0
+#define DPL_EINVAL (-1)  /* bad argument (null pointer, size out of domain) */
+#define DPL_ELAUNCH (-3) /* hipLaunch / runtime error                        */
+
+#define DPL_MAX_K 16       /* largest domain size of a variable               */
+#define DPL_MAX_CLUSTERS 8 /* largest number of k-means clusters              */
+
+const char *dpl_last_error(void);
+int dpl_abi_version(void);
+
+/* Column counts: for item i (a column of a task) counts[i * kmax + v] = number of rows r in the
+ * item's segment with x[item_col[i]][row_index[item_row_off[i] + r]] == v, v < kmax <= DPL_MAX_K.
+ * They answer the zero-variance test (learnspn.py:132), give the MLE leaves (leaf.py:162, 263) and
+ * the marginals of the G-test.  counts: [n_items * kmax] int32. */
+int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,
+                      int kmax, int32_t *counts, void *stream);
+
+/* G statistics (gvs.py:190-197): for pair q the joint counts c[a][b] of columns pair_col_i[q],
+ * pair_col_j[q] (domain sizes pair_ki[q], pair_kj[q] <= DPL_MAX_K) over the pair's row segment, in
+ * exact integers, then in float64, in this order of operations:
+ *   h[a][b] = c[a][b] + 2^-23;  m1[a] = h[a][0] + h[a][1] + ...;  m2[b] = h[0][b] + h[1][b] + ...;
+ *   e = m1[a] * m2[b] / n;  g = 2 * (t[0][0] + t[0][1] + ... row major),  t = h * log(h / e).
+ * g: [n_pairs] float64. */
+int dpl_pair_g(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+               const int32_t *pair_col_i, const int32_t *pair_col_j, const int64_t *pair_row_off, const int32_t *pair_n,
+               const int32_t *pair_ki, const int32_t *pair_kj, int64_t n_pairs, double *g, void *stream);
+
+/* The next generation's row-index array.  Child c copies, in order, the rows of the source segment
+ * [child_src_off[c], + child_src_n[c]) of `row_index` whose label equals child_label[c] -- the label
+ * of source position s is labels[child_label_off[c] + s] -- or all of them when child_label[c] < 0,
+ * to out_index[child_dst_off[c] ...]; child_dst_n[c] is the number of rows that match (no more are
+ * written).  The destination segments tile [0, n_out).  A stable partition: a slice keeps the row
+ * order that boolean indexing gives (rows.py:40).  `labels` may be null when no child filters. */
+int dpl_partition_rows(const int32_t *row_index, int64_t n_index, const int64_t *child_src_off, const int32_t *child_src_n,
+                       const int64_t *child_label_off, const int32_t *child_label, const int64_t *child_dst_off,
+                       const int32_t *child_dst_n, int64_t n_children, const uint8_t *labels, int64_t n_labels,
+                       int32_t *out_index, int64_t n_out, void *stream);
+
+/* ---- k-means (this project's definition: DESIGN.md, "LearnSPN on the device") ------------------
+ * Task t has columns col_index[task_col_off[t] .. task_col_off[t + 1]) with domain sizes col_k[same
+ * positions], rows row_index[task_row_off[t] .. + task_n[t]), labels at labels[r * n_lab +
+ * task_lab_off[t] + i] for restart r, and centroids at cent[task_cent_off[t] + ((r * n_clusters + c)
+ * * ncols_t + p) * kmax + k]: the frequency of value k of the task's p-th column in cluster c.
+ * A column with K <= 2 is ONE feature (its value, centroid coordinate = frequency of 1), a column
+ * with K > 2 is K one-hot features (cluster.py:58-60, utils/data.py:152-172).  The squared distance
+ * of a row to a centroid is accumulated in float64 over columns in order, values in order. */
+
+/* cent = the one-hot image of the row at position seeds[(t * n_restarts + r) * n_clusters + c] of
+ * task t's segment.  cent: [n_cent] float64, every element written. */
+int dpl_kmeans_init(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                    const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                    const int32_t *task_n, const int64_t *task_cent_off, const int32_t *seeds, int n_tasks,
+                    int n_restarts, int n_clusters, int kmax, double *cent, int64_t n_cent, void *stream);
+
+/* One assignment step of every (task, restart): block b covers rows block_row0[b] .. + 256 of task
+ * block_task[b].  A row joins the nearest centroid, ties to the lower index.  With first != 0 every
+ * label is written and *changed is set to 1; otherwise a label is compared with the one stored and
+ * *changed is set to 1 when any differs (never cleared here: the caller hands in a zeroed word).
+ * labels: [n_restarts * n_lab] uint8. */
+int dpl_kmeans_assign(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *task_col_off, const int32_t *col_index, const int32_t *col_k,
+                      const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_cent_off,
+                      const int64_t *task_lab_off, const int32_t *block_task, const int32_t *block_row0, int64_t n_blocks,
+                      int n_restarts, int n_clusters, int kmax, const double *cent, uint8_t *labels, int64_t n_lab,
+                      int first, int32_t *changed, void *stream);
+
+/* Centroids from labels: item i is column position item_p[i] of task item_task[i]; per restart and
+ * cluster the counts of the column's values over the cluster's rows (exact), centroid = count / size;
+ * a cluster without rows keeps its centroid. */
+int dpl_kmeans_update(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                      const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                      const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off,
+                      const int32_t *item_task, const int32_t *item_p, int64_t n_items, int n_restarts, int n_clusters,
+                      int kmax, const uint8_t *labels, int64_t n_lab, double *cent, void *stream);
+
+/* inertia[t * n_restarts + r] = sum of the squared distances of the rows to their labelled centroid:
+ * 256 partial sums (partial l takes rows l, l + 256, ... in order), added in order of l; and
+ * sizes[(t * n_restarts + r) * n_clusters + c] = rows labelled c. */
+int dpl_kmeans_inertia(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                       const int32_t *task_col_off, const int32_t *col_index, const int32_t *col_k,
+                       const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_cent_off,
+                       const int64_t *task_lab_off, int n_tasks, int n_restarts, int n_clusters, int kmax,
+                       const double *cent, const uint8_t *labels, int64_t n_lab, double *inertia, int32_t *sizes,
+                       void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DEEPROB_LEARN_H */
