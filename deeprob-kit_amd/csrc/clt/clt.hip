@@ -1,0 +1,355 @@
+// libdeeprob_clt.so: binary Chow-Liu trees (include/deeprob_clt.h).  Built with -ffp-contract=off: the float32
+// expressions of the queries are evaluated operation by operation, in the order the header states, so that a host
+// restatement in the same order reproduces them up to the rounding of expf / log1pf.
+//
+// Layout of the work.  Learning: the data become bit planes (one 64 x 64 tile of x per work-group, transposed through
+// LDS, a ballot per column), then work-groups tile the (i, j) pairs 32 x 32, stage 32 words of each plane in LDS and add
+// popcounts in registers; only tiles on or above the diagonal are computed, each writes its mirror image too.  Queries:
+// one thread per row over column-major codes, the row's 2 D floats of state in `work` as [2 D][B], so that the lanes of
+// a wave read and write consecutive addresses and the tree tables are wave-uniform loads.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include "../../../include/deeprob_clt.h"
+
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "libdeeprob_clt is written for gfx950 (MI355X)"
+#endif
+
+namespace {
+
+thread_local char g_error[512] = "";
+
+void set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_error, sizeof(g_error), fmt, ap);
+    va_end(ap);
+}
+
+#define DPC_REQUIRE(cond, ...)        \
+    do {                              \
+        if (!(cond)) {                \
+            set_error(__VA_ARGS__);   \
+            return DPC_EINVAL;        \
+        }                             \
+    } while (0)
+
+#define DPC_LAUNCH(what, ...)                                          \
+    do {                                                               \
+        (void)hipGetLastError();                                       \
+        hipLaunchKernelGGL(__VA_ARGS__);                               \
+        hipError_t e__ = hipGetLastError();                            \
+        if (e__ != hipSuccess) {                                       \
+            set_error("%s: %s", (what), hipGetErrorString(e__));       \
+            return DPC_ELAUNCH;                                        \
+        }                                                              \
+    } while (0)
+
+typedef unsigned long long u64;
+constexpr int kThreads = 256;
+constexpr int kTile = 64;          // rows and columns of x per packing work-group
+constexpr int kPairTile = 32;      // variables per side of a pair tile
+constexpr int kPairWords = 32;     // plane words staged per step
+constexpr int kRowThreads = 64;    // query rows per work-group: one wave, so that few rows still spread over the CUs
+constexpr int64_t kMaxGridX = 2147483647;
+
+// ---- packing ---------------------------------------------------------------------------------------------------------
+// One work-group per 64 rows x 64 columns of x.  Loads are coalesced along a row; the tile is read back by column.
+__global__ __launch_bounds__(kThreads) void pack_bits_kernel(const float *__restrict__ x, int64_t n, int d, int64_t n_words,
+                                                             u64 *__restrict__ planes) {
+    __shared__ float tile[kTile][kTile + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t word = blockIdx.x, r0 = word * kTile;
+    const int c0 = blockIdx.y * kTile;
+    for (int rr = wave; rr < kTile; rr += kThreads / 64) {
+        const int64_t r = r0 + rr;
+        const int c = c0 + lane;
+        tile[rr][lane] = (r < n && c < d) ? x[r * d + c] : 0.f;
+    }
+    __syncthreads();
+    // wave w owns columns 16 w .. 16 w + 15 of the tile; lane c keeps the word of "its" column and stores it
+    u64 mine = 0;
+    for (int cc = 0; cc < 16; ++cc) {
+        const u64 m = __ballot(tile[lane][wave * 16 + cc] == 1.f);
+        if (lane == cc) mine = m;
+    }
+    const int c = c0 + wave * 16 + lane;
+    if (lane < 16 && c < d) planes[(int64_t)c * n_words + word] = mine;
+}
+
+__global__ __launch_bounds__(kThreads) void pack_query_kernel(const float *__restrict__ x, int64_t b, int d,
+                                                              uint8_t *__restrict__ codes) {
+    __shared__ uint8_t tile[kTile][kTile + 4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kTile;
+    const int c0 = blockIdx.y * kTile;
+    for (int rr = wave; rr < kTile; rr += kThreads / 64) {
+        const int64_t r = r0 + rr;
+        const int c = c0 + lane;
+        uint8_t code = 0;
+        if (r < b && c < d) {
+            const float v = x[r * d + c];
+            code = (v != v) ? (uint8_t)DPC_MISSING : (v != 0.f ? 1 : 0);
+        }
+        tile[rr][lane] = code;
+    }
+    __syncthreads();
+    for (int cc = wave; cc < kTile; cc += kThreads / 64) {
+        const int c = c0 + cc;
+        const int64_t r = r0 + lane;
+        if (c < d && r < b) codes[(int64_t)c * b + r] = tile[lane][cc];
+    }
+}
+
+// ---- pair counts -----------------------------------------------------------------------------------------------------
+// Thread (ty, tx) of the 16 x 16 work-group owns the pairs (ty + 16 a, tx + 16 b), a, b in {0, 1}, of its tile.
+__global__ __launch_bounds__(kThreads) void pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
+                                                               int32_t *__restrict__ ones) {
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj < ti) return;            // the mirror image is written by tile (tj, ti)
+    __shared__ u64 pi[kPairTile][kPairWords + 1], pj[kPairTile][kPairWords + 1];
+    const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
+    int acc[2][2] = {{0, 0}, {0, 0}};
+    for (int64_t w0 = 0; w0 < n_words; w0 += kPairWords) {
+        for (int e = t; e < kPairTile * kPairWords; e += kThreads) {
+            const int r = e / kPairWords, w = e % kPairWords;
+            const int i = ti * kPairTile + r, j = tj * kPairTile + r;
+            const bool in = w0 + w < n_words;
+            pi[r][w] = (in && i < d) ? planes[(int64_t)i * n_words + w0 + w] : 0ull;
+            pj[r][w] = (in && j < d) ? planes[(int64_t)j * n_words + w0 + w] : 0ull;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int w = 0; w < kPairWords; ++w) {
+            const u64 a0 = pi[ty][w], a1 = pi[ty + 16][w], b0 = pj[tx][w], b1 = pj[tx + 16][w];
+            acc[0][0] += __popcll(a0 & b0);
+            acc[0][1] += __popcll(a0 & b1);
+            acc[1][0] += __popcll(a1 & b0);
+            acc[1][1] += __popcll(a1 & b1);
+        }
+        __syncthreads();
+    }
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            const int i = ti * kPairTile + ty + 16 * a, j = tj * kPairTile + tx + 16 * b;
+            if (i < d && j < d) {
+                ones[(int64_t)i * d + j] = acc[a][b];
+                ones[(int64_t)j * d + i] = acc[a][b];
+            }
+        }
+}
+
+// ---- queries -----------------------------------------------------------------------------------------------------------
+enum : int { kLogLikelihood = 0, kMpe = 1, kSample = 2 };
+
+struct QueryArgs {
+    const float *x;
+    const uint8_t *codes;
+    int64_t b;
+    int d;
+    const int32_t *bfs, *parent;
+    const float *params;
+    const int32_t *child_off, *child_idx;
+    u64 seed;
+    int64_t row0;
+    float *work, *out;
+};
+
+// the generator of dpk_flat_spn_topdown (csrc/flat_spn_queries.hip)
+__device__ __forceinline__ float uniform01(u64 seed, u64 ctr) {
+    u64 z = seed + ctr * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+__device__ __forceinline__ float lse2(float a, float b) {
+    const float hi = fmaxf(a, b), lo = fminf(a, b);
+    if (hi == -INFINITY) return -INFINITY;
+    return hi + log1pf(expf(lo - hi));
+}
+
+// m_j: the children's contributions, pulled in list order
+__device__ __forceinline__ void pull(const QueryArgs &a, const float *t, int j, float &m0, float &m1) {
+    m0 = 0.f;
+    m1 = 0.f;
+    const int e1 = a.child_off[j + 1];
+    for (int e = a.child_off[j]; e < e1; ++e) {
+        const int64_t c = a.child_idx[e];
+        m0 += t[2 * c * a.b];
+        m1 += t[(2 * c + 1) * a.b];
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+    if (r >= a.b) return;
+    const int64_t B = a.b;
+    const int D = a.d;
+    const uint8_t *q = a.codes + r;     // q[j * B]
+    float *t = a.work + r;              // t[(2 j + l) * B]
+
+    if (MODE == kLogLikelihood) {
+        double s = 0.0;
+        bool missing = false;
+        for (int i = 0; i < D; ++i) {
+            const int pa = a.parent[i];
+            const int ci = q[(int64_t)i * B], cp = pa < 0 ? 0 : q[(int64_t)pa * B];
+            if (ci == DPC_MISSING) missing = true;
+            if (ci != DPC_MISSING && cp != DPC_MISSING) s += (double)a.params[i * 4 + cp * 2 + ci];
+        }
+        if (!missing) {
+            a.out[r] = (float)s;
+            return;
+        }
+    }
+
+    // upward: t_j of every node but the root, children before parents
+    for (int p = D - 1; p >= 1; --p) {
+        const int j = a.bfs[p];
+        const float *pj = a.params + j * 4;
+        const int cj = q[(int64_t)j * B];
+        float m0, m1;
+        pull(a, t, j, m0, m1);
+        float t0, t1;
+        if (cj != DPC_MISSING) {
+            const float m = cj ? m1 : m0;
+            t0 = pj[cj] + m;
+            t1 = pj[2 + cj] + m;
+        } else if (MODE == kMpe) {
+            t0 = fmaxf(pj[0] + m0, pj[1] + m1);
+            t1 = fmaxf(pj[2] + m0, pj[3] + m1);
+        } else {
+            t0 = lse2(pj[0] + m0, pj[1] + m1);
+            t1 = lse2(pj[2] + m0, pj[3] + m1);
+        }
+        t[2 * (int64_t)j * B] = t0;
+        t[(2 * (int64_t)j + 1) * B] = t1;
+    }
+
+    if (MODE == kLogLikelihood) {
+        const int j = a.bfs[0];
+        const float *pj = a.params + j * 4;
+        const int cj = q[(int64_t)j * B];
+        float m0, m1;
+        pull(a, t, j, m0, m1);
+        a.out[r] = cj != DPC_MISSING ? pj[cj] + (cj ? m1 : m0) : lse2(pj[0] + m0, pj[1] + m1);
+        return;
+    }
+
+    // downward: parents before children.  Once j has its value, t_j is dead (only j's parent pulled it, and that came
+    // first): slot 2 j keeps the value for j's children.
+    for (int p = 0; p < D; ++p) {
+        const int j = a.bfs[p];
+        const int pa = a.parent[j];
+        const int cj = q[(int64_t)j * B];
+        const int xp = pa < 0 ? 0 : (int)t[2 * (int64_t)pa * B];
+        float value;
+        int v;
+        if (cj != DPC_MISSING) {
+            v = cj;
+            value = a.x[r * D + j];
+        } else {
+            const float *pj = a.params + j * 4 + xp * 2;
+            float m0, m1;
+            pull(a, t, j, m0, m1);
+            if (MODE == kMpe) {
+                v = (pj[1] + m1) > (pj[0] + m0);
+            } else {
+                const float prob = expf(pj[1] + (pa < 0 ? m1 : (xp ? m1 : m0)));
+                v = uniform01(a.seed, (u64)(a.row0 + r) * (u64)D + (u64)j) < prob;
+            }
+            value = (float)v;
+        }
+        a.out[r * D + j] = value;
+        t[2 * (int64_t)j * B] = (float)v;
+    }
+}
+
+int check_query(const char *what, const void *x, bool needs_x, const QueryArgs &a) {
+    DPC_REQUIRE(a.d >= 1 && a.d <= DPC_MAX_D, "%s: d = %d is outside 1..%d", what, a.d, DPC_MAX_D);
+    DPC_REQUIRE(a.b >= 0 && a.b <= kMaxGridX, "%s: b = %lld is out of domain", what, (long long)a.b);
+    DPC_REQUIRE(a.codes && a.bfs && a.parent && a.params && a.child_off && a.work && a.out && (x || !needs_x),
+                "%s: null pointer", what);
+    DPC_REQUIRE(a.child_idx || a.d == 1, "%s: null pointer (child_idx)", what);
+    return DPC_OK;
+}
+
+template <int MODE>
+int launch_query(const char *what, const QueryArgs &a, void *stream) {
+    if (a.b == 0) return DPC_OK;
+    const unsigned grid = (unsigned)((a.b + kRowThreads - 1) / kRowThreads);
+    DPC_LAUNCH(what, query_kernel<MODE>, dim3(grid), dim3(kRowThreads), 0, (hipStream_t)stream, a);
+    return DPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *dpc_last_error(void) { return g_error; }
+
+int dpc_abi_version(void) { return 1; }
+
+int dpc_pack_bits(const float *x, int64_t n, int d, uint64_t *planes, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pack_bits: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(n >= 1 && n < 2147483648ll, "dpc_pack_bits: n = %lld is outside 1..2^31-1", (long long)n);
+    DPC_REQUIRE(x && planes, "dpc_pack_bits: null pointer");
+    const int64_t n_words = (n + 63) / 64;
+    DPC_LAUNCH("dpc_pack_bits", pack_bits_kernel, dim3((unsigned)n_words, (unsigned)((d + kTile - 1) / kTile)),
+               dim3(kThreads), 0, (hipStream_t)stream, x, n, d, n_words, (u64 *)planes);
+    return DPC_OK;
+}
+
+int dpc_pack_query(const float *x, int64_t b, int d, uint8_t *codes, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pack_query: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(b >= 0 && b <= kMaxGridX, "dpc_pack_query: b = %lld is out of domain", (long long)b);
+    DPC_REQUIRE(x && codes, "dpc_pack_query: null pointer");
+    if (b == 0) return DPC_OK;
+    DPC_LAUNCH("dpc_pack_query", pack_query_kernel, dim3((unsigned)((b + kTile - 1) / kTile), (unsigned)((d + kTile - 1) / kTile)),
+               dim3(kThreads), 0, (hipStream_t)stream, x, b, d, codes);
+    return DPC_OK;
+}
+
+int dpc_pair_counts(const uint64_t *planes, int64_t n_words, int d, int32_t *ones, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pair_counts: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(n_words >= 1 && n_words <= (1ll << 25), "dpc_pair_counts: n_words = %lld is outside 1..2^25 (n < 2^31)",
+                (long long)n_words);
+    DPC_REQUIRE(planes && ones, "dpc_pair_counts: null pointer");
+    const unsigned nt = (unsigned)((d + kPairTile - 1) / kPairTile);
+    DPC_LAUNCH("dpc_pair_counts", pair_counts_kernel, dim3(nt, nt), dim3(kThreads), 0, (hipStream_t)stream,
+               (const u64 *)planes, n_words, d, ones);
+    return DPC_OK;
+}
+
+int dpc_clt_log_likelihood(const uint8_t *codes, int64_t b, int d, const int32_t *bfs, const int32_t *parent,
+                           const float *params, const int32_t *child_off, const int32_t *child_idx, float *work,
+                           float *out, void *stream) {
+    const QueryArgs a = {nullptr, codes, b, d, bfs, parent, params, child_off, child_idx, 0ull, 0, work, out};
+    if (int rc = check_query("dpc_clt_log_likelihood", nullptr, false, a)) return rc;
+    return launch_query<kLogLikelihood>("dpc_clt_log_likelihood", a, stream);
+}
+
+int dpc_clt_mpe(const float *x, const uint8_t *codes, int64_t b, int d, const int32_t *bfs, const int32_t *parent,
+                const float *params, const int32_t *child_off, const int32_t *child_idx, float *work, float *out,
+                void *stream) {
+    const QueryArgs a = {x, codes, b, d, bfs, parent, params, child_off, child_idx, 0ull, 0, work, out};
+    if (int rc = check_query("dpc_clt_mpe", x, true, a)) return rc;
+    return launch_query<kMpe>("dpc_clt_mpe", a, stream);
+}
+
+int dpc_clt_sample(const float *x, const uint8_t *codes, int64_t b, int d, const int32_t *bfs, const int32_t *parent,
+                   const float *params, const int32_t *child_off, const int32_t *child_idx, uint64_t seed, int64_t row0,
+                   float *work, float *out, void *stream) {
+    const QueryArgs a = {x, codes, b, d, bfs, parent, params, child_off, child_idx, (u64)seed, row0, work, out};
+    if (int rc = check_query("dpc_clt_sample", x, true, a)) return rc;
+    DPC_REQUIRE(row0 >= 0, "dpc_clt_sample: row0 = %lld is negative", (long long)row0);
+    return launch_query<kSample>("dpc_clt_sample", a, stream);
+}
+
+}  // extern "C"

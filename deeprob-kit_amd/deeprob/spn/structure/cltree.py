@@ -1,0 +1,241 @@
+"""``BinaryCLT``: the binary Chow-Liu tree of the reference (deeprob/spn/structure/cltree.py) as a stand-alone density
+estimator, learned and queried on the HIP device through ``libdeeprob_clt.so`` (include/deeprob_clt.h).
+
+``fit`` counts on the device (``dpc_pack_bits``, ``dpc_pair_counts``) and finishes on the host: float32 priors, joints
+and mutual information in the reference's expressions from exact integer counts, Prim's maximum spanning tree, the
+conditional tables.  ``log_likelihood``, ``mpe`` and ``sample`` run one thread per row on the device.  Inputs follow
+``deeprob.spn.algorithms.inference.log_likelihood``: a numpy array is evaluated on the current HIP device and numpy comes
+back, a device tensor stays on its device, a CPU tensor or a missing library raises ``HipError``.
+
+Two deliberate differences from the reference, both documented in DESIGN.md ("Chow-Liu trees"):
+``bfs`` is breadth first with children in increasing index (the reference's comes from scipy's sparse storage order);
+it only fixes the order of float32 additions.  ``sample`` draws from a counter-based generator with an explicit ``seed``
+(the reference uses scipy's global generator and cannot be replayed).
+
+The class is not a leaf of node-graph SPNs here (``learn_spn(learn_leaf='binary-clt')`` raises), so the reference's
+``em_init`` / ``em_step`` are not built.
+"""
+from typing import List, Optional, Union
+
+import numpy as np
+
+from deeprob.spn.structure.leaf import Leaf, LeafType
+from deeprob.utils.random import RandomState, check_random_state
+from deeprob.utils.graph import build_tree_structure, compute_bfs_ordering, maximum_spanning_tree
+from deeprob.utils.statistics import compute_mutual_information, estimate_priors_joints
+
+
+def _post_order(root):
+    """The ``TreeNode``s under ``root`` as the reference's explicit stack visits them (cltree.py:365-392): a node after
+    its children, the children of a node from the last to the first."""
+    out, stack = [], [(root, False)]
+    while stack:
+        node, expanded = stack.pop()
+        if expanded or node.is_leaf():
+            out.append(node)
+        else:
+            stack.append((node, True))
+            stack.extend((c, False) for c in node.get_children())
+    return out
+
+
+class BinaryCLT(Leaf):
+    LEAF_TYPE = LeafType.DISCRETE
+
+    def __init__(
+        self,
+        scope: List[int],
+        root: Optional[int] = None,
+        tree: Optional[Union[List[int], np.ndarray]] = None,
+        params: Optional[Union[List[List[List[float]]], np.ndarray]] = None
+    ):
+        """
+        Initialize a Binary Chow-Liu Tree (CLT).
+
+        :param scope: The scope: the ids of the variables.
+        :param root: The root variable (an id of the scope). If None, ``fit`` draws it.
+        :param tree: The predecessors, as positions in the scope, -1 at the root.
+        :param params: The conditional probability tables as a (N, 2, 2) array in log space,
+                       ``params[i, l, k] = log P(X_i=k | Pa(X_i)=l)``.
+        :raises ValueError: If the root variable is not in scope.
+        :raises ValueError: If the tree is not compatible with the number of variables and the root.
+        :raises ValueError: If the CPTs are invalid.
+        """
+        scope = [scope] if isinstance(scope, int) else list(scope)
+        if len(scope) == 0:
+            raise ValueError("The scope must not be empty")
+        if len(set(scope)) != len(scope):
+            raise ValueError("The scope must not contain duplicates")
+        self.scope = scope
+
+        if root is not None and tree is None:
+            if root not in scope:
+                raise ValueError("The root variable must be in scope")
+            root = scope.index(root)
+        bfs = None
+        if tree is not None:
+            if isinstance(tree, list):
+                tree = np.array(tree, dtype=np.int32)
+            if len(tree) != len(scope):
+                raise ValueError("Invalid tree structure's number of variables")
+            if root is None:
+                roots = np.flatnonzero(tree == -1)
+                if len(roots) != 1:
+                    raise ValueError("Invalid tree structure's root node")
+                root = int(roots[0])
+            else:
+                if root not in scope:
+                    raise ValueError("The root variable must be in scope")
+                root = scope.index(root)
+            if tree[root] != -1:
+                raise ValueError("Invalid tree structure's root node")
+            bfs = compute_bfs_ordering(tree)
+        self.root, self.tree, self.bfs = root, tree, bfs
+
+        if isinstance(params, list):
+            params = np.array(params, dtype=np.float32)
+            if params.shape != (len(scope), 2, 2):
+                raise ValueError("Invalid conditional probability table (CPT) shape")
+            if not np.allclose(np.exp(params).sum(axis=2), 1.0):
+                raise ValueError("Invalid conditional probability table (CPT) values")
+        self.params = params
+
+    # ---- learning ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def compute_clt_parameters(bfs: np.ndarray, tree: np.ndarray, priors: np.ndarray, joints: np.ndarray) -> np.ndarray:
+        """The CPTs (not in log space) of a tree from priors and joints (cltree.py:105-115):
+        ``params[i, l, k] = P(X_i=k | Pa(X_i)=l)``; both rows of the root hold its prior."""
+        tree = np.asarray(tree)
+        me = np.arange(len(bfs))
+        pair = joints[me, tree]                              # [i, k, l] = P(X_i=k, X_pa=l); the root's row is overwritten
+        inverse = np.reciprocal(priors[tree])                # [i, l]
+        params = pair.transpose(0, 2, 1) * inverse[:, :, None]
+        params[bfs[0]] = priors[bfs[0]]
+        # float32 rounding leaves the rows a little off 1
+        params /= np.sum(params, axis=2, keepdims=True)
+        return params
+
+    def fit(self, data, domain: List[list], alpha: float = 0.1, random_state: Optional[RandomState] = None, **kwargs):
+        """
+        Fit the structure (unless a tree was given) and the parameters to binary training data.
+
+        :param data: The training data ``[N, len(scope)]``, every value 0 or 1: a numpy array or a device tensor.
+        :param domain: The domains of the variables, ``[0, 1]`` each.
+        :param alpha: The Laplace smoothing factor.
+        :param random_state: None, a seed or a Numpy RandomState: draws the root when none was given.
+        :raises ValueError: If a parameter is out of domain or the data are not binary.
+        """
+        if len(data.shape) != 2 or len(domain) != data.shape[1]:
+            raise ValueError("Each data column should correspond to a random variable having a domain")
+        if not all(d == [0, 1] for d in domain):
+            raise ValueError("The domains must be binary for a Binary CLT distribution")
+        if alpha < 0.0:
+            raise ValueError("The Laplace smoothing factor must be non-negative")
+        if data.shape[1] != len(self.scope):
+            raise ValueError("expected data [N, {}], got {}".format(len(self.scope), tuple(data.shape)))
+        random_state = check_random_state(random_state)
+        if self.root is None:
+            self.root = int(random_state.choice(len(self.scope)))
+
+        priors, joints = estimate_priors_joints(data, alpha=alpha)
+        if self.tree is None:
+            self.bfs, self.tree = maximum_spanning_tree(self.root, compute_mutual_information(priors, joints))
+        with np.errstate(divide='ignore'):      # (alpha = 0 can leave a zero probability)
+            self.params = np.log(self.compute_clt_parameters(self.bfs, self.tree, priors, joints))
+
+    # ---- queries -----------------------------------------------------------------------------------------------------
+    def _on_device(self, device):
+        from deeprob.hip import clt
+        if self.tree is None or self.params is None:
+            raise ValueError("The CLT's structure and parameters must be already initialized")
+        # (uploaded per call, one small copy: `params` is a public array a caller may write into)
+        return clt.DeviceTree(self.bfs, self.tree, self.params, device)
+
+    def _run(self, op, x, *args):
+        """``op(tree, x on the device, *args)`` under the input rules of the module docstring."""
+        import torch
+        from deeprob.hip import HipError, clt
+        clt.load_library()
+        as_numpy = not isinstance(x, torch.Tensor)
+        if as_numpy:
+            if not torch.cuda.is_available():
+                raise HipError("BinaryCLT needs a HIP device (there is no CPU fallback)")
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
+        elif not x.is_cuda:
+            raise HipError("x lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
+                           "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
+                           "device tensor".format(x.device))
+        if x.dim() != 2 or x.shape[1] != len(self.scope):
+            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
+        out = op(self._on_device(x.device), x, *args)
+        return out.cpu().numpy() if as_numpy else out
+
+    def log_likelihood(self, x):
+        """``[B, 1]`` float32 log likelihoods; NaN entries are marginalised."""
+        from deeprob.hip import clt
+        return self._run(clt.log_likelihood, x).reshape(-1, 1)
+
+    def likelihood(self, x):
+        ll = self.log_likelihood(x)
+        return np.exp(ll) if isinstance(ll, np.ndarray) else ll.exp()
+
+    def mpe(self, x):
+        """A copy of ``x`` with every NaN entry filled by the most probable completion given the observed entries."""
+        from deeprob.hip import clt
+        return self._run(clt.mpe, x)
+
+    def sample(self, x, seed: Optional[int] = None):
+        """A copy of ``x`` with every NaN entry drawn given the observed entries.  ``seed``: the seed of the counter-based
+        generator (the same seed gives the same bytes); None draws one from numpy's global generator."""
+        from deeprob.hip import clt
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        return self._run(clt.sample, x, int(seed))
+
+    def moment(self, k: int = 1) -> float:
+        raise NotImplementedError("Computation of moments on Binary CLTs not yet implemented")
+
+    # ---- parameters and structure ------------------------------------------------------------------------------------
+    def params_count(self) -> int:
+        return 1 + len(self.tree) + self.params.size
+
+    def params_dict(self) -> dict:
+        return {'root': None if self.root is None else self.scope[self.root], 'tree': self.tree, 'params': self.params}
+
+    def to_pc(self):
+        """
+        The smooth, deterministic and structured-decomposable circuit equivalent to the tree (cltree.py:352-395), as a
+        :class:`deeprob.spn.structure.io.FlatSpn` with ids in ``assign_ids`` order.
+
+        Variable v becomes two indicator leaves and, under each value l of its parent, a sum node with the weights
+        ``exp(params[v][l])`` over the two (a leaf of the tree) or over two products "indicator x the children's sums for
+        this value".  The circuit's root is the sum for l = 1 of the tree's root.
+        """
+        from deeprob.spn.learning.learnspn import new_node, to_flat
+        weights = {self.scope[i]: np.exp(self.params[i]) for i in range(len(self.tree))}
+        sums = ([], [])                 # per parent value l: the sums of the nodes visited and not yet consumed
+        for node in _post_order(build_tree_structure(self.tree, scope=self.scope)):
+            v, n_kids = node.get_id(), len(node.get_children())
+            branches = [new_node('Bernoulli', [v], params={'p': float(k)}) for k in (0, 1)]
+            if n_kids:
+                for k in (0, 1):
+                    kids = [branches[k]] + sums[k][-n_kids:]
+                    del sums[k][-n_kids:]
+                    branches[k] = dict(new_node('Product', [s for c in kids for s in c['scope']]), children=kids)
+            for l in (0, 1):
+                sums[l].append(dict(new_node('Sum', branches[0]['scope'], weights=weights[v][l]), children=list(branches)))
+        return to_flat(sums[1][0])
+
+    def get_scopes(self):
+        """The scope of every inner node of the tree, as in the circuit of ``to_pc``: each once, children first."""
+        scopes, pending = [], []
+        for node in _post_order(build_tree_structure(self.tree, scope=self.scope)):
+            n_kids = len(node.get_children())
+            if n_kids == 0:
+                pending.append([node.get_id()])
+                continue
+            merged = [v for s in pending[-n_kids:] for v in s] + [node.get_id()]
+            del pending[-n_kids:]
+            pending.append(merged)
+            scopes.append(merged)
+        return scopes
