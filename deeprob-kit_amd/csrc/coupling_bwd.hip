@@ -177,6 +177,13 @@ static void launch_gemm_kernel(const GemmArgs &g, dim3 grid, hipStream_t st) {
     else DPK_LAUNCH((gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, g);
 }
 
+// C = 0 in front of the fallback's atomicAdds
+__global__ void gemm_zero_kernel(const GemmArgs g) {
+    const int64_t total = (int64_t)g.M * g.N;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
+        g.C[(e / g.N) * g.ldc + e % g.N] = 0.f;
+}
+
 // bias / ReLU / gate of a split-K product (the per-column scale was applied to the partial sums; with a bias the
 // scale is 1 in every call site, so the order bias -> relu -> scale of the unsplit epilogue is preserved)
 __global__ void gemm_epilogue_kernel(const GemmArgs g) {
@@ -271,8 +278,12 @@ void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
         g.tickets = nullptr;
         if (!(g.bias && g.nscale)) {   // (the fallback's epilogue order: bias -> relu, the scale already applied)
             if (!g.accumulate) {
-                if (g.ldc == g.N) (void)hipMemsetAsync(g.C, 0, (size_t)g.M * g.N * 4, st);
-                else (void)hipMemset2DAsync(g.C, (size_t)g.ldc * 4, 0, (size_t)g.N * 4, (size_t)g.M, st);
+                // (a kernel, not hipMemsetAsync: this path runs inside stream captures, and a captured memset node in
+                // front of the atomics left every fourth element of C with a stale fill pattern when the graph was
+                // replayed right behind host-to-device copies -- tests/test_gemm_f32_gpu.py, the captured fallback)
+                const int64_t total = (int64_t)g.M * g.N;
+                const int64_t nb = (total + 255) / 256;
+                DPK_LAUNCH(gemm_zero_kernel, dim3((int)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st, g);
             }
             launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT), g.ksplit), st);
             if (g.bias || g.relu || g.gate) {

@@ -31,6 +31,29 @@ def conditioner64(wm, act, x):
     return h
 
 
+TORCH_ACTS = {'relu': torch.relu, 'tanh': torch.tanh}
+
+
+def density64_torch(layer, act, x):
+    """apply_backward of an AutoregressiveLayer restated in float64 torch, so that its autograd gives reference gradients:
+    h <- act(F.linear(h, W o M, b)) per hidden layer, (t, s) = the halves of the last linear layer's output,
+    u = (x - t) exp(-a tanh s), ildj = -sum a tanh s.  Returns (u, ildj, x64, a64, [(W64, b64)]) with the last three
+    requiring grad."""
+    lins = [m for m in layer.network if hasattr(m, 'mask')]
+    params = [(m.weight.detach().double().cpu().requires_grad_(True), m.bias.detach().double().cpu().requires_grad_(True))
+              for m in lins]
+    a = layer.scale_act.weight.detach().double().cpu().requires_grad_(True)
+    x = torch.as_tensor(x).detach().double().cpu().requires_grad_(True)
+    h = x
+    for i, (m, (w, b)) in enumerate(zip(lins, params)):
+        h = torch.nn.functional.linear(h, w * m.mask.detach().double().cpu(), b)
+        if i + 1 < len(lins):
+            h = TORCH_ACTS[act](h)
+    D = x.shape[1]
+    s = a * torch.tanh(h[:, D:])
+    return (x - h[:, :D]) * torch.exp(-s), -s.sum(dim=1), x, a, params
+
+
 def sample_step_loop64(layer, act, u):
     """x_i = u_i exp(a tanh(s_i)) + t_i, one variable per step in the order of inv_ordering, the conditioner evaluated
     on the current x (entries not produced yet are zero)."""

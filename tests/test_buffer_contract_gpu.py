@@ -81,6 +81,7 @@ REPLAY = [
     ('test_flows_gpu', 'test_sample_replays_against_the_oracle', {'#': {0}}),
     ('test_flows_gpu', 'test_column_pair_kernels_shapes_vs_oracle', {'#': {0, 6}}),
     ('test_routines_gpu', 'test_train_flow_with_batch_norm', {}),
+    ('test_flows_gpu', 'test_coupling_backward_multi_tile_vs_oracle', dict(case='A')),
     # ---- MAF ----------------------------------------------------------------------------------------------------
     ('test_maf_gpu', 'test_golden_eval', dict(name={'maf20_depth2', 'maf33_tanh', 'maf2_energy', 'maf192_bn', 'maf12_units200'})),
     ('test_maf_gpu', 'test_fused_density_vs_float64', {}),
@@ -90,6 +91,7 @@ REPLAY = [
     ('test_maf_gpu', 'test_masked_linear_forward_backward', {}),
     ('test_maf_gpu', 'test_fused_density_folded_batch_norm_and_accumulate', {}),
     ('test_maf_gpu', 'test_rsample_gradient_golden', {}),
+    ('test_gemm_f32_gpu', 'test_integer_data_is_exact', dict(shape=(257, 129, 65))),
     # ---- flat (node-graph) SPN ------------------------------------------------------------------------------------
     ('test_flat_spn_gpu', 'test_golden', {}),
     ('test_flat_spn_gpu', 'test_random_circuits_against_oracle', dict(B={1, 63, 65, 1000})),

@@ -552,3 +552,160 @@ def test_accuracy_guard_leaves_ordinary_flows_on_the_split_f16_kernels():
         sd = {k: v.detach().cpu().clone() for k, v in flow.state_dict().items()}
         want = forc.flow_log_prob(sd, x.cpu()).numpy()
         assert rel_err(got, want) <= 1e-4          # (an ill-conditioned flow: the reference's own fp32 noise is ~1e-5 here)
+
+
+# ---- the training route past one GEMM tile: split-K, ragged edges ---------------------------------------------------------
+# name -> (constructor kwargs, B, train mode).  Every matrix product of the coupling backward goes through launch_gemm
+# (csrc/coupling_bwd.hip), which splits K when K >= 128 and the 64 x 64 tiles fill less than 3/4 of the compute units:
+#   A  dW2 = dZ^T H, dH = dZ W2, dW1 = dH^T x split 3 / 4 / 3 with last slices 22 / 8 / 22 wide; H, Z, gx unsplit over
+#      6 - 12 tiles; the batch-norm kernels at D no multiple of 16 and B no multiple of 64
+#   B  the headline flow: all six products split (7, 2, 5, 7, 5, 2 slices, ragged last slices, tile counts no multiple of 8)
+#   C  the MLP route's gated products under split-K, kscale + bias + relu in one epilogue, D just over 4 x 64 (the
+#      element-wise kernel's four-columns-per-lane loop takes its clamped tail)
+MULTI_TILE_CASES = {
+    'A': (dict(in_features=100, n_flows=2, units=96), 150, True),
+    'B': (dict(in_features=784, n_flows=2, units=128), 300, True),
+    'C': (dict(in_features=257, n_flows=2, depth=3, units=65, affine=False, batch_norm=False), 129, True),
+}
+_multi_tile_cache = {}
+
+
+def _multi_tile_flow(case):
+    from deeprob.flows.models import RealNVP1d
+    from tests.util import randomise_flow
+    kw, B, train = MULTI_TILE_CASES[case]
+    torch.manual_seed(50 + ord(case))
+    flow = RealNVP1d(**kw)
+    randomise_flow(flow, 60 + ord(case))
+    return flow.train(train)
+
+
+def _multi_tile_reference(case):
+    """Inputs and the oracle's float64 results of a case (CPU, made once, left unchanged): u, ildj, the running statistics
+    after the step, d/dx and every parameter gradient of (u w_u).sum() + (ildj w_l).sum(); and the distance of the same
+    oracle evaluated in float32 from that, per quantity."""
+    if case in _multi_tile_cache:
+        return _multi_tile_cache[case]
+    kw, B, train = MULTI_TILE_CASES[case]
+    D = kw['in_features']
+    flow = _multi_tile_flow(case)
+    gen = torch.Generator().manual_seed(70 + ord(case))
+    x, wu, wl = torch.randn(B, D, generator=gen), torch.randn(B, D, generator=gen), torch.randn(B, generator=gen)
+    names = [n for n, _ in flow.named_parameters()]
+
+    def evaluate(dtype):
+        sd = {k: (v.detach().to(dtype) if v.is_floating_point() else v.detach().clone()) for k, v in flow.state_dict().items()}
+        for n in names:
+            sd[n] = sd[n].clone().requires_grad_(True)
+        xo = x.to(dtype).clone().requires_grad_(True)      # (a copy: x.to(float32) is x itself)
+        running = {}
+        u, ildj = forc.flow_apply_backward(sd, xo, train=train and kw.get('batch_norm', True), running=running)
+        ((u * wu.to(dtype)).sum() + (ildj * wl.to(dtype)).sum()).backward()
+        out = {'u': u.detach(), 'ildj': ildj.detach(), 'grad.x': xo.grad}
+        out.update({'after.' + k: v.detach().reshape(flow.state_dict()[k].shape) for k, v in running.items()})
+        out.update({'grad.' + n: sd[n].grad for n in names if sd[n].grad is not None})
+        return {k: v.double().numpy() for k, v in out.items()}
+
+    want, want32 = evaluate(torch.float64), evaluate(torch.float32)
+    noise = {k: (grad_err if k.startswith('grad.') else rel_err)(want32[k], want[k]) for k in want}
+    for v in want.values():
+        v.setflags(write=False)
+    _multi_tile_cache[case] = (x, wu, wl, want, noise)
+    return _multi_tile_cache[case]
+
+
+def _held(case, test, name, got, want, noise):
+    """SURVEY 8c bars: 1e-5 relative on forward quantities and running statistics, 1e-4 of the tensor's largest magnitude
+    on gradients; a gradient that is mathematically zero (the reference holds rounding noise only) must be as small.
+    Recorded next to each: the distance of the float32 oracle from its float64 self (every case sits at that level,
+    one to two orders below the bars)."""
+    is_grad = name.startswith('grad.')
+    if is_grad and np.max(np.abs(want)) < 1e-6:
+        err, bar = float(np.max(np.abs(got))), 1e-6
+    else:
+        err, bar = (grad_err if is_grad else rel_err)(got, want), (1e-4 if is_grad else 1e-5)
+    report_measured('{}[{}] {}'.format(test, case, name), err, bar, '(the float32 oracle against its float64 self: %.2e)' % noise[name])
+    return err <= bar, (name, err, bar)
+
+
+@pytest.mark.parametrize('keep', [True, False], ids=['kept-activations', 'recompute'])
+@pytest.mark.parametrize('case', sorted(MULTI_TILE_CASES))
+def test_coupling_backward_multi_tile_vs_oracle(case, keep, monkeypatch):
+    """Autograd through a 2-flow RealNVP1d in float32 at shapes where the backward's matrix products span several tiles
+    and split K, against the oracle's autograd in float64: u, ildj, running statistics, d/dx and every parameter
+    gradient, both incoming gradients live.  keep=False: the depth-1 layers take CouplingFn / dpk_coupling1d_backward."""
+    from deeprob.hip import ops_flows
+    if not keep:
+        monkeypatch.setattr(ops_flows, 'KEEP_ACTIVATIONS_BYTES', 0)
+    x, wu, wl, want, noise = _multi_tile_reference(case)
+    flow = _multi_tile_flow(case).cuda()
+    xg = x.cuda().requires_grad_(True)
+    u, ildj = flow.apply_backward(xg)
+    ((u * wu.cuda()).sum() + (ildj * wl.cuda()).sum()).backward()
+    got = {'u': u.detach(), 'ildj': ildj.detach(), 'grad.x': xg.grad}
+    got.update({'grad.' + n: p.grad for n, p in flow.named_parameters() if p.grad is not None})
+    got.update({'after.' + k: v for k, v in flow.state_dict().items() if 'after.' + k in want})
+    assert set(got) == set(want), set(got) ^ set(want)
+    test = 'test_coupling_backward_multi_tile_vs_oracle[%s]' % ('kept-activations' if keep else 'recompute')
+    verdicts = [_held(case, test, k, got[k].cpu().numpy(), want[k], noise) for k in sorted(want)]
+    assert all(ok for ok, _ in verdicts), [v for ok, v in verdicts if not ok]
+    assert sum(k.startswith('grad.layers') for k in want) >= 8
+
+
+def test_sampling_direction_gradients_multi_tile_vs_oracle():
+    """apply_forward of case A's layer sizes in eval mode (dpk_coupling1d_mlp_backward_inverse past one tile): x, ldj,
+    d/dz and every parameter gradient against the oracle's autograd in float64."""
+    x, wu, wl, _, _ = _multi_tile_reference('A')
+    flow = _multi_tile_flow('A').eval()
+    names = [n for n, _ in flow.named_parameters()]
+
+    def evaluate(dtype):
+        sd = {k: (v.detach().to(dtype) if v.is_floating_point() else v.detach().clone()) for k, v in flow.state_dict().items()}
+        for n in names:
+            sd[n] = sd[n].clone().requires_grad_(True)
+        zo = x.to(dtype).clone().requires_grad_(True)
+        xo, lo = forc.flow_apply_forward(sd, zo)
+        ((xo * wu.to(dtype)).sum() + (lo * wl.to(dtype)).sum()).backward()
+        out = {'x': xo.detach(), 'ldj': lo.detach(), 'grad.z': zo.grad}
+        out.update({'grad.' + n: sd[n].grad for n in names if sd[n].grad is not None})
+        return {k: v.double().numpy() for k, v in out.items()}
+
+    want, want32 = evaluate(torch.float64), evaluate(torch.float32)
+    noise = {k: (grad_err if k.startswith('grad.') else rel_err)(want32[k], want[k]) for k in want}
+    flow.cuda()
+    zg = x.cuda().requires_grad_(True)
+    xg, lg = flow.apply_forward(zg)
+    ((xg * wu.cuda()).sum() + (lg * wl.cuda()).sum()).backward()
+    got = {'x': xg.detach(), 'ldj': lg.detach(), 'grad.z': zg.grad}
+    got.update({'grad.' + n: p.grad for n, p in flow.named_parameters() if p.grad is not None})
+    assert set(got) == set(want), set(got) ^ set(want)
+    verdicts = [_held('A-sampling', 'test_sampling_direction_gradients_multi_tile_vs_oracle', k, got[k].cpu().numpy(), want[k], noise)
+                for k in sorted(want)]
+    assert all(ok for ok, _ in verdicts), [v for ok, v in verdicts if not ok]
+
+
+@pytest.mark.parametrize('keep', [True, False], ids=['kept-activations', 'recompute'])
+def test_coupling_backward_multi_tile_repeats_bit_identically(keep, monkeypatch):
+    """Case A twice on the same inputs: the split-K sums are taken in slice order, so d/dx and the gradients of the
+    conditioners' weights and biases are the same bits.  (The ScaledTanh gradient and the batch norm's log-det go
+    through float atomics and are exempt.)"""
+    from deeprob.hip import ops_flows
+    if not keep:
+        monkeypatch.setattr(ops_flows, 'KEEP_ACTIVATIONS_BYTES', 0)
+    x, wu, wl, _, _ = _multi_tile_reference('A')
+    flow = _multi_tile_flow('A').cuda()
+    state = {k: v.clone() for k, v in flow.state_dict().items()}
+    wud, wld = wu.cuda(), wl.cuda()
+    runs = []
+    for _ in range(2):
+        flow.load_state_dict(state)          # (the running statistics of the first pass do not enter the second)
+        flow.zero_grad(set_to_none=True)
+        xg = x.cuda().requires_grad_(True)
+        u, ildj = flow.apply_backward(xg)
+        ((u * wud).sum() + (ildj * wld).sum()).backward()
+        grads = {'grad.x': xg.grad.clone()}
+        grads.update({n: p.grad.clone() for n, p in flow.named_parameters() if '.network.' in n})
+        runs.append(grads)
+    assert len(runs[0]) == 1 + 2 * 4
+    for k in runs[0]:
+        assert torch.equal(runs[0][k], runs[1][k]), '{} differs at {} elements'.format(k, int((runs[0][k] != runs[1][k]).sum()))

@@ -302,6 +302,45 @@ def test_training_goldens(tag):
             assert rel_err(b.cpu().numpy(), g['after.' + k]) <= 1e-5, k
 
 
+@pytest.mark.parametrize('act', ['tanh', 'relu'])
+@pytest.mark.parametrize('depth,seq', [(1, False), (2, True)], ids=['depth1-random', 'depth2-sequential'])
+def test_chain_backward_multi_tile_vs_float64(depth, seq, act):
+    """The chained route and its backward where the matrix products span several tiles and split K (D = 150, 136 units,
+    B = 200: dW = dOut^T In is 300 x 136 over K = 200, 15 tiles; dIn = dOut Wm accumulates into grad_x under split-K):
+    float32 autograd through ops_maf.autoregressive_backward, and density_chain directly, against the float64 torch
+    restatement (maf_cases.density64_torch) and its autograd.  Bars: 1e-5 relative on u / ildj, 1e-4 of the tensor's
+    largest magnitude on gradients; a masked weight's gradient is exactly zero."""
+    from deeprob.hip import ops_maf
+    from tests.util import report_measured
+    D, units, B = 150, 136, 200
+    layer = _layer(D, units, depth=depth, act=act, seed=6, sequential=seq)
+    gen = torch.Generator().manual_seed(11)
+    x, wu, wl = torch.randn(B, D, generator=gen), torch.randn(B, D, generator=gen), torch.randn(B, generator=gen)
+    u64, ildj64, x64, a64, params64 = mc.density64_torch(layer, act, x)
+    ((u64 * wu.double()).sum() + (ildj64 * wl.double()).sum()).backward()
+    xg = x.to(DEV).requires_grad_(True)
+    u, ildj = ops_maf.autoregressive_backward(xg, layer)
+    ((u * wu.to(DEV)).sum() + (ildj * wl.to(DEV)).sum()).backward()
+    with torch.no_grad():
+        uc, ic = ops_maf.density_chain(xg.detach(), layer)
+    lins = [m for m in layer.network if hasattr(m, 'mask')]
+    checks = [('u', u, u64), ('ildj', ildj, ildj64), ('density_chain u', uc, u64), ('density_chain ildj', ic, ildj64),
+              ('grad.x', xg.grad, x64.grad), ('grad.scale_act.weight', layer.scale_act.weight.grad.reshape(-1), a64.grad.reshape(-1))]
+    for i, (m, (w64, b64)) in enumerate(zip(lins, params64)):
+        checks += [('grad.W%d' % i, m.weight.grad, w64.grad), ('grad.b%d' % i, m.bias.grad, b64.grad)]
+        assert np.all(m.weight.grad.cpu().numpy()[m.mask.cpu().numpy() == 0] == 0), i
+    failed = []
+    for name, got, want in checks:
+        is_grad = name.startswith('grad.')
+        err = (grad_err if is_grad else rel_err)(got.detach().cpu().numpy(), want.detach().numpy())
+        bar = 1e-4 if is_grad else 1e-5
+        report_measured('test_chain_backward_multi_tile_vs_float64[depth %d, %s, %s] %s'
+                        % (depth, 'sequential' if seq else 'random degrees', act, name), err, bar)
+        if err > bar:
+            failed.append((name, err, bar))
+    assert not failed, failed
+
+
 def test_training_step_lowers_loss():
     from deeprob.flows.models import MAF
     torch.manual_seed(0)
