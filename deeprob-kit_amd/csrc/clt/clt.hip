@@ -7,46 +7,11 @@
 // popcounts in registers; only tiles on or above the diagonal are computed, each writes its mirror image too.  Queries:
 // one thread per row over column-major codes, the row's 2 D floats of state in `work` as [2 D][B], so that the lanes of
 // a wave read and write consecutive addresses and the tree tables are wave-uniform loads.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include "../../../include/deeprob_clt.h"
-
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "libdeeprob_clt is written for gfx950 (MI355X)"
-#endif
+#include "clt_common.h"
 
 namespace {
 
-thread_local char g_error[512] = "";
-
-void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-
-#define DPC_REQUIRE(cond, ...)        \
-    do {                              \
-        if (!(cond)) {                \
-            set_error(__VA_ARGS__);   \
-            return DPC_EINVAL;        \
-        }                             \
-    } while (0)
-
-#define DPC_LAUNCH(what, ...)                                          \
-    do {                                                               \
-        (void)hipGetLastError();                                       \
-        hipLaunchKernelGGL(__VA_ARGS__);                               \
-        hipError_t e__ = hipGetLastError();                            \
-        if (e__ != hipSuccess) {                                       \
-            set_error("%s: %s", (what), hipGetErrorString(e__));       \
-            return DPC_ELAUNCH;                                        \
-        }                                                              \
-    } while (0)
+using dpc_detail::lse2;
 
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
@@ -165,12 +130,6 @@ __device__ __forceinline__ float uniform01(u64 seed, u64 ctr) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
     return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
-}
-
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float hi = fmaxf(a, b), lo = fminf(a, b);
-    if (hi == -INFINITY) return -INFINITY;
-    return hi + log1pf(expf(lo - hi));
 }
 
 // m_j: the children's contributions, pulled in list order
@@ -292,7 +251,7 @@ int launch_query(const char *what, const QueryArgs &a, void *stream) {
 
 extern "C" {
 
-const char *dpc_last_error(void) { return g_error; }
+const char *dpc_last_error(void) { return dpc_detail::g_error; }
 
 int dpc_abi_version(void) { return 1; }
 

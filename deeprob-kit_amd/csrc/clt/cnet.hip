@@ -1,0 +1,473 @@
+// libdeeprob_clt.so, the cutset-network part (the dpc_cnet_* entry points of include/deeprob_clt.h).  Built with
+// -ffp-contract=off like clt.hip: every floating-point expression is evaluated operation by operation in the order the
+// header states.
+//
+// Layout of the work.  Learning is level synchronous: a generation is every open node of one depth, each with a segment
+// of a row-index array.  gather_pack_kernel makes bit planes of the generation's rows through the index, every segment on
+// a word boundary; seg_pair_counts_kernel is the 32 x 32 pair tile of clt.hip with the task on grid.z and the task's
+// words only; the scores are one thread per (task, column) for the conditional entropies and one thread per task for the
+// serial sums the header orders; partition_kernel splits a segment by the bits of its cut column, one work-group per task,
+// the position of a row from popcounts (no atomics, no scan through memory).  The query is one thread per row: a complete
+// row walks one path, a row with NaN walks the OR tree depth first with its stack in `work`.
+#include "clt_common.h"
+
+namespace {
+
+using dpc_detail::lse2;
+
+typedef unsigned long long u64;
+constexpr int kThreads = 256;
+constexpr int kTile = 64;
+constexpr int kPairTile = 32;
+constexpr int kPairWords = 32;
+constexpr int kRowThreads = 64;
+constexpr int kScoreThreads = 64;
+constexpr int64_t kMaxGridX = 2147483647;
+constexpr int kMaxGridZ = 65535;
+
+// ---- gather-pack ---------------------------------------------------------------------------------------------------------
+// One work-group per plane word x 64 columns; the word's task is found by bisection of word_off (empty tasks own no word).
+__global__ __launch_bounds__(kThreads) void gather_pack_kernel(const float *__restrict__ x, int64_t n, int d,
+                                                               const int32_t *__restrict__ rows,
+                                                               const int32_t *__restrict__ seg_off,
+                                                               const int32_t *__restrict__ word_off, int n_tasks,
+                                                               int64_t n_words, u64 *__restrict__ planes) {
+    __shared__ float tile[kTile][kTile + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t word = blockIdx.x;
+    int lo = 0, hi = n_tasks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)word_off[mid + 1] <= word) lo = mid + 1; else hi = mid;
+    }
+    const int64_t p0 = (int64_t)seg_off[lo] + (word - word_off[lo]) * kTile, p_end = seg_off[lo + 1];
+    const int c0 = blockIdx.y * kTile;
+    for (int rr = wave; rr < kTile; rr += kThreads / 64) {
+        const int64_t p = p0 + rr;
+        const int c = c0 + lane;
+        float v = 0.f;
+        if (p < p_end && c < d) {
+            const int64_t r = rows[p];
+            if (r >= 0 && r < n) v = x[r * d + c];
+        }
+        tile[rr][lane] = v;
+    }
+    __syncthreads();
+    u64 mine = 0;
+    for (int cc = 0; cc < 16; ++cc) {
+        const u64 m = __ballot(tile[lane][wave * 16 + cc] == 1.f);
+        if (lane == cc) mine = m;
+    }
+    const int c = c0 + wave * 16 + lane;
+    if (lane < 16 && c < d) planes[(int64_t)c * n_words + word] = mine;
+}
+
+// ---- segmented pair counts -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void seg_pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
+                                                                   const int32_t *__restrict__ word_off,
+                                                                   int32_t *__restrict__ ones) {
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj < ti) return;            // the mirror image is written by tile (tj, ti)
+    __shared__ u64 pi[kPairTile][kPairWords + 1], pj[kPairTile][kPairWords + 1];
+    const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
+    const int64_t w_begin = word_off[blockIdx.z], w_end = word_off[blockIdx.z + 1];
+    int acc[2][2] = {{0, 0}, {0, 0}};
+    for (int64_t w0 = w_begin; w0 < w_end; w0 += kPairWords) {
+        for (int e = t; e < kPairTile * kPairWords; e += kThreads) {
+            const int r = e / kPairWords, w = e % kPairWords;
+            const int i = ti * kPairTile + r, j = tj * kPairTile + r;
+            const bool in = w0 + w < w_end;
+            pi[r][w] = (in && i < d) ? planes[(int64_t)i * n_words + w0 + w] : 0ull;
+            pj[r][w] = (in && j < d) ? planes[(int64_t)j * n_words + w0 + w] : 0ull;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int w = 0; w < kPairWords; ++w) {
+            const u64 a0 = pi[ty][w], a1 = pi[ty + 16][w], b0 = pj[tx][w], b1 = pj[tx + 16][w];
+            acc[0][0] += __popcll(a0 & b0);
+            acc[0][1] += __popcll(a0 & b1);
+            acc[1][0] += __popcll(a1 & b0);
+            acc[1][1] += __popcll(a1 & b1);
+        }
+        __syncthreads();
+    }
+    int32_t *out = ones + (int64_t)blockIdx.z * d * d;
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            const int i = ti * kPairTile + ty + 16 * a, j = tj * kPairTile + tx + 16 * b;
+            if (i < d && j < d) {
+                out[(int64_t)i * d + j] = acc[a][b];
+                out[(int64_t)j * d + i] = acc[a][b];
+            }
+        }
+}
+
+// ---- scores --------------------------------------------------------------------------------------------------------------
+// h(c0, c1) = -(c0 ln c0 + c1 ln c1)
+__device__ __forceinline__ double entropy2(double c0, double c1) { return -(c0 * log(c0) + c1 * log(c1)); }
+
+// gains[t][i] <- E_i = (c_i / n) H_i,1 + (1 - c_i / n) H_i,0 for an active i (score_select_kernel turns it into the gain).
+// ones[t] is symmetric: thread i reads ones[j][i], consecutive over the threads.
+__global__ __launch_bounds__(kScoreThreads) void score_entropy_kernel(const int32_t *__restrict__ ones,
+                                                                      const int32_t *__restrict__ seg_off,
+                                                                      const uint8_t *__restrict__ active, int d, double alpha,
+                                                                      double *__restrict__ gains) {
+    const int t = blockIdx.y, i = blockIdx.x * kScoreThreads + threadIdx.x;
+    if (i >= d) return;
+    const int32_t *o = ones + (int64_t)t * d * d;
+    const uint8_t *act = active + (int64_t)t * d;
+    double *g = gains + (int64_t)t * d;
+    if (!act[i]) {
+        g[i] = -INFINITY;
+        return;
+    }
+    const double n = (double)(seg_off[t + 1] - seg_off[t]);
+    const double ci = (double)o[(int64_t)i * d + i];
+    const double den1 = ci + 4.0 * alpha, den0 = (n - ci) + 4.0 * alpha, a2 = 2.0 * alpha;
+    double h1 = 0.0, h0 = 0.0;
+    int others = 0;
+    for (int j = 0; j < d; ++j) {
+        if (j == i || !act[j]) continue;
+        const double cj = (double)o[(int64_t)j * d + j], oij = (double)o[(int64_t)j * d + i];
+        // the four cells of (x_i = a, x_j = b) in exact integers (held exactly by a double)
+        const double c11 = oij, c10 = ci - oij, c01 = cj - oij, c00 = ((n - ci) - cj) + oij;
+        h1 += entropy2((c10 + a2) / den1, (c11 + a2) / den1);
+        h0 += entropy2((c00 + a2) / den0, (c01 + a2) / den0);
+        ++others;
+    }
+    if (others) {
+        h1 = h1 / (double)others;
+        h0 = h0 / (double)others;
+    }
+    const double ratio = n > 0.0 ? ci / n : 0.0;
+    g[i] = ratio * h1 + (1.0 - ratio) * h0;
+}
+
+__global__ __launch_bounds__(kScoreThreads) void score_select_kernel(const int32_t *__restrict__ ones,
+                                                                     const int32_t *__restrict__ seg_off,
+                                                                     const uint8_t *__restrict__ active, int n_tasks, int d,
+                                                                     double alpha, double *__restrict__ gains,
+                                                                     double *__restrict__ stats, int32_t *__restrict__ best) {
+    const int t = blockIdx.x * kScoreThreads + threadIdx.x;
+    if (t >= n_tasks) return;
+    const int32_t *o = ones + (int64_t)t * d * d;
+    const uint8_t *act = active + (int64_t)t * d;
+    double *g = gains + (int64_t)t * d;
+    const double n = (double)(seg_off[t + 1] - seg_off[t]);
+    double s = 0.0;
+    int d_active = 0;
+    for (int i = 0; i < d; ++i) {
+        if (!act[i]) continue;
+        const double p1 = ((double)o[(int64_t)i * d + i] + 2.0 * alpha) / (n + 4.0 * alpha), p0 = 1.0 - p1;
+        s += p0 * log(p0) + p1 * log(p1);
+        ++d_active;
+    }
+    const double mean_entropy = d_active ? -s / (double)d_active : 0.0;
+    int arg = -1;
+    double top = -INFINITY;
+    for (int i = 0; i < d; ++i) {
+        if (!act[i]) continue;
+        const double gain = mean_entropy - g[i];
+        g[i] = gain;
+        if (arg < 0 || gain > top) {
+            arg = i;
+            top = gain;
+        }
+    }
+    stats[2 * t] = mean_entropy;
+    stats[2 * t + 1] = top;
+    best[2 * t] = arg;
+    best[2 * t + 1] = arg < 0 ? 0 : o[(int64_t)arg * d + arg];
+}
+
+// ---- partition -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 shfl64(u64 v, int src) {
+    const unsigned lo = __shfl((unsigned)v, src), hi = __shfl((unsigned)(v >> 32), src);
+    return ((u64)hi << 32) | lo;
+}
+
+// One work-group per task.  Every wave reads all words of the task's cut plane (64 at a time, one per lane) and keeps the
+// count of ones before the current word; wave w places the rows of the words k with k % 4 == w.
+__global__ __launch_bounds__(kThreads) void partition_kernel(const u64 *__restrict__ planes, int64_t n_words,
+                                                             const int32_t *__restrict__ rows,
+                                                             const int32_t *__restrict__ seg_off,
+                                                             const int32_t *__restrict__ word_off,
+                                                             const int32_t *__restrict__ cut,
+                                                             const int32_t *__restrict__ out_off,
+                                                             int32_t *__restrict__ rows_out, int32_t *__restrict__ child_n) {
+    const int t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = cut[t];
+    if (c < 0) {
+        if (threadIdx.x < 2) child_n[2 * t + threadIdx.x] = 0;
+        return;
+    }
+    const int64_t s0 = seg_off[t], n = seg_off[t + 1] - s0;
+    const int64_t nw = word_off[t + 1] - word_off[t];
+    const u64 *plane = planes + (int64_t)c * n_words + word_off[t];
+    int cnt = 0;
+    for (int64_t k = lane; k < nw; k += 64) cnt += __popcll(plane[k]);
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    const int64_t n_left = n - cnt;
+    if (threadIdx.x == 0) {
+        child_n[2 * t] = (int32_t)n_left;
+        child_n[2 * t + 1] = cnt;
+    }
+    const int64_t left0 = out_off[t], right0 = left0 + n_left;
+    int64_t before = 0;             // ones in the words in front of the current one
+    for (int64_t k0 = 0; k0 < nw; k0 += 64) {
+        const u64 mine = k0 + lane < nw ? plane[k0 + lane] : 0ull;
+        const int steps = nw - k0 < 64 ? (int)(nw - k0) : 64;
+        for (int i = 0; i < steps; ++i) {
+            const u64 word = shfl64(mine, i);
+            if (((k0 + i) & (kThreads / 64 - 1)) == wave) {
+                const int64_t p = (k0 + i) * 64 + lane;
+                if (p < n) {
+                    const int64_t ob = before + __popcll(word & ((1ull << lane) - 1ull));
+                    const int64_t dst = ((word >> lane) & 1ull) ? right0 + ob : left0 + (p - ob);
+                    rows_out[dst] = rows[s0 + p];
+                }
+            }
+            before += __popcll(word);
+        }
+    }
+}
+
+// ---- query ---------------------------------------------------------------------------------------------------------------
+struct CnetArgs {
+    const uint8_t *codes;
+    int64_t b;
+    const int32_t *node_col, *node_child;
+    const double *node_logw;
+    const int32_t *leaf_meta, *leaf_ints;
+    const float *leaf_params;
+    int levels;
+    double *val;        // [levels][b]
+    float *t;           // [2 max_leaf_d][b]
+    int32_t *ns;        // [levels][b]
+    float *out;
+};
+
+struct Leaf {
+    int d;
+    const int32_t *col, *bfs, *parent, *child_off, *child_idx;
+    const float *params;
+};
+
+__device__ __forceinline__ Leaf leaf_of(const CnetArgs &a, int l) {
+    const int32_t *m = a.leaf_meta + 3 * (int64_t)l;
+    const int d = m[0];
+    const int32_t *ints = a.leaf_ints + m[1];
+    return {d, ints, ints + d, ints + 2 * d, ints + 3 * d, ints + 4 * d + 1, a.leaf_params + m[2]};
+}
+
+__device__ __forceinline__ double lse64(double x, double y) {
+    const double hi = fmax(x, y), lo = fmin(x, y);
+    if (hi == -INFINITY) return -INFINITY;
+    return hi + log1p(exp(lo - hi));
+}
+
+// s += params[i][x_parent(i)][x_i] over the leaf's positions in order; false (and s unspecified) if an entry is missing
+__device__ __forceinline__ bool leaf_gather(const Leaf &f, const uint8_t *q, int64_t B, double &s) {
+    for (int i = 0; i < f.d; ++i) {
+        const int pa = f.parent[i];
+        const int ci = q[(int64_t)f.col[i] * B], cp = pa < 0 ? 0 : q[(int64_t)f.col[pa] * B];
+        if (ci == DPC_MISSING) return false;
+        s += (double)f.params[i * 4 + cp * 2 + ci];
+    }
+    return true;
+}
+
+__device__ __forceinline__ void pull(const Leaf &f, const float *t, int64_t B, int j, float &m0, float &m1) {
+    m0 = 0.f;
+    m1 = 0.f;
+    const int e1 = f.child_off[j + 1];
+    for (int e = f.child_off[j]; e < e1; ++e) {
+        const int64_t c = f.child_idx[e];
+        m0 += t[2 * c * B];
+        m1 += t[(2 * c + 1) * B];
+    }
+}
+
+// the upward pass of dpc_clt_log_likelihood over the leaf's columns
+__device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+    for (int p = f.d - 1; p >= 1; --p) {
+        const int j = f.bfs[p];
+        const float *pj = f.params + j * 4;
+        const int cj = q[(int64_t)f.col[j] * B];
+        float m0, m1;
+        pull(f, t, B, j, m0, m1);
+        float t0, t1;
+        if (cj != DPC_MISSING) {
+            const float m = cj ? m1 : m0;
+            t0 = pj[cj] + m;
+            t1 = pj[2 + cj] + m;
+        } else {
+            t0 = lse2(pj[0] + m0, pj[1] + m1);
+            t1 = lse2(pj[2] + m0, pj[3] + m1);
+        }
+        t[2 * (int64_t)j * B] = t0;
+        t[(2 * (int64_t)j + 1) * B] = t1;
+    }
+    const int j = f.bfs[0];
+    const float *pj = f.params + j * 4;
+    const int cj = q[(int64_t)f.col[j] * B];
+    float m0, m1;
+    pull(f, t, B, j, m0, m1);
+    return cj != DPC_MISSING ? pj[cj] + (cj ? m1 : m0) : lse2(pj[0] + m0, pj[1] + m1);
+}
+
+__global__ __launch_bounds__(kRowThreads) void cnet_query_kernel(const CnetArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+    if (r >= a.b) return;
+    const int64_t B = a.b;
+    const uint8_t *q = a.codes + r;
+
+    {   // a complete row: one path
+        int k = 0;
+        double s = 0.0;
+        bool complete = true;
+        for (int col = a.node_col[k]; col >= 0; col = a.node_col[k]) {
+            const int c = q[(int64_t)col * B];
+            if (c == DPC_MISSING) {
+                complete = false;
+                break;
+            }
+            s += a.node_logw[2 * k + c];
+            k = a.node_child[2 * k + c];
+        }
+        if (complete && leaf_gather(leaf_of(a, a.node_child[2 * k]), q, B, s)) {
+            a.out[r] = (float)s;
+            return;
+        }
+    }
+
+    // depth first; a stack entry is 4 * node + state: 0 = new, 1 = NaN, left child running, 2 = NaN, right child
+    // running, 3 = observed, its one child running
+    double *val = a.val + r;
+    int32_t *ns = a.ns + r;
+    int depth = 0;
+    double ret = 0.0;
+    ns[0] = 0;
+    while (depth >= 0) {
+        const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
+        const int col = a.node_col[k];
+        if (col < 0) {
+            const Leaf f = leaf_of(a, a.node_child[2 * k]);
+            double s = 0.0;
+            ret = leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward(f, q, B, a.t + r);
+            --depth;
+            continue;
+        }
+        const int c = q[(int64_t)col * B];
+        if (st == 0 || st == 1) {
+            if (depth + 1 >= a.levels) {        // the tables are not a tree of `levels` levels: no write past the stack
+                a.out[r] = NAN;
+                return;
+            }
+            int next;
+            if (st == 1) {
+                val[depth * B] = a.node_logw[2 * k] + ret;
+                ns[depth * B] = 4 * k + 2;
+                next = a.node_child[2 * k + 1];
+            } else if (c != DPC_MISSING) {
+                ns[depth * B] = 4 * k + 3;
+                next = a.node_child[2 * k + c];
+            } else {
+                ns[depth * B] = 4 * k + 1;
+                next = a.node_child[2 * k];
+            }
+            ++depth;
+            ns[depth * B] = 4 * next;
+        } else if (st == 2) {
+            ret = lse64(val[depth * B], a.node_logw[2 * k + 1] + ret);
+            --depth;
+        } else {
+            ret = a.node_logw[2 * k + c] + ret;
+            --depth;
+        }
+    }
+    a.out[r] = (float)ret;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dpc_cnet_gather_pack(const float *x, int64_t n, int d, const int32_t *rows, const int32_t *seg_off,
+                         const int32_t *word_off, int n_tasks, int64_t n_words, uint64_t *planes, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_cnet_gather_pack: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(n >= 1 && n < 2147483648ll, "dpc_cnet_gather_pack: n = %lld is outside 1..2^31-1", (long long)n);
+    DPC_REQUIRE(n_tasks >= 1, "dpc_cnet_gather_pack: n_tasks = %d is not positive", n_tasks);
+    DPC_REQUIRE(n_words >= 0 && n_words <= kMaxGridX, "dpc_cnet_gather_pack: n_words = %lld is out of domain",
+                (long long)n_words);
+    DPC_REQUIRE(x && rows && seg_off && word_off && planes, "dpc_cnet_gather_pack: null pointer");
+    if (n_words == 0) return DPC_OK;
+    DPC_LAUNCH("dpc_cnet_gather_pack", gather_pack_kernel, dim3((unsigned)n_words, (unsigned)((d + kTile - 1) / kTile)),
+               dim3(kThreads), 0, (hipStream_t)stream, x, n, d, rows, seg_off, word_off, n_tasks, n_words, (u64 *)planes);
+    return DPC_OK;
+}
+
+int dpc_cnet_pair_counts(const uint64_t *planes, int64_t n_words, int d, const int32_t *word_off, int n_tasks,
+                         int32_t *ones, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_cnet_pair_counts: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(n_tasks >= 1 && n_tasks <= kMaxGridZ, "dpc_cnet_pair_counts: n_tasks = %d is outside 1..%d", n_tasks,
+                kMaxGridZ);
+    DPC_REQUIRE(n_words >= 0 && n_words <= kMaxGridX, "dpc_cnet_pair_counts: n_words = %lld is out of domain",
+                (long long)n_words);
+    DPC_REQUIRE((planes || n_words == 0) && word_off && ones, "dpc_cnet_pair_counts: null pointer");
+    const unsigned nt = (unsigned)((d + kPairTile - 1) / kPairTile);
+    DPC_LAUNCH("dpc_cnet_pair_counts", seg_pair_counts_kernel, dim3(nt, nt, (unsigned)n_tasks), dim3(kThreads), 0,
+               (hipStream_t)stream, (const u64 *)planes, n_words, d, word_off, ones);
+    return DPC_OK;
+}
+
+int dpc_cnet_scores(const int32_t *ones, const int32_t *seg_off, const uint8_t *active, int n_tasks, int d, double alpha,
+                    double *gains, double *stats, int32_t *best, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_cnet_scores: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(n_tasks >= 1 && n_tasks <= kMaxGridZ, "dpc_cnet_scores: n_tasks = %d is outside 1..%d", n_tasks, kMaxGridZ);
+    DPC_REQUIRE(alpha >= 0.0, "dpc_cnet_scores: alpha = %g is negative", alpha);
+    DPC_REQUIRE(ones && seg_off && active && gains && stats && best, "dpc_cnet_scores: null pointer");
+    DPC_LAUNCH("dpc_cnet_scores", score_entropy_kernel, dim3((unsigned)((d + kScoreThreads - 1) / kScoreThreads), (unsigned)n_tasks),
+               dim3(kScoreThreads), 0, (hipStream_t)stream, ones, seg_off, active, d, alpha, gains);
+    DPC_LAUNCH("dpc_cnet_scores", score_select_kernel, dim3((unsigned)((n_tasks + kScoreThreads - 1) / kScoreThreads)),
+               dim3(kScoreThreads), 0, (hipStream_t)stream, ones, seg_off, active, n_tasks, d, alpha, gains, stats, best);
+    return DPC_OK;
+}
+
+int dpc_cnet_partition(const uint64_t *planes, int64_t n_words, const int32_t *rows, const int32_t *seg_off,
+                       const int32_t *word_off, const int32_t *cut, const int32_t *out_off, int n_tasks,
+                       int32_t *rows_out, int32_t *child_n, void *stream) {
+    DPC_REQUIRE(n_tasks >= 1 && n_tasks <= kMaxGridX, "dpc_cnet_partition: n_tasks = %d is not positive", n_tasks);
+    DPC_REQUIRE(n_words >= 0 && n_words <= kMaxGridX, "dpc_cnet_partition: n_words = %lld is out of domain",
+                (long long)n_words);
+    DPC_REQUIRE((planes || n_words == 0) && rows && seg_off && word_off && cut && out_off && rows_out && child_n,
+                "dpc_cnet_partition: null pointer");
+    DPC_LAUNCH("dpc_cnet_partition", partition_kernel, dim3((unsigned)n_tasks), dim3(kThreads), 0, (hipStream_t)stream,
+               (const u64 *)planes, n_words, rows, seg_off, word_off, cut, out_off, rows_out, child_n);
+    return DPC_OK;
+}
+
+int dpc_cnet_log_likelihood(const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
+                            const int32_t *node_child, const double *node_logw, const int32_t *leaf_meta,
+                            const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work,
+                            float *out, void *stream) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_cnet_log_likelihood: d = %d is outside 1..%d", d, DPC_MAX_D);
+    DPC_REQUIRE(b >= 0 && b <= kMaxGridX, "dpc_cnet_log_likelihood: b = %lld is out of domain", (long long)b);
+    DPC_REQUIRE(n_nodes >= 1 && n_nodes < (1 << 29), "dpc_cnet_log_likelihood: n_nodes = %d is outside 1..2^29-1", n_nodes);
+    DPC_REQUIRE(levels >= 1 && levels <= d + 1, "dpc_cnet_log_likelihood: levels = %d is outside 1..d+1", levels);
+    DPC_REQUIRE(max_leaf_d >= 1 && max_leaf_d <= d, "dpc_cnet_log_likelihood: max_leaf_d = %d is outside 1..d", max_leaf_d);
+    DPC_REQUIRE(codes && node_col && node_child && leaf_meta && leaf_ints && leaf_params && work && out,
+                "dpc_cnet_log_likelihood: null pointer");
+    DPC_REQUIRE(node_logw || n_nodes == 1, "dpc_cnet_log_likelihood: null pointer (node_logw)");
+    DPC_REQUIRE(((uintptr_t)work & 7) == 0, "dpc_cnet_log_likelihood: work is not 8-byte aligned");
+    if (b == 0) return DPC_OK;
+    char *w = (char *)work;
+    CnetArgs a = {codes, b, node_col, node_child, node_logw, leaf_meta, leaf_ints, leaf_params, levels,
+                  (double *)w, (float *)(w + 8 * (int64_t)levels * b),
+                  (int32_t *)(w + (8 * (int64_t)levels + 8 * (int64_t)max_leaf_d) * b), out};
+    DPC_LAUNCH("dpc_cnet_log_likelihood", cnet_query_kernel, dim3((unsigned)((b + kRowThreads - 1) / kRowThreads)),
+               dim3(kRowThreads), 0, (hipStream_t)stream, a);
+    return DPC_OK;
+}
+
+}  // extern "C"

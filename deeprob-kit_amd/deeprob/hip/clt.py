@@ -88,26 +88,32 @@ def children_csr(bfs, parent):
     return off, idx
 
 
+def check_tree(bfs, parent, params):
+    """``(bfs, parent, params)`` as int64 / int64 / contiguous float32 arrays, checked on the host: the kernels trust these
+    tables (they index device memory with them).  One root, first in ``bfs``, and every other node after its parent."""
+    d = len(parent)
+    if not 1 <= d <= DPC_MAX_D:
+        raise HipError("a tree of {} variables is outside 1..{} (DPC_MAX_D)".format(d, DPC_MAX_D))
+    params = np.ascontiguousarray(params, np.float32)
+    bfs, parent = np.asarray(bfs, np.int64), np.asarray(parent, np.int64)
+    position = np.full(d, -1, np.int64)
+    if bfs.shape == (d,) and ((0 <= bfs) & (bfs < d)).all():
+        position[bfs] = np.arange(d)
+    rest = bfs[1:] if (position >= 0).all() else None
+    if rest is None or parent.shape != (d,) or parent[bfs[0]] != -1 or not ((0 <= parent[rest]) & (parent[rest] < d)).all() \
+            or not (position[parent[rest]] < position[rest]).all():
+        raise ValueError("bfs and tree do not describe one rooted tree")
+    if params.shape != (d, 2, 2):
+        raise ValueError("Invalid conditional probability table (CPT) shape")
+    return bfs, parent, params
+
+
 class DeviceTree:
     """``bfs``, ``parent``, ``params`` and the children lists of one tree on ``device`` (one host-to-device copy)."""
 
     def __init__(self, bfs, parent, params, device):
+        bfs, parent, params = check_tree(bfs, parent, params)
         d = len(parent)
-        if not 1 <= d <= DPC_MAX_D:
-            raise HipError("a tree of {} variables is outside 1..{} (DPC_MAX_D)".format(d, DPC_MAX_D))
-        params = np.ascontiguousarray(params, np.float32)
-        bfs, parent = np.asarray(bfs, np.int64), np.asarray(parent, np.int64)
-        # the kernels trust these tables (they index device memory with them): one root, first in `bfs`, and every other
-        # node after its parent
-        position = np.full(d, -1, np.int64)
-        if bfs.shape == (d,) and ((0 <= bfs) & (bfs < d)).all():
-            position[bfs] = np.arange(d)
-        rest = bfs[1:] if (position >= 0).all() else None
-        if rest is None or parent.shape != (d,) or parent[bfs[0]] != -1 or not ((0 <= parent[rest]) & (parent[rest] < d)).all() \
-                or not (position[parent[rest]] < position[rest]).all():
-            raise ValueError("bfs and tree do not describe one rooted tree")
-        if params.shape != (d, 2, 2):
-            raise ValueError("Invalid conditional probability table (CPT) shape")
         off, idx = children_csr(bfs, parent)
         ints = np.concatenate([np.asarray(bfs, np.int32), np.asarray(parent, np.int32), off, idx])
         buf = torch.from_numpy(np.concatenate([ints.view(np.uint8), params.reshape(-1).view(np.uint8)])).to(device)

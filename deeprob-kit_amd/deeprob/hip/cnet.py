@@ -1,0 +1,197 @@
+"""The cutset-network entry points of ``libdeeprob_clt.so`` (``dpc_cnet_*`` of ``include/deeprob_clt.h``), on top of the
+binding of ``deeprob.hip.clt``: one library, one header, one loader.
+
+:class:`Generation` is one level of the level-synchronous learner -- the row segments of its tasks, their bit planes,
+counts, scores and the partition into the next level; :class:`DeviceCNet` holds a fitted model as one concatenated
+table, uploaded in one copy.  Everything takes and returns device tensors; there is no CPU fallback.
+"""
+import numpy as np
+import torch
+
+from deeprob import hip
+from deeprob.hip import HipError, clt
+from deeprob.hip.clt import DPC_MAX_D, call, load_library
+
+#: int32 counts of scratch per launch of the segmented pair counts (256 MiB): a generation is counted and scored in
+#: chunks of COUNT_INTS / D^2 tasks
+COUNT_INTS = 1 << 26
+#: bytes of scratch per query launch (128 MiB): a long batch is evaluated in pieces
+WORK_BYTES = 1 << 27
+MAX_CHUNK_TASKS = 65535         # (grid.z of the count kernel)
+
+
+def chunk_tasks(d: int) -> int:
+    """Tasks per chunk of a generation for ``d`` columns: at least 1."""
+    return max(1, min(MAX_CHUNK_TASKS, COUNT_INTS // (d * d)))
+
+
+def query_rows(row_bytes: int) -> int:
+    """Rows per query launch for ``row_bytes`` of scratch per row: a multiple of 64, at least 1024."""
+    return max(1024, WORK_BYTES // row_bytes // 64 * 64)
+
+
+class Generation:
+    """The tasks of one depth over the rows ``x`` ``[N, D]``: ``rows`` int32 ``[sum(sizes)]`` on the device, task t owning
+    the next ``sizes[t]`` of them.  The offsets go up in one copy."""
+
+    def __init__(self, x: torch.Tensor, rows: torch.Tensor, sizes):
+        x = hip.require_device_f32(x, 'data')
+        sizes = np.asarray(sizes, np.int64)
+        if x.dim() != 2 or not 1 <= x.shape[1] <= DPC_MAX_D or not 1 <= x.shape[0] < 2 ** 31:
+            raise ValueError("expected data [1 .. 2^31 - 1, 1 .. {}], got {}".format(DPC_MAX_D, tuple(x.shape)))
+        if sizes.ndim != 1 or len(sizes) < 1 or (sizes < 0).any() or int(sizes.sum()) >= 2 ** 31:
+            raise ValueError("expected the sizes of one or more tasks, fewer than 2^31 rows in all")
+        if rows.dtype != torch.int32 or rows.device != x.device or rows.dim() != 1 or rows.shape[0] != int(sizes.sum()) \
+                or not rows.is_contiguous():
+            raise ValueError("expected rows as {} int32 on '{}'".format(int(sizes.sum()), x.device))
+        self.x, self.rows, self.sizes = x, rows, sizes
+        self.n_tasks, self.d = len(sizes), int(x.shape[1])
+        self.seg_off = np.concatenate([[0], np.cumsum(sizes)])
+        self.word_off = np.concatenate([[0], np.cumsum((sizes + 63) // 64)])
+        self.n_words = int(self.word_off[-1])
+        offs = torch.from_numpy(np.concatenate([self.seg_off, self.word_off]).astype(np.int32)).to(x.device)
+        self._seg, self._word = offs[:self.n_tasks + 1], offs[self.n_tasks + 1:]
+        self._st = hip.stream_ptr(x.device)
+        self.planes = None
+
+    def pack(self) -> torch.Tensor:
+        """``[D, n_words]`` int64 bit planes of the generation's rows (``dpc_cnet_gather_pack``)."""
+        planes = torch.empty((self.d, self.n_words), dtype=torch.int64, device=self.x.device)
+        call(load_library().dpc_cnet_gather_pack, self.x.data_ptr(), self.x.shape[0], self.d, self.rows.data_ptr(),
+             self._seg.data_ptr(), self._word.data_ptr(), self.n_tasks, self.n_words, planes.data_ptr(), self._st)
+        self.planes = planes
+        return planes
+
+    def counts(self, t0: int, n: int) -> torch.Tensor:
+        """``[n, D, D]`` int32 co-occurrence counts of the tasks ``t0 .. t0 + n`` (``dpc_cnet_pair_counts``)."""
+        assert self.planes is not None and 0 <= t0 and n >= 1 and t0 + n <= self.n_tasks
+        ones = torch.empty((n, self.d, self.d), dtype=torch.int32, device=self.x.device)
+        call(load_library().dpc_cnet_pair_counts, self.planes.data_ptr(), self.n_words, self.d,
+             self._word[t0:].data_ptr(), n, ones.data_ptr(), self._st)
+        return ones
+
+    def scores(self, ones: torch.Tensor, t0: int, active, alpha: float):
+        """``(gains [n, D] float64, stats [n, 2] float64, best [n, 2] int32)`` of the tasks ``t0 .. t0 + n`` from their
+        counts (``dpc_cnet_scores``); ``active``: ``[n, D]`` bool / uint8, numpy or on the device."""
+        n = ones.shape[0]
+        if not isinstance(active, torch.Tensor):
+            active = torch.from_numpy(np.ascontiguousarray(active, np.uint8))
+        active = active.to(device=self.x.device, dtype=torch.uint8).contiguous()
+        assert ones.shape == (n, self.d, self.d) and active.shape == (n, self.d) and t0 + n <= self.n_tasks
+        dev = self.x.device
+        gains = torch.empty((n, self.d), dtype=torch.float64, device=dev)
+        stats = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        best = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        call(load_library().dpc_cnet_scores, ones.data_ptr(), self._seg[t0:].data_ptr(), active.data_ptr(), n, self.d,
+             float(alpha), gains.data_ptr(), stats.data_ptr(), best.data_ptr(), self._st)
+        return gains, stats, best
+
+    def partition(self, cut):
+        """``(rows_out int32, child_n [T, 2] int32)``: the segments of the tasks with ``cut[t] >= 0`` split stably by that
+        column, zeros first, laid out back to back in task order (``dpc_cnet_partition``)."""
+        cut = np.asarray(cut, np.int64)
+        if cut.shape != (self.n_tasks,) or (cut < -1).any() or (cut >= self.d).any():
+            raise ValueError("expected one cut column (or -1) per task")
+        assert self.planes is not None
+        moved = np.where(cut >= 0, self.sizes, 0)
+        out_off = np.concatenate([[0], np.cumsum(moved)[:-1]])
+        dev = self.x.device
+        args = torch.from_numpy(np.concatenate([cut, out_off]).astype(np.int32)).to(dev)
+        rows_out = torch.empty(int(moved.sum()), dtype=torch.int32, device=dev)
+        child_n = torch.empty((self.n_tasks, 2), dtype=torch.int32, device=dev)
+        call(load_library().dpc_cnet_partition, self.planes.data_ptr(), self.n_words, self.rows.data_ptr(),
+             self._seg.data_ptr(), self._word.data_ptr(), args[:self.n_tasks].data_ptr(), args[self.n_tasks:].data_ptr(),
+             self.n_tasks, rows_out.data_ptr(), child_n.data_ptr(), self._st)
+        return rows_out, child_n
+
+
+class DeviceCNet:
+    """A cutset network over ``d`` columns as the tables of ``dpc_cnet_log_likelihood``, in one host-to-device copy.
+
+    ``node_col`` ``[M]``: the cut column of node k, -1 at a leaf; ``node_child`` ``[M, 2]``: its children (at a leaf,
+    ``[leaf number, -1]``); ``node_logw`` ``[M, 2]`` float64; ``leaves``: per leaf number ``(cols, bfs, parent, params)``,
+    ``cols`` the column of every position of the leaf's scope.  Checked on the host -- the kernel indexes device memory
+    with these tables: node 0 roots one binary tree that reaches every node once, and along every path the cut columns and
+    the leaf's columns are distinct columns of ``0 .. d - 1``."""
+
+    def __init__(self, d, node_col, node_child, node_logw, leaves, device):
+        node_col, node_child = np.asarray(node_col, np.int64), np.asarray(node_child, np.int64)
+        node_logw = np.ascontiguousarray(node_logw, np.float64)
+        m = len(node_col)
+        if not 1 <= d <= DPC_MAX_D:
+            raise HipError("a model of {} variables is outside 1..{} (DPC_MAX_D)".format(d, DPC_MAX_D))
+        if m < 1 or node_child.shape != (m, 2) or node_logw.shape != (m, 2):
+            raise ValueError("the node tables do not describe one cutset network")
+        ints, params, meta = [], [], []
+        n_ints = n_params = 0
+        for cols, bfs, parent, par in leaves:
+            bfs, parent, par = clt.check_tree(bfs, parent, par)
+            cols = np.asarray(cols, np.int64)
+            if cols.shape != (len(parent),):
+                raise ValueError("the node tables do not describe one cutset network")
+            off, idx = clt.children_csr(bfs, parent)
+            ints += [cols.astype(np.int32), bfs.astype(np.int32), parent.astype(np.int32), off, idx]
+            params.append(par.reshape(-1))
+            meta.append((len(parent), n_ints, n_params))
+            n_ints, n_params = n_ints + 5 * len(parent), n_params + 4 * len(parent)
+        # one walk from the root: every node once, columns distinct along a path
+        seen, levels, stack = np.zeros(m, bool), 0, [(0, 1, frozenset())]
+        leaf_seen = np.zeros(len(meta), bool)
+        while stack:
+            k, level, used = stack.pop()
+            ok = 0 <= k < m and not seen[k]
+            if ok:
+                seen[k] = True
+                levels = max(levels, level)
+                col = int(node_col[k])
+                if col < 0:
+                    l = int(node_child[k, 0])
+                    ok = 0 <= l < len(meta) and not leaf_seen[l]
+                    if ok:
+                        leaf_seen[l] = True
+                        cols = leaves[l][0]
+                        ok = len(set(int(c) for c in cols)) == len(cols) and all(0 <= int(c) < d and int(c) not in used
+                                                                                 for c in cols)
+                else:
+                    ok = col < d and col not in used
+                    stack += [(int(node_child[k, 1]), level + 1, used | {col}), (int(node_child[k, 0]), level + 1, used | {col})]
+            if not ok:
+                raise ValueError("the node tables do not describe one cutset network")
+        if not seen.all() or not leaf_seen.all():
+            raise ValueError("the node tables do not describe one cutset network")
+        ints_all = np.concatenate([node_col.astype(np.int32), node_child.astype(np.int32).reshape(-1),
+                                   np.asarray(meta, np.int32).reshape(-1)] + ints)
+        buf = torch.from_numpy(np.concatenate([node_logw.reshape(-1).view(np.uint8), ints_all.view(np.uint8),
+                                               np.concatenate(params).view(np.uint8)])).to(device)
+        self.d, self.n_nodes, self.levels, self.device, self._buf = int(d), m, levels, buf.device, buf
+        self.max_leaf_d = max(k for k, _, _ in meta)
+        self.node_logw = buf[:16 * m].view(torch.float64)
+        ints_d = buf[16 * m:16 * m + 4 * len(ints_all)].view(torch.int32)
+        self.node_col, self.node_child = ints_d[:m], ints_d[m:3 * m]
+        self.leaf_meta, self.leaf_ints = ints_d[3 * m:3 * m + 3 * len(meta)], ints_d[3 * m + 3 * len(meta):]
+        self.leaf_params = buf[16 * m + 4 * len(ints_all):].view(torch.float32)
+        self.row_bytes = 12 * self.levels + 8 * self.max_leaf_d
+
+
+def log_likelihood(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
+    """``[B]`` float32 (``dpc_cnet_log_likelihood``); NaN entries are marginalised."""
+    lib = load_library()
+    x = hip.require_device_f32(x, 'x')
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != model.d:
+        raise ValueError("expected inputs [B, {}], got {}".format(model.d, tuple(x.shape)))
+    if x.device != model.device:
+        raise HipError("x lives on '{}', the model on '{}'".format(x.device, model.device))
+    b, d = x.shape
+    st = hip.stream_ptr(x.device)
+    out = torch.empty(b, dtype=torch.float32, device=x.device)
+    step = query_rows(model.row_bytes)
+    work = torch.empty(model.row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
+    for r0 in range(0, b, step):
+        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
+        n = xs.shape[0]
+        codes = clt.pack_query(xs)
+        call(lib.dpc_cnet_log_likelihood, codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(),
+             model.node_child.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
+             model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d, work.data_ptr(),
+             os_.data_ptr(), st)
+    return out

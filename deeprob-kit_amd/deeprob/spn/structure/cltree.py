@@ -22,7 +22,7 @@ import numpy as np
 from deeprob.spn.structure.leaf import Leaf, LeafType
 from deeprob.utils.random import RandomState, check_random_state
 from deeprob.utils.graph import build_tree_structure, compute_bfs_ordering, maximum_spanning_tree
-from deeprob.utils.statistics import compute_mutual_information, estimate_priors_joints
+from deeprob.utils.statistics import compute_mutual_information, pair_counts, priors_joints_from_counts
 
 
 def _post_order(root):
@@ -137,7 +137,12 @@ class BinaryCLT(Leaf):
         if self.root is None:
             self.root = int(random_state.choice(len(self.scope)))
 
-        priors, joints = estimate_priors_joints(data, alpha=alpha)
+        self.fit_counts(*pair_counts(data), alpha=alpha)
+
+    def fit_counts(self, ones: np.ndarray, n_samples: int, alpha: float = 0.1):
+        """The host part of ``fit``: structure (unless a tree was given) and parameters from the exact co-occurrence counts
+        ``ones`` ``[len(scope), len(scope)]`` of ``n_samples`` rows.  ``root`` must be set."""
+        priors, joints = priors_joints_from_counts(ones, n_samples, alpha=alpha)
         if self.tree is None:
             self.bfs, self.tree = maximum_spanning_tree(self.root, compute_mutual_information(priors, joints))
         with np.errstate(divide='ignore'):      # (alpha = 0 can leave a zero probability)

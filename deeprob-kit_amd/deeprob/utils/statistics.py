@@ -13,9 +13,10 @@ from typing import Tuple
 import numpy as np
 
 
-def pair_counts(data) -> Tuple[np.ndarray, int]:
-    """``(ones [D, D] int64, N)`` of binary ``data`` ``[N, D]``: a numpy array (counted on the current HIP device) or a
-    device tensor.  ValueError for NaN or values other than 0 / 1; HipError for a CPU tensor or a missing library."""
+def device_binary_rows(data):
+    """Binary ``data`` ``[N, D]`` as a float32 tensor on a HIP device: a numpy array is uploaded to the current device, a
+    device tensor is taken as it is.  ValueError for NaN or values other than 0 / 1; HipError for a CPU tensor or a
+    missing library."""
     import torch
     from deeprob.hip import HipError, clt
     if isinstance(data, torch.Tensor):
@@ -39,8 +40,45 @@ def pair_counts(data) -> Tuple[np.ndarray, int]:
         x = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
     if x.shape[0] < 1 or x.shape[0] >= 2 ** 31:
         raise ValueError("expected 1 .. 2^31 - 1 rows, got {}".format(x.shape[0]))
+    return x
+
+
+def pair_counts(data) -> Tuple[np.ndarray, int]:
+    """``(ones [D, D] int64, N)`` of binary ``data`` ``[N, D]``: a numpy array (counted on the current HIP device) or a
+    device tensor.  ValueError for NaN or values other than 0 / 1; HipError for a CPU tensor or a missing library."""
+    from deeprob.hip import clt
+    x = device_binary_rows(data)
     ones = clt.pair_counts(clt.pack_bits(x))
     return ones.cpu().numpy().astype(np.int64), int(x.shape[0])
+
+
+def _cells(ones: np.ndarray, n: int) -> np.ndarray:
+    """``[D, D, 2, 2]`` int64: ``cells[i, j, k, l]`` = rows with ``x_i = k`` and ``x_j = l``."""
+    d = ones.shape[0]
+    col = np.diag(ones)                              # col[i] = rows with x_i = 1
+    cells = np.empty((d, d, 2, 2), np.int64)
+    cells[:, :, 1, 1] = ones
+    cells[:, :, 0, 1] = col[None, :] - ones          # x_i = 0, x_j = 1
+    cells[:, :, 1, 0] = col[:, None] - ones
+    cells[:, :, 0, 0] = n - col[None, :] - col[:, None] + ones
+    return cells
+
+
+def compute_prior_counts(data) -> np.ndarray:
+    """``[D, 2]`` float32, ``[i, k]`` = rows with ``x_i = k`` (the reference's statistics.py:185-201), from the exact
+    device counts of :func:`pair_counts`."""
+    ones, n = pair_counts(data)
+    out = np.empty((ones.shape[0], 2), np.float32)
+    out[:, 1] = np.diag(ones)
+    out[:, 0] = n - np.diag(ones)
+    return out
+
+
+def compute_joint_counts(data) -> np.ndarray:
+    """``[D, D, 2, 2]`` float32, ``[i, j, k, l]`` = rows with ``x_i = k`` and ``x_j = l`` (the reference's
+    statistics.py:204-225; the diagonal holds a variable against itself), from :func:`pair_counts`."""
+    ones, n = pair_counts(data)
+    return _cells(ones, n).astype(np.float32)
 
 
 def priors_joints_from_counts(ones: np.ndarray, n_samples: int, alpha: float = 0.1) -> Tuple[np.ndarray, np.ndarray]:
@@ -53,11 +91,7 @@ def priors_joints_from_counts(ones: np.ndarray, n_samples: int, alpha: float = 0
     col = np.diag(ones)                              # col[i] = rows with x_i = 1
     n = int(n_samples)
     # the four cells of every pair in integers; float32 holds them exactly for n < 2^24, as it holds the reference's
-    cells = np.empty((d, d, 2, 2), np.int64)
-    cells[:, :, 1, 1] = ones
-    cells[:, :, 0, 1] = col[None, :] - ones          # x_i = 0, x_j = 1
-    cells[:, :, 1, 0] = col[:, None] - ones
-    cells[:, :, 0, 0] = n - col[None, :] - col[:, None] + ones
+    cells = _cells(ones, n)
 
     priors = np.empty((d, 2), np.float32)
     priors[:, 1] = (col.astype(np.float32) + 2 * alpha) / (n + 4 * alpha)

@@ -105,6 +105,86 @@ int dpc_clt_sample(const float *x, const uint8_t *codes, int64_t b, int d, const
                    const float *params, const int32_t *child_off, const int32_t *child_idx, uint64_t seed,
                    int64_t row0, float *work, float *out, void *stream);
 
+/* ---- Cutset networks (deeprob.spn.structure.cnet.BinaryCNet; reference spn/structure/cnet.py) -------
+ *
+ * A cutset network is an OR tree that conditions on one binary variable per node, with a Chow-Liu
+ * tree at every leaf.  Learning is LEVEL SYNCHRONOUS: a generation is every open node ("task") of one
+ * depth.  Task t owns the rows rows[seg_off[t] .. seg_off[t+1]) of a row-index array (indices into
+ * the training matrix x) and a set of still-active columns; the launches of a generation -- gather-pack,
+ * pair counts, scores, partition -- do not depend on the number of tasks.
+ *
+ * Planes of a generation: [d, n_words] uint64.  Task t owns the words word_off[t] .. word_off[t+1) of
+ * every plane, word_off[t+1] - word_off[t] = (n_t + 63) / 64 with n_t = seg_off[t+1] - seg_off[t]: every
+ * segment starts on a word boundary, a task of 0 rows owns no word, word_off[n_tasks] = n_words.
+ * seg_off, word_off: [n_tasks + 1] int32, non-decreasing; they and `rows` are trusted (they index
+ * device memory), except that a row index outside 0 .. n-1 packs as a row of zeros. */
+
+/* Bit (p % 64) of planes[c * n_words + word_off[t] + p / 64] is set iff x[rows[seg_off[t] + p]][c] == 1,
+ * p < n_t; the bits of a task's last word past its last row are zero.  All d columns are packed.
+ * x: [n, d] float32 row major. */
+int dpc_cnet_gather_pack(const float *x, int64_t n, int d, const int32_t *rows, const int32_t *seg_off,
+                         const int32_t *word_off, int n_tasks, int64_t n_words, uint64_t *planes, void *stream);
+
+/* ones[t][i][j] = rows of task t with x_i = x_j = 1, for n_tasks <= 65535 consecutive tasks: AND +
+ * popcount over the task's words only, exact integers, about d * d * n_words popcounts in all
+ * whatever the number of tasks.  word_off: the [n_tasks + 1] entries of these tasks (a pointer into
+ * the generation's array; the values stay offsets into the planes).  ones: [n_tasks, d, d] int32,
+ * all zero for a task of 0 rows. */
+int dpc_cnet_pair_counts(const uint64_t *planes, int64_t n_words, int d, const int32_t *word_off, int n_tasks,
+                         int32_t *ones, void *stream);
+
+/* The cut scores of cnet.py:168-198, in float64 from the exact counts (the reference evaluates them in
+ * float32).  For task t with n = seg_off[t+1] - seg_off[t] rows, c_i = ones[t][i][i], over the columns
+ * with active[t][i] != 0 only (d_a of them), a2 = 2 alpha, a4 = 4 alpha:
+ *   p_i1 = (c_i + a2) / (n + a4), p_i0 = 1 - p_i1;
+ *   mean_entropy = -S / d_a, S = sum over active i IN INCREASING i of (p_i0 ln p_i0 + p_i1 ln p_i1);
+ *   cells of (x_i = a, x_j = b): c11 = ones[i][j], c10 = c_i - c11, c01 = c_j - c11,
+ *                                c00 = ((n - c_i) - c_j) + c11;
+ *   h_ij1 = -(q0 ln q0 + q1 ln q1) with q0 = (c10 + a2) / (c_i + a4), q1 = (c11 + a2) / (c_i + a4);
+ *   h_ij0 = -(q0 ln q0 + q1 ln q1) with q0 = (c00 + a2) / ((n - c_i) + a4), q1 = (c01 + a2) / ((n - c_i) + a4);
+ *   H_i,a = (sum over active j != i IN INCREASING j of h_ija) / (d_a - 1)   (0 when d_a = 1);
+ *   gain_i = mean_entropy - ((c_i / n) H_i,1 + (1 - c_i / n) H_i,0)          (c_i / n := 0 when n = 0).
+ * gains: [n_tasks, d] float64, -inf at an inactive column.  stats: [n_tasks, 2] float64 = (mean_entropy,
+ * the largest gain).  best: [n_tasks, 2] int32 = (the smallest i with the largest gain, c_i of it);
+ * (-1, 0) with a gain of -inf when no column is active.  n_tasks <= 65535.  active: [n_tasks, d] uint8. */
+int dpc_cnet_scores(const int32_t *ones, const int32_t *seg_off, const uint8_t *active, int n_tasks, int d, double alpha,
+                    double *gains, double *stats, int32_t *best, void *stream);
+
+/* Stable partition of every task with cut[t] >= 0 by the bits of plane cut[t]:
+ * rows_out[out_off[t] ..] = the task's row indices with x_cut = 0 in their order, then those with
+ * x_cut = 1 in their order (n_t entries in all); child_n[t] = (zeros, ones).  A task with cut[t] = -1
+ * copies nothing and gets child_n[t] = (0, 0).  The caller lays the splitting tasks out back to back
+ * (out_off[t] = the rows of the splitting tasks before t), so that the segments tile rows_out.
+ * cut, out_off: [n_tasks] int32; child_n: [n_tasks, 2] int32. */
+int dpc_cnet_partition(const uint64_t *planes, int64_t n_words, const int32_t *rows, const int32_t *seg_off,
+                       const int32_t *word_off, const int32_t *cut, const int32_t *out_off, int n_tasks,
+                       int32_t *rows_out, int32_t *child_n, void *stream);
+
+/* out[r] = log P(the observed entries of row r) under a cutset network.  The model (trusted tables):
+ *   node_col[n_nodes]       the cut column of an OR node, -1 at a leaf; node 0 is the root;
+ *   node_child[n_nodes][2]  the children for x_col = 0 / 1; at a leaf, node_child[k][0] = its leaf number;
+ *   node_logw[n_nodes][2]   float64 log weights (unused at a leaf);
+ *   leaf_meta[n_leaves][3]  (d_l, offset into leaf_ints, offset into leaf_params);
+ *   leaf_ints               per leaf: col[d_l] (the column of each position of the leaf's scope), then
+ *                           bfs[d_l], parent[d_l], child_off[d_l + 1], child_idx[d_l - 1] of its tree;
+ *   leaf_params             per leaf: params[d_l][2][2] float32.
+ * A row WITHOUT NaN descends one path: the float64 sum of node_logw[k][x_col] from the root to the
+ * leaf, then of the leaf's params[i][x_parent(i)][x_i] over i = 0 .. d_l - 1, in this order, rounded once
+ * to float32.  A row WITH NaN is evaluated depth first, V(root) rounded to float32, where
+ *   V(leaf)    = the value dpc_clt_log_likelihood gives the leaf's tree on the leaf's columns (float32:
+ *                the gather path if none of them is NaN, else the upward pass with R = lse);
+ *   V(OR node) = node_logw[k][x] + V(child x)                                       x_col observed,
+ *              = lse64(node_logw[k][0] + V(child 0), node_logw[k][1] + V(child 1))   x_col NaN,
+ *   lse64(a,b) = hi + log1p(exp(lo - hi)) in float64, -inf when hi = -inf.
+ * levels: the largest number of nodes on a path from the root to a leaf (1 for a lone leaf);
+ * max_leaf_d: the largest d_l.  work: b * (12 * levels + 8 * max_leaf_d) bytes of scratch, 8-byte
+ * aligned: per row a stack of `levels` (float64, int32) entries and the 2 * max_leaf_d floats of the
+ * upward pass.  codes: the output of dpc_pack_query for the same b, d. */
+int dpc_cnet_log_likelihood(const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
+                            const int32_t *node_child, const double *node_logw, const int32_t *leaf_meta,
+                            const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work,
+                            float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
