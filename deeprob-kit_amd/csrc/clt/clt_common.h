@@ -1,5 +1,5 @@
 // What the translation units of libdeeprob_clt.so share: the thread-local error text behind dpc_last_error(), the
-// argument and launch checks, and lse2 of the header's order of operations.
+// argument and launch checks, lse2 of the header's order of operations, and the shape of the segmented pair-count tile.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -13,6 +13,14 @@
 #endif
 
 namespace dpc_detail {
+
+// The segmented pair counts (cnet.hip, cut.hip): a work-group of kPairThreads owns kPairTile x kPairTile variable pairs
+// and stages kPairWords plane words of both operands per step; grid.z is the task or the entry.
+constexpr int kPairThreads = 256;
+constexpr int kPairTile = 32;
+constexpr int kPairWords = 32;
+constexpr int kMaxGridZ = 65535;
+constexpr int64_t kMaxGridX = 2147483647;
 
 // (an inline variable: one copy for the whole library)
 inline thread_local char g_error[512] = "";

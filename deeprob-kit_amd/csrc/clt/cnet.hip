@@ -18,12 +18,12 @@ using dpc_detail::lse2;
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
 constexpr int kTile = 64;
-constexpr int kPairTile = 32;
-constexpr int kPairWords = 32;
+using dpc_detail::kPairTile;
+using dpc_detail::kPairWords;
 constexpr int kRowThreads = 64;
 constexpr int kScoreThreads = 64;
-constexpr int64_t kMaxGridX = 2147483647;
-constexpr int kMaxGridZ = 65535;
+using dpc_detail::kMaxGridX;
+using dpc_detail::kMaxGridZ;
 
 // ---- gather-pack ---------------------------------------------------------------------------------------------------------
 // One work-group per plane word x 64 columns; the word's task is found by bisection of word_off (empty tasks own no word).

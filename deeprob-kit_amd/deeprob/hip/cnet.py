@@ -1,5 +1,5 @@
-"""The cutset-network entry points of ``libdeeprob_clt.so`` (``dpc_cnet_*`` of ``include/deeprob_clt.h``), on top of the
-binding of ``deeprob.hip.clt``: one library, one header, one loader.
+"""The cutset-network entry points of ``libdeeprob_clt.so`` (``dpc_cnet_*`` and ``dpc_cut_*`` of
+``include/deeprob_clt.h``), on top of the binding of ``deeprob.hip.clt``: one library, one header, one loader.
 
 :class:`Generation` is one level of the level-synchronous learner -- the row segments of its tasks, their bit planes,
 counts, scores and the partition into the next level; :class:`DeviceCNet` holds a fitted model as one concatenated
@@ -69,6 +69,24 @@ class Generation:
         call(load_library().dpc_cnet_pair_counts, self.planes.data_ptr(), self.n_words, self.d,
              self._word[t0:].data_ptr(), n, ones.data_ptr(), self._st)
         return ones
+
+    def cut_counts(self, entry_task, entry_col) -> torch.Tensor:
+        """``[E, D, D]`` int32: for entry e the co-occurrence counts of the rows of task ``entry_task[e]`` with
+        ``x[entry_col[e]] = 1`` (``dpc_cut_pair_counts``); one launch for at most ``MAX_CHUNK_TASKS`` entries, the table in
+        one copy.  An entry costs as many ints as a task: size the entry chunks with :func:`chunk_tasks`."""
+        entry_task, entry_col = np.asarray(entry_task, np.int64), np.asarray(entry_col, np.int64)
+        e = len(entry_task)
+        if entry_task.shape != (e,) or entry_col.shape != (e,) or not 1 <= e <= MAX_CHUNK_TASKS:
+            raise ValueError("expected 1 .. {} entries, a task and a column each".format(MAX_CHUNK_TASKS))
+        if (entry_task < 0).any() or (entry_task >= self.n_tasks).any() or (entry_col < 0).any() or (entry_col >= self.d).any():
+            raise ValueError("an entry names a task outside 0 .. {} or a column outside 0 .. {}".format(self.n_tasks - 1,
+                                                                                                        self.d - 1))
+        assert self.planes is not None
+        table = torch.from_numpy(np.concatenate([entry_task, entry_col]).astype(np.int32)).to(self.x.device)
+        ones1 = torch.empty((e, self.d, self.d), dtype=torch.int32, device=self.x.device)
+        call(load_library().dpc_cut_pair_counts, self.planes.data_ptr(), self.n_words, self.d, self._word.data_ptr(),
+             self.n_tasks, table[:e].data_ptr(), table[e:].data_ptr(), e, ones1.data_ptr(), self._st)
+        return ones1
 
     def scores(self, ones: torch.Tensor, t0: int, active, alpha: float):
         """``(gains [n, D] float64, stats [n, 2] float64, best [n, 2] int32)`` of the tasks ``t0 .. t0 + n`` from their

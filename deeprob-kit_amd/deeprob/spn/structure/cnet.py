@@ -18,8 +18,9 @@ leaf in breadth-first order, left child before right.  And in ``log_likelihood``
 silently drops a row from the sum at the first OR node whose variable is NaN (cnet.py:226-229).  The scores are float64
 (the reference's are float32), which only matters where two gains tie to float32 precision.
 
-Not built: ``mpe`` and ``sample`` (the reference has none for cutset networks), ``learn_cnet_bd`` / ``learn_cnet_bic``
-(``learning/cnet_bayesian.py`` needs ``scipy.special.gammaln``, which this package does not import) and the xpc learners.
+Not built: ``mpe`` and ``sample`` (the reference has none for cutset networks) and the xpc learners.  The scored learners
+``learn_cnet_bd`` / ``learn_cnet_bic`` are built in ``deeprob.spn.learning.cnet_bayesian`` and return a
+``BinaryCNet``.
 """
 import time
 from typing import List, Optional, Union

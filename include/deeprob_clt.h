@@ -185,6 +185,24 @@ int dpc_cnet_log_likelihood(const uint8_t *codes, int64_t b, int d, int n_nodes,
                             const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work,
                             float *out, void *stream);
 
+/* ---- Scored cutset learners (deeprob.spn.learning.cnet_bayesian; reference spn/learning/cnet_bayesian.py) ----
+ *
+ * learn_cnet_bd / learn_cnet_bic try several candidate cut columns per task and fit a Chow-Liu tree to each
+ * side of every candidate.  All a fit needs is the co-occurrence counts of the task's rows CONDITIONED on
+ * the candidate column.  An entry e names a task entry_task[e] of the generation (an index into word_off)
+ * and a cut column entry_col[e]:
+ *   ones1[e][i][j] = rows of the task with x_i = x_j = x_c = 1
+ *                  = popcount(P_i & P_j & P_c) over the words word_off[task] .. word_off[task + 1)
+ * of the planes of dpc_cnet_gather_pack, exact integers.  The side x_c = 0 is the caller's subtraction
+ * dpc_cnet_pair_counts[task] - ones1[e]; the side sizes are ones[task][c][c] and n_task minus it.
+ * ones1: [n_entries, d, d] int32, n_entries <= 65535; every element is written, each [d, d] block is
+ * symmetric, and it is all zero for an entry whose task owns no word -- or whose task is outside
+ * 0 .. n_tasks - 1 or whose column is outside 0 .. d - 1: such an entry reads nothing.  Row i = c and column
+ * j = c hold ones[task][c][.], the diagonal holds popcount(P_i & P_c).  word_off: the generation's
+ * [n_tasks + 1] offsets (trusted, as above).  Entries may name the tasks in any order, any number of times. */
+int dpc_cut_pair_counts(const uint64_t *planes, int64_t n_words, int d, const int32_t *word_off, int n_tasks,
+                        const int32_t *entry_task, const int32_t *entry_col, int n_entries, int32_t *ones1, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
