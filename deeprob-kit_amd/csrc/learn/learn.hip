@@ -79,22 +79,14 @@ __global__ __launch_bounds__(kThreads) void column_counts_kernel(
     if ((int)threadIdx.x < kmax) counts[item * kmax + threadIdx.x] = cnt[threadIdx.x];
 }
 
-// ---- G statistics ----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void pair_g_kernel(
-    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
-    const int32_t *__restrict__ pair_col_i, const int32_t *__restrict__ pair_col_j, const int64_t *__restrict__ pair_row_off,
-    const int32_t *__restrict__ pair_n, const int32_t *__restrict__ pair_ki, const int32_t *__restrict__ pair_kj,
-    double *__restrict__ g) {
-    __shared__ int joint[DPL_MAX_K * DPL_MAX_K];
-    __shared__ double term[DPL_MAX_K * DPL_MAX_K];
-    __shared__ double m1[DPL_MAX_K], m2[DPL_MAX_K];
-    const int64_t q = blockIdx.x;
-    const int ki = pair_ki[q], kj = pair_kj[q], n = pair_n[q], cells = ki * kj;
+// ---- joint counts of a column pair (shared by the G statistic and the maximal correlation) -------------------------------
+// joint[a * kj + b] = rows of the segment with (ci, cj) == (a, b), a < ki, b < kj; all kThreads threads call it, and the
+// counts are complete for every thread when it returns.
+__device__ __forceinline__ void count_joint(int *joint, const uint8_t *__restrict__ ci, const uint8_t *__restrict__ cj,
+                                            const int32_t *__restrict__ rows, int n, int ki, int kj) {
     joint[threadIdx.x] = 0;     // (kThreads == DPL_MAX_K * DPL_MAX_K)
     __syncthreads();
-    const uint8_t *ci = x + (int64_t)pair_col_i[q] * n_rows, *cj = x + (int64_t)pair_col_j[q] * n_rows;
-    const int32_t *rows = row_index + pair_row_off[q];
-    if (cells <= 4) {
+    if (ki * kj <= 4) {
         // binary pairs: the (up to) four cells in registers, one LDS add per thread and cell
         int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
         for (int r = threadIdx.x; r < n; r += kThreads) {
@@ -118,6 +110,21 @@ __global__ __launch_bounds__(kThreads) void pair_g_kernel(
         }
     }
     __syncthreads();
+}
+
+// ---- G statistics ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void pair_g_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ pair_col_i, const int32_t *__restrict__ pair_col_j, const int64_t *__restrict__ pair_row_off,
+    const int32_t *__restrict__ pair_n, const int32_t *__restrict__ pair_ki, const int32_t *__restrict__ pair_kj,
+    double *__restrict__ g) {
+    __shared__ int joint[DPL_MAX_K * DPL_MAX_K];
+    __shared__ double term[DPL_MAX_K * DPL_MAX_K];
+    __shared__ double m1[DPL_MAX_K], m2[DPL_MAX_K];
+    const int64_t q = blockIdx.x;
+    const int ki = pair_ki[q], kj = pair_kj[q], n = pair_n[q], cells = ki * kj;
+    count_joint(joint, x + (int64_t)pair_col_i[q] * n_rows, x + (int64_t)pair_col_j[q] * n_rows, row_index + pair_row_off[q], n,
+                ki, kj);
     const int t = threadIdx.x;
     if (t < ki) {
         double s = 0.0;
@@ -142,6 +149,117 @@ __global__ __launch_bounds__(kThreads) void pair_g_kernel(
         double s = term[0];
         for (int c = 1; c < cells; ++c) s += term[c];
         g[q] = 2.0 * s;
+    }
+}
+
+// ---- maximal correlation (the exact value of the RDC score of two discrete columns) ---------------------------------
+// The header states the order of operations; tests/rdc_ref.py:maxcorr_jacobi restates it.  Every thread of the block
+// forms the three dot products of a rotation itself (broadcast LDS reads, the same sequential order), so every branch
+// below is block-uniform and the barriers around the update are reached by all threads or by none.
+constexpr double kJacobiTol = 3.552713678800501e-15;    // 2^-48
+constexpr int kJacobiSweeps = 30;
+
+__global__ __launch_bounds__(kThreads) void pair_maxcorr_kernel(
+    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
+    const int32_t *__restrict__ pair_col_i, const int32_t *__restrict__ pair_col_j, const int64_t *__restrict__ pair_row_off,
+    const int32_t *__restrict__ pair_n, const int32_t *__restrict__ pair_ki, const int32_t *__restrict__ pair_kj,
+    double *__restrict__ score) {
+    __shared__ int joint[DPL_MAX_K * DPL_MAX_K];
+    __shared__ double w[DPL_MAX_K * DPL_MAX_K];        // vector v of the shorter side at w[v * DPL_MAX_K ...]
+    __shared__ int r[DPL_MAX_K], s[DPL_MAX_K], pa[DPL_MAX_K], pb[DPL_MAX_K], sizes[2];
+    const int64_t q = blockIdx.x;
+    const int ki = min(pair_ki[q], DPL_MAX_K), kj = min(pair_kj[q], DPL_MAX_K);
+    count_joint(joint, x + (int64_t)pair_col_i[q] * n_rows, x + (int64_t)pair_col_j[q] * n_rows, row_index + pair_row_off[q],
+                pair_n[q], ki, kj);
+    const int t = threadIdx.x;
+    if (t < ki) {
+        int sum = 0;
+        for (int b = 0; b < kj; ++b) sum += joint[t * kj + b];
+        r[t] = sum;
+    }
+    if (t >= 64 && t < 64 + kj) {
+        const int b = t - 64;
+        int sum = 0;
+        for (int a = 0; a < ki; ++a) sum += joint[a * kj + b];
+        s[b] = sum;
+    }
+    __syncthreads();
+    if (t == 0) {       // the present values of each side, in increasing order
+        int na = 0, nb = 0;
+        for (int a = 0; a < ki; ++a)
+            if (r[a] > 0) pa[na++] = a;
+        for (int b = 0; b < kj; ++b)
+            if (s[b] > 0) pb[nb++] = b;
+        sizes[0] = na;
+        sizes[1] = nb;
+    }
+    __syncthreads();
+    const int na = sizes[0], nb = sizes[1];
+    if (na < 2 || nb < 2) {
+        if (t == 0) score[q] = 0.0;
+        return;
+    }
+    if (na == 2 && nb == 2) {
+        if (t == 0) {
+            const int64_t c00 = joint[pa[0] * kj + pb[0]], c01 = joint[pa[0] * kj + pb[1]];
+            const int64_t c10 = joint[pa[1] * kj + pb[0]], c11 = joint[pa[1] * kj + pb[1]];
+            const int64_t det = c00 * c11 - c01 * c10;
+            const double num = (double)(det < 0 ? -det : det);
+            const double den = sqrt((double)((int64_t)r[pa[0]] * r[pa[1]]) * (double)((int64_t)s[pb[0]] * s[pb[1]]));
+            score[q] = fmin(1.0, num / den);
+        }
+        return;
+    }
+    const bool rows_are_vectors = na <= nb;
+    const int p = rows_are_vectors ? na : nb, len = rows_are_vectors ? nb : na;
+    if (t < p * len) {
+        const int v = t / len, e = t - v * len;
+        const int a = pa[rows_are_vectors ? v : e], b = pb[rows_are_vectors ? e : v];
+        int64_t total = 0;
+        for (int k = 0; k < na; ++k) total += r[pa[k]];
+        const int64_t rs = (int64_t)r[a] * s[b];
+        const double num = (double)((int64_t)joint[a * kj + b] * total - rs);
+        const double den = (double)total * sqrt((double)rs);
+        w[v * DPL_MAX_K + e] = num / den;
+    }
+    __syncthreads();
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+        bool rotated = false;
+        for (int i = 0; i < p - 1; ++i) {
+            for (int j = i + 1; j < p; ++j) {
+                const double *wi = w + i * DPL_MAX_K, *wj = w + j * DPL_MAX_K;
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+                for (int e = 0; e < len; ++e) {
+                    const double u = wi[e], v = wj[e];
+                    alpha = alpha + u * u;
+                    beta = beta + v * v;
+                    gamma = gamma + u * v;
+                }
+                if (!(fabs(gamma) > kJacobiTol * sqrt(alpha * beta))) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double tn = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / sqrt(1.0 + tn * tn);
+                const double sn = cs * tn;
+                __syncthreads();        // every thread has read both vectors
+                if (t < len) {
+                    const double u = wi[t], v = wj[t];
+                    w[i * DPL_MAX_K + t] = cs * u - sn * v;
+                    w[j * DPL_MAX_K + t] = sn * u + cs * v;
+                }
+                __syncthreads();
+            }
+        }
+        if (!rotated) break;
+    }
+    if (t == 0) {
+        double best = 0.0;
+        for (int v = 0; v < p; ++v) {
+            double sq = 0.0;
+            for (int e = 0; e < len; ++e) sq = sq + w[v * DPL_MAX_K + e] * w[v * DPL_MAX_K + e];
+            best = sq > best ? sq : best;
+        }
+        score[q] = fmin(1.0, sqrt(best));
     }
 }
 
@@ -345,7 +463,7 @@ bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
 extern "C" {
 
 const char *dpl_last_error(void) { return g_error; }
-int dpl_abi_version(void) { return 1; }
+int dpl_abi_version(void) { return 2; }
 
 int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
                       const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,
@@ -368,6 +486,19 @@ int dpl_pair_g(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_
     DPL_REQUIRE(n_pairs >= 1 && n_pairs <= kMaxGrid, "dpl_pair_g: n_pairs = %lld out of domain", (long long)n_pairs);
     DPL_LAUNCH("dpl_pair_g", pair_g_kernel, dim3((unsigned)n_pairs), dim3(kThreads), 0, (hipStream_t)stream, x, n_rows,
                row_index, pair_col_i, pair_col_j, pair_row_off, pair_n, pair_ki, pair_kj, g);
+    return DPL_OK;
+}
+
+int dpl_pair_maxcorr(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                     const int32_t *pair_col_i, const int32_t *pair_col_j, const int64_t *pair_row_off, const int32_t *pair_n,
+                     const int32_t *pair_ki, const int32_t *pair_kj, int64_t n_pairs, double *score, void *stream) {
+    static_assert(kThreads == DPL_MAX_K * DPL_MAX_K, "one thread per joint cell");
+    if (!common_ok(x, n_rows, n_cols, row_index, n_index, "dpl_pair_maxcorr")) return DPL_EINVAL;
+    DPL_REQUIRE(pair_col_i && pair_col_j && pair_row_off && pair_n && pair_ki && pair_kj && score,
+                "dpl_pair_maxcorr: null argument");
+    DPL_REQUIRE(n_pairs >= 1 && n_pairs <= kMaxGrid, "dpl_pair_maxcorr: n_pairs = %lld out of domain", (long long)n_pairs);
+    DPL_LAUNCH("dpl_pair_maxcorr", pair_maxcorr_kernel, dim3((unsigned)n_pairs), dim3(kThreads), 0, (hipStream_t)stream, x, n_rows,
+               row_index, pair_col_i, pair_col_j, pair_row_off, pair_n, pair_ki, pair_kj, score);
     return DPL_OK;
 }
 

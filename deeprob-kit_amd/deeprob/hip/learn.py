@@ -147,6 +147,19 @@ def pair_g(data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> tor
     return g
 
 
+def pair_maxcorr(data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> torch.Tensor:
+    """``[n_pairs]`` float64 maximal correlations (``dpl_pair_maxcorr``); the pair tables are host arrays."""
+    lib = load_library()
+    n_pairs = len(col_i)
+    t = upload(data.device, ci=np.asarray(col_i, np.int32), cj=np.asarray(col_j, np.int32), off=np.asarray(row_off, np.int64),
+               n=np.asarray(n, np.int32), ki=np.asarray(ki, np.int32), kj=np.asarray(kj, np.int32))
+    score = torch.empty(n_pairs, dtype=torch.float64, device=data.device)
+    call(lib.dpl_pair_maxcorr, *data.head(row_index), t['ci'].data_ptr(), t['cj'].data_ptr(), t['off'].data_ptr(),
+         t['n'].data_ptr(), t['ki'].data_ptr(), t['kj'].data_ptr(), n_pairs, score.data_ptr(), _stream(data.device))
+    COUNTERS['kernels'] += 1
+    return score
+
+
 def partition_rows(row_index, src_off, src_n, label_off, label, dst_off, dst_n, labels, n_out: int) -> torch.Tensor:
     """The next generation's ``[n_out]`` int32 row-index array (``dpl_partition_rows``); ``labels``: a device uint8
     tensor or None."""

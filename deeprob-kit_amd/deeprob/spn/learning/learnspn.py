@@ -6,8 +6,8 @@ The reference pops one task at a time from a FIFO queue.  The queue is breadth f
 (one depth of the task tree, a retry counting as a child) are consecutive in it and their children follow in the same
 order; a generation is processed here as a whole: column counts of all its tasks in one launch, the operations decided
 from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the G
-statistics of all column-splitting tasks in one launch, the k-means of all row-splitting tasks together, and one
-partition launch that writes the next generation's row-index array.  See DESIGN.md, "LearnSPN on the device".
+statistics (or, for ``rdc_cols``, the maximal correlations) of all column-splitting tasks in one launch, the k-means of
+all row-splitting tasks together, and one partition launch that writes the next generation's row-index array.  See DESIGN.md, "LearnSPN on the device".
 """
 from collections import deque
 from typing import List, Optional, Union
@@ -65,6 +65,23 @@ def check_random_state(random_state):
     raise ValueError("The random state must be either None, a seed integer or a Numpy RandomState")
 
 
+def check_discrete(distributions, domains, who='learn_spn'):
+    """Every distribution is Bernoulli or Categorical and every domain ``list(range(K))`` with ``K <= DPL_MAX_K``."""
+    from deeprob.hip import learn as L
+    for dist in distributions:
+        if getattr(dist, 'LEAF_TYPE', None) != LeafType.DISCRETE or dist not in (Bernoulli, Categorical):
+            raise NotImplementedError("{} leaves are not built by {} on the HIP path (built: Bernoulli, Categorical)"
+                                      .format(getattr(dist, '__name__', dist), who))
+    for i, (dist, dom) in enumerate(zip(distributions, domains)):
+        if not isinstance(dom, list) or len(dom) == 0 or [int(v) for v in dom] != list(range(len(dom))) \
+                or any(v != int(v) for v in dom):
+            raise ValueError("The domain of variable {} must be list(range(K)), got {}".format(i, dom))
+        if len(dom) > L.DPL_MAX_K:
+            raise ValueError("The domain of variable {} has {} values, at most {} are built".format(i, len(dom), L.DPL_MAX_K))
+        if dist is Bernoulli and list(dom) != [0, 1]:
+            raise ValueError("The domain of the Bernoulli variable {} must be [0, 1], got {}".format(i, dom))
+
+
 def check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs, split_rows_kwargs,
                     split_cols_kwargs, min_rows_slice, min_cols_slice):
     """The argument checks of ``learn_spn`` in the reference's order (learnspn.py:80-96), then what this path does not
@@ -84,27 +101,24 @@ def check_arguments(data, distributions, domains, learn_leaf, split_rows, split_
         raise ValueError("Each data column should correspond to a random variable having a distribution and a domain")
     _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
     _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
-    _method(split_cols, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
+    from deeprob.spn.learning.splitting.rdc import rdc_cols, check_parameters, D_DEFAULT, K_DEFAULT, S_DEFAULT
+    rdc = split_cols is rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
+    if not rdc:
+        _method(split_cols, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
     leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
     rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
-    cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
+    if rdc:
+        cols_kw = _kwargs(split_cols_kwargs, {'d': D_DEFAULT, 'k': K_DEFAULT, 's': S_DEFAULT}, 'rdc_cols')
+    else:
+        cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
     if leaf_kw['alpha'] < 0.0:
         raise ValueError("The Laplace smoothing factor must be non-negative")
     from deeprob.hip import learn as L
     if split_rows == 'kmeans' and not 1 <= int(rows_kw['n']) <= L.DPL_MAX_CLUSTERS:
         raise ValueError("k-means on the HIP path takes 1..{} clusters".format(L.DPL_MAX_CLUSTERS))
-    for dist in distributions:
-        if getattr(dist, 'LEAF_TYPE', None) != LeafType.DISCRETE or dist not in (Bernoulli, Categorical):
-            raise NotImplementedError("{} leaves are not built by learn_spn on the HIP path (built: Bernoulli, Categorical)"
-                                      .format(getattr(dist, '__name__', dist)))
-    for i, (dist, dom) in enumerate(zip(distributions, domains)):
-        if not isinstance(dom, list) or len(dom) == 0 or [int(v) for v in dom] != list(range(len(dom))) \
-                or any(v != int(v) for v in dom):
-            raise ValueError("The domain of variable {} must be list(range(K)), got {}".format(i, dom))
-        if len(dom) > L.DPL_MAX_K:
-            raise ValueError("The domain of variable {} has {} values, at most {} are built".format(i, len(dom), L.DPL_MAX_K))
-        if dist is Bernoulli and list(dom) != [0, 1]:
-            raise ValueError("The domain of the Bernoulli variable {} must be [0, 1], got {}".format(i, dom))
+    check_discrete(distributions, domains)
+    if rdc:
+        check_parameters([len(dom) for dom in domains], **cols_kw)
     return leaf_kw, rows_kw, cols_kw
 
 
@@ -241,20 +255,22 @@ def learn_spn(
 
     Built: discrete data with ``Bernoulli`` (domain ``[0, 1]``) and ``Categorical`` leaves, every domain
     ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``; ``split_rows`` in ``'kmeans'``, ``'random'``;
-    ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``.  Every other name the reference knows, custom callables and
-    continuous distributions raise ``NotImplementedError`` before any device work -- so does the default
-    ``split_cols='rdc'``: pass ``split_cols='gvs'``.  ``'kmeans'`` is this project's own k-means, not
-    scikit-learn's: the same kind of split, not the same labels.
+    ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``, or the function
+    ``deeprob.spn.learning.splitting.rdc.rdc_cols`` itself (recognised by identity): the RDC split as the exact maximal
+    correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``.  Every other name the reference knows, every other
+    callable and continuous distributions raise ``NotImplementedError`` before any device work -- so does the STRING
+    ``'rdc'``, the default: pass ``split_cols=rdc_cols`` or ``split_cols='gvs'``.  ``'kmeans'`` is this project's own
+    k-means, not scikit-learn's: the same kind of split, not the same labels.
 
     :param data: The training data: a numpy array or a tensor on a HIP device, complete (no NaN).
     :param distributions: A list of distribution classes of ``deeprob.spn.structure.leaf`` (one for each feature).
     :param domains: A list of domains (one for each feature), each ``list(range(K))``.
     :param learn_leaf: The method to use to learn a distribution leaf node: 'mle'.
     :param split_rows: The rows splitting method: 'kmeans' or 'random'.
-    :param split_cols: The columns splitting method: 'gvs', 'rgvs' or 'random'.
+    :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random' or the function ``rdc_cols``.
     :param learn_leaf_kwargs: The parameters of the learn leaf method (``alpha``).
     :param split_rows_kwargs: The parameters of the rows splitting method (``n`` | ``a``, ``b``).
-    :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b``).
+    :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b`` | ``d``, ``k``, ``s``).
     :param min_rows_slice: The minimum number of samples required to split horizontally.
     :param min_cols_slice: The minimum number of features required to split vertically.
     :param random_state: The random state. It can be either None, a seed integer or a Numpy RandomState.
@@ -270,6 +286,9 @@ def learn_spn(
     random_state = check_random_state(random_state)
     import torch
     from deeprob.hip import learn as L
+    from deeprob.spn.learning.splitting import rdc as R
+    if split_cols is R.rdc_cols:
+        split_cols = 'rdc'
     L.load_library()
     ks_all = [len(d) for d in domains]
     dev_data = _to_device(data, ks_all)
@@ -322,6 +341,9 @@ def learn_spn(
             elif t.op == 'cols' and split_cols == 'random':
                 p = random_state.beta(cols_kw['a'], cols_kw['b'])
                 t.draw = random_state.binomial(1, p, size=nf)
+            elif t.op == 'cols' and split_cols == 'rdc':
+                R.consume_draws(random_state, [ks_all[s] for s in t.scope], int(cols_kw['k']))      # rdc.py:170-176
+                t.draw = (np.arange(nf), None, None)
             elif t.op == 'cols':
                 k = int(max(np.sqrt(nf), 2))
                 if split_cols == 'gvs' or k == nf:
@@ -330,8 +352,9 @@ def learn_spn(
                     perm = random_state.permutation(np.arange(nf))[:k]
                     start = random_state.randint(0, k)
                     t.draw = (perm, start, random_state.rand())
-        # ---- G statistics of every gvs / rgvs task --------------------------------------------------------------------
+        # ---- G statistics of every gvs / rgvs task, or maximal correlations of every rdc task -------------------------
         gvs_tasks = [t for t in generation if t.op == 'cols' and split_cols != 'random']
+        pair_stat = L.pair_maxcorr if split_cols == 'rdc' else L.pair_g
         pc = {k: [] for k in ('ci', 'cj', 'off', 'n', 'ki', 'kj')}
         for t in gvs_tasks:
             sub = [t.scope[i] for i in t.draw[0]]
@@ -343,7 +366,7 @@ def learn_spn(
                     pc['n'].append(t.n)
                     pc['ki'].append(ks_all[sub[a]])
                     pc['kj'].append(ks_all[sub[b]])
-        g_all = L.read(L.pair_g(dev_data, row_index, pc['ci'], pc['cj'], pc['off'], pc['n'], pc['ki'], pc['kj'])) \
+        g_all = L.read(pair_stat(dev_data, row_index, pc['ci'], pc['cj'], pc['off'], pc['n'], pc['ki'], pc['kj'])) \
             if pc['ci'] else np.zeros(0)
         # ---- k-means of every row-splitting task ----------------------------------------------------------------------
         km_tasks = [t for t in generation if t.op == 'rows' and split_rows == 'kmeans']
@@ -411,17 +434,23 @@ def learn_spn(
                     q = 0
                     for a in range(k):
                         for b in range(a + 1, k):
-                            dof = (ks_all[scope[sub[a]]] - 1) * (ks_all[scope[sub[b]]] - 1)
-                            dependent = not (g[q] < 2.0 * dof * cols_kw['p'])         # gvs.py:203-205, :42
+                            if split_cols == 'rdc':
+                                dependent = bool(g[q] > cols_kw['d'])                     # rdc.py:43
+                            else:
+                                dof = (ks_all[scope[sub[a]]] - 1) * (ks_all[scope[sub[b]]] - 1)
+                                dependent = not (g[q] < 2.0 * dof * cols_kw['p'])         # gvs.py:203-205, :42
                             adjacent[a, b] = adjacent[b, a] = dependent
                             q += 1
-                    part = np.zeros(k, np.int64)
-                    part[list(component(adjacent, int(start)))] = 1
-                    if coin is None:
-                        clusters = part
+                    if split_cols == 'rdc':
+                        clusters = R.components(adjacent)                                 # rdc.py:46-48
                     else:
-                        clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
-                        clusters[sub] = part
+                        part = np.zeros(k, np.int64)
+                        part[list(component(adjacent, int(start)))] = 1
+                        if coin is None:
+                            clusters = part
+                        else:
+                            clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
+                            clusters[sub] = part
                 present = np.unique(clusters)
                 if len(present) == 1:
                     child(_Task(t.parent, t.n, scope, no_cols_split=True, no_rows_split=False), t)

@@ -4,8 +4,8 @@
  *
  * The reference is Python on numpy (deeprob/spn/learning/learnspn.py:121-222); the statistics it
  * gathers per task -- column histograms (leaf.py:162, 263; learnspn.py:132), the joint histograms
- * of the G-test (splitting/gvs.py:178-208) and the clustering of rows (splitting/cluster.py:41-65)
- * -- are what the entry points below compute, for ALL tasks of one generation of the task queue in
+ * of the G-test (splitting/gvs.py:178-208) and of the RDC score (splitting/rdc.py:85-134, here as the
+ * exact maximal correlation) and the clustering of rows (splitting/cluster.py:41-65) -- are what the entry points below compute, for ALL tasks of one generation of the task queue in
  * one launch each.  The task loop itself, every random draw and the graph stay on the host
  * (deeprob/spn/learning/learnspn.py of this package).
  *
@@ -69,6 +69,32 @@ int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_
 int dpl_pair_g(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
                const int32_t *pair_col_i, const int32_t *pair_col_j, const int64_t *pair_row_off, const int32_t *pair_n,
                const int32_t *pair_ki, const int32_t *pair_kj, int64_t n_pairs, double *g, void *stream);
+
+/* Maximal correlation (the exact value of the RDC score of two discrete columns, rdc.py:85-134: the
+ * largest canonical correlation of the two indicator spaces; the reference's random projections
+ * cancel out of it).  The pair tables are those of dpl_pair_g.  For pair q, in this order:
+ *   1. c[a][b]: the joint counts over the pair's row segment, exact int32 (as for dpl_pair_g);
+ *   2. r[a] = c[a][0] + c[a][1] + ..., s[b] = c[0][b] + c[1][b] + ..., n' = r[0] + r[1] + ..., integers
+ *      (n' is the number of counted rows);
+ *   3. the PRESENT values: the a with r[a] > 0 and the b with s[b] > 0, each in increasing order;
+ *   4. fewer than two present values on either side: score = 0.0;
+ *   5. a 2 x 2 present table: score = min(1, |c00 c11 - c01 c10| / sqrt(f64(r0 r1) * f64(s0 s1))), the
+ *      determinant and the two products exact in int64;
+ *   6. otherwise, over present values, M[a][b] = f64(c[a][b] n' - r[a] s[b]) / (f64(n') * sqrt(f64(r[a]
+ *      s[b]))), numerator and r[a] s[b] exact in int64.  The VECTORS are the rows of M when it has no
+ *      more rows than columns, else its columns: p vectors of length len, p <= len.  One-sided
+ *      (Hestenes) Jacobi on them, never on M M^T: sweeps over the pairs (i, j), i = 0 .. p - 2,
+ *      j = i + 1 .. p - 1, in that order; for a pair alpha = w_i.w_i, beta = w_j.w_j, gamma = w_i.w_j,
+ *      each summed from 0.0 over e = 0 .. len - 1 in order (one multiply, one add per term); the pair
+ *      is rotated when |gamma| > 2^-48 * sqrt(alpha * beta), with zeta = (beta - alpha) / (2 gamma),
+ *      t = sign(zeta) / (|zeta| + sqrt(1 + zeta * zeta)) (sign(0) = +1), c = 1 / sqrt(1 + t * t),
+ *      s = c * t, w_i' = c * w_i - s * w_j, w_j' = s * w_i + c * w_j.  The sweeps stop after the first
+ *      one that rotates no pair, or after 30;
+ *   7. score = min(1, sqrt(the largest w_v.w_v)), the norms summed as in 6, v in order.
+ * score: [n_pairs] float64, every element written (0 <= score <= 1). */
+int dpl_pair_maxcorr(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                     const int32_t *pair_col_i, const int32_t *pair_col_j, const int64_t *pair_row_off, const int32_t *pair_n,
+                     const int32_t *pair_ki, const int32_t *pair_kj, int64_t n_pairs, double *score, void *stream);
 
 /* The next generation's row-index array.  Child c copies, in order, the rows of the source segment
  * [child_src_off[c], + child_src_n[c]) of `row_index` whose label equals child_label[c] -- the label
