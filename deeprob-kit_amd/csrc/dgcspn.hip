@@ -433,8 +433,8 @@ __global__ void spatial_sum_bwd_kernel(const float *__restrict__ x, const float 
 
 // Cin, Cout <= 8 (the DGC-SPN defaults): thread = pixel x half of the input channels x slice of samples, with the
 // pixel's 8 x 4 linear weights and the batch sums of glw in registers.  pi[o,c] = W[o,c] e^{x_c - m} e^{m - out_o}
-// with m = max_c x_c: 12 exponentials per thread and sample instead of 32, gx written once.  m - out_o is bounded
-// by -log(max_c W[o,c]); an output whose bound leaves the fp32 range takes the exact log-domain expression.
+// with m = max_c x_c: 12 exponentials per thread and sample instead of 32, gx written once.  m - out_o is at most
+// -log W[o, argmax_c x_c]; an output for which it reaches 64 takes the exact log-domain expression.
 // TAPS: the sum layer's input is the depthwise product of the map `x` [B,Cin,q.H,q.W] (dpk_spatial_prodsum_backward:
 // the product map of the training forward is never stored); x_c is then the sum of the pixel's taps, gx the gradient
 // of that product map.
@@ -530,7 +530,9 @@ __global__ __launch_bounds__(256) void spatial_sum_bwd8_kernel(const float *__re
             const float xo = xo8[o], gv = g8[o];
             if (!(xo > -INFINITY)) continue;   // also the padding outputs o >= Cout
             const float d = mm - xo;
-            if (d < 80.f) {
+            // __expf returns 0 below the normal range: e^{x_c - m} is lost from x_c - m = -87.3 down, and with it a term of
+            // up to e^{d - 87.3}.  Up to d = 64 that is under 1e-10 of g; with the switch at 80 it was 7e-4
+            if (d < 64.f) {
                 const float eo = gv * __expf(d);
 #pragma unroll
                 for (int q = 0; q < kSp8C; ++q) {

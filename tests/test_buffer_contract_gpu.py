@@ -70,6 +70,8 @@ REPLAY = [
     ('test_dgcspn_gpu', 'test_fused_leaf_and_first_level_against_oracle', {'#': {0}}),
     ('test_dgcspn_gpu', 'test_fused_level_autograd_matches_layer_chain', {'#': {0, 1}}),
     ('test_dgcspn_gpu', 'test_sum_backward_extreme_weights_against_oracle', dict(cin=6)),
+    ('test_dgcspn_backward_gpu', 'test_generic_sum_backward_blocks_and_dispatch', dict(cin={16, 12}, cout={32, 17})),
+    ('test_dgcspn_backward_gpu', 'test_fused_level_autograd_against_fp64', {'#': {0}}),
     # ---- RealNVP-1D ---------------------------------------------------------------------------------------------
     ('test_flows_gpu', 'test_log_prob_golden', {}),
     ('test_flows_gpu', 'test_layers_and_inverse_golden', {}),
