@@ -6,43 +6,28 @@
 #include <stdint.h>
 #include <stdio.h>
 #include "../../../include/deeprob_learn.h"
+#include "learn_common.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "libdeeprob_learn is written for gfx950 (MI355X)"
 #endif
 
 namespace {
-
 thread_local char g_error[512] = "";
+}
 
-void set_error(const char *fmt, ...) {
+void dpl_detail::set_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_error, sizeof(g_error), fmt, ap);
     va_end(ap);
 }
 
-#define DPL_REQUIRE(cond, ...)        \
-    do {                              \
-        if (!(cond)) {                \
-            set_error(__VA_ARGS__);   \
-            return DPL_EINVAL;        \
-        }                             \
-    } while (0)
+namespace {
 
-#define DPL_LAUNCH(what, ...)                                          \
-    do {                                                               \
-        (void)hipGetLastError();                                       \
-        hipLaunchKernelGGL(__VA_ARGS__);                               \
-        hipError_t e__ = hipGetLastError();                            \
-        if (e__ != hipSuccess) {                                       \
-            set_error("%s: %s", (what), hipGetErrorString(e__));       \
-            return DPL_ELAUNCH;                                        \
-        }                                                              \
-    } while (0)
-
-constexpr int kThreads = 256;
-constexpr int kMaxGrid = 2147483647;
+using dpl_detail::kMaxGrid;
+using dpl_detail::kThreads;
+using dpl_detail::set_error;
 constexpr double kEps32 = 1.1920928955078125e-07;   // np.finfo(np.float32).eps (gvs.py:193)
 
 // ---- column counts ---------------------------------------------------------------------------------------------------
@@ -463,7 +448,7 @@ bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
 extern "C" {
 
 const char *dpl_last_error(void) { return g_error; }
-int dpl_abi_version(void) { return 2; }
+int dpl_abi_version(void) { return 3; }
 
 int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
                       const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,

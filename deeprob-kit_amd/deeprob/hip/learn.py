@@ -76,13 +76,13 @@ def read(t: torch.Tensor, lloyd: bool = False) -> np.ndarray:
 
 
 def upload(device, **arrays):
-    """Integer host tables of one launch, packed into one int64-aligned buffer and copied in ONE transfer: a dict of
-    device views (int32 or int64, as the host arrays are)."""
+    """Host tables of one launch (int32, int64, uint8 or float32), packed into one int64-aligned buffer and copied in ONE
+    transfer: a dict of device views of the host arrays' types."""
     COUNTERS['uploads'] += 1
     parts, spans, o = [], {}, 0
     for name, a in arrays.items():
         a = np.ascontiguousarray(a)
-        if a.dtype not in (np.int32, np.int64, np.uint8):
+        if a.dtype not in (np.int32, np.int64, np.uint8, np.float32):
             raise TypeError('{}: {}'.format(name, a.dtype))
         raw = a.view(np.uint8).reshape(-1)
         pad = (-len(raw)) % 8
@@ -96,8 +96,8 @@ def upload(device, **arrays):
     out = {}
     for name, (o, n, dtype, shape) in spans.items():
         view = dev[o:o + n]
-        out[name] = view.view({np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64,
-                               np.dtype(np.uint8): torch.uint8}[np.dtype(dtype)]).reshape(shape)
+        out[name] = view.view({np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8,
+                               np.dtype(np.float32): torch.float32}[np.dtype(dtype)]).reshape(shape)
     out['_buffer'] = dev
     return out
 
@@ -243,5 +243,198 @@ class KMeansBatch:
         call(lib.dpl_kmeans_inertia, *head, p['col_off'], p['cols'], p['ks'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
              self.T, self.R, self.C, self.kmax, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(),
              sizes.data_ptr(), st)
+        COUNTERS['kernels'] += 1
+        return read(inertia), read(sizes), labels, iterations
+
+
+# ---- continuous data (the last section of the header) ---------------------------------------------------------------------
+class DeviceDataF:
+    """The training set on the device as float32, column major (see the header, "continuous data")."""
+
+    def __init__(self, x_cm: torch.Tensor, n_rows: int, n_cols: int):
+        if not x_cm.is_cuda:
+            raise HipError("data lives on '{}': the deeprob HIP path only works on a HIP device (there is no CPU "
+                           "fallback)".format(x_cm.device))
+        assert x_cm.dtype == torch.float32 and x_cm.is_contiguous() and x_cm.numel() == n_rows * n_cols
+        self.x, self.n_rows, self.n_cols, self.device = x_cm, int(n_rows), int(n_cols), x_cm.device
+
+    head = DeviceData.head
+
+
+def column_moments(data: DeviceDataF, row_index, item_col, item_row_off, item_n) -> torch.Tensor:
+    """``[n_items, 2]`` float64: mean and population variance of every item (``dpl_column_moments``)."""
+    lib = load_library()
+    n_items = len(item_col)
+    t = upload(data.device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
+               n=np.asarray(item_n, np.int32))
+    moments = torch.empty((n_items, 2), dtype=torch.float64, device=data.device)
+    call(lib.dpl_column_moments, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(), n_items,
+         moments.data_ptr(), _stream(data.device))
+    COUNTERS['kernels'] += 1
+    return moments
+
+
+def _row_blocks(ns):
+    """(item of each 256-row block, its first row) for items of ``ns`` rows."""
+    item, row0 = [], []
+    for i, n in enumerate(ns):
+        for r0 in range(0, int(n), 256):
+            item.append(i)
+            row0.append(r0)
+    return np.asarray(item, np.int32), np.asarray(row0, np.int32)
+
+
+def ecdf_ranks(data: DeviceDataF, row_index, item_col, item_row_off, item_n):
+    """``(ranks, out_off)``: the int32 "max" ranks of every item, item i at ``ranks[out_off[i] : out_off[i] + item_n[i]]``
+    in segment order (``dpl_ecdf_ranks``).  The values of all items are gathered and sorted on the device with
+    ``torch.sort`` (by value, then stably by item); no row is sorted on the host."""
+    lib = load_library()
+    n_items = len(item_col)
+    ns = np.asarray(item_n, np.int64)
+    out_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    total = int(out_off[-1])
+    block_item, block_row0 = _row_blocks(ns)
+    t = upload(data.device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
+               n=ns.astype(np.int32), out=out_off[:-1].copy(), bi=block_item, br=block_row0)
+    item_of = torch.repeat_interleave(torch.arange(n_items, device=data.device), t['n'].long(), output_size=total)
+    pos = torch.arange(total, device=data.device) - t['out'][item_of]
+    rows = row_index[t['off'][item_of] + pos].long()
+    values = data.x[t['col'][item_of].long() * data.n_rows + rows]
+    by_value, order = torch.sort(values, stable=True)
+    _, by_item = torch.sort(item_of[order], stable=True)
+    in_order = by_value[by_item].contiguous()
+    ranks = torch.empty(total, dtype=torch.int32, device=data.device)
+    call(lib.dpl_ecdf_ranks, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
+         t['out'].data_ptr(), n_items, t['bi'].data_ptr(), t['br'].data_ptr(), len(block_item), in_order.data_ptr(),
+         ranks.data_ptr(), total, _stream(data.device))
+    COUNTERS['kernels'] += 1
+    return ranks, out_off[:-1]
+
+
+#: rows of one unit of ``dpl_rdc_gram``, and the units whose partial sums fit in 256 MiB
+GRAM_ROW_CHUNK = 1024
+GRAM_MAX_UNITS = (256 << 20) // (8 * CONSTANTS['DPL_GRAM_PARTIAL'])
+#: whether the products of ``dpl_rdc_gram`` run on v_mfma_f64_16x16x4_f64 (else on the VALU): picked by measurement (DESIGN.md)
+GRAM_USE_MFMA = True
+
+
+def rdc_gram(ranks: torch.Tensor, tasks, k: int, w: np.ndarray, b: np.ndarray, row_chunk: int = GRAM_ROW_CHUNK,
+             max_units: int = GRAM_MAX_UNITS, mfma: bool = None):
+    """The column sums and raw Gram matrices of the random features of every task (``dpl_rdc_gram``).  ``tasks``: a list of
+    ``(n, m, rank_off)``: task t has its ``m`` rank arrays of ``n`` rows at ``ranks[rank_off ...]``; ``w``, ``b``: the
+    float32 draws of all tasks, ``m * k`` each, one after the other.  Returns a dict: ``G`` (device float64, task t's
+    ``[F, F]`` matrix at ``g_off[t]``), ``S`` (device float64, task t's ``[F]`` sums at ``feat_off[t]``), ``g_off``,
+    ``feat_off`` and ``partials`` (the scratch of every call).  The tile pairs are split over calls so that the partial
+    sums of one call stay under 256 MiB."""
+    lib = load_library()
+    device, tile = ranks.device, CONSTANTS['DPL_GRAM_TILE']
+    k = int(k)
+    fs = [int(m) * k for _, m, _ in tasks]
+    feat_off = np.concatenate([[0], np.cumsum(fs)]).astype(np.int64)
+    g_off = np.concatenate([[0], np.cumsum([f * f for f in fs])]).astype(np.int64)
+    w, b = np.ascontiguousarray(w, np.float32).reshape(-1), np.ascontiguousarray(b, np.float32).reshape(-1)
+    assert len(w) == len(b) == int(feat_off[-1])
+    tt = upload(device, n=np.asarray([t[0] for t in tasks], np.int32), f=np.asarray(fs, np.int32),
+                rank_off=np.asarray([t[2] for t in tasks], np.int64), feat_off=feat_off[:-1].copy(), g_off=g_off[:-1].copy(),
+                w=w, b=b)
+    G = torch.empty(int(g_off[-1]), dtype=torch.float64, device=device)
+    S = torch.empty(int(feat_off[-1]), dtype=torch.float64, device=device)
+    groups = []                 # (task, i0, j0) in task order, tile pairs i0 <= j0
+    for t, f in enumerate(fs):
+        for i0 in range(0, f, tile):
+            for j0 in range(i0, f, tile):
+                groups.append((t, i0, j0))
+    partials, g = [], 0
+    while g < len(groups):
+        unit, group, n_units = {key: [] for key in ('task', 'i0', 'j0', 'row0', 'rows')}, {'unit0': [], 'units': []}, 0
+        while g < len(groups):
+            t, i0, j0 = groups[g]
+            n = int(tasks[t][0])
+            chunks = -(-n // row_chunk)
+            if chunks > max_units:
+                raise HipError("rdc_gram: a task of {} rows needs {} partial sums per tile, over the 256 MiB of one call"
+                               .format(n, chunks))
+            if n_units + chunks > max_units:
+                break
+            group['unit0'].append(n_units)
+            group['units'].append(chunks)
+            for c in range(chunks):
+                for key, v in zip(('task', 'i0', 'j0', 'row0', 'rows'), (t, i0, j0, c * row_chunk, min(row_chunk, n - c * row_chunk))):
+                    unit[key].append(v)
+            n_units += chunks
+            g += 1
+        ut = upload(device, **{key: np.asarray(v, np.int32) for key, v in list(unit.items()) + list(group.items())})
+        partial = torch.empty(n_units * CONSTANTS['DPL_GRAM_PARTIAL'], dtype=torch.float64, device=device)
+        call(lib.dpl_rdc_gram, ranks.data_ptr(), ranks.numel(), tt['w'].data_ptr(), tt['b'].data_ptr(), len(w), k,
+             tt['n'].data_ptr(), tt['f'].data_ptr(), tt['rank_off'].data_ptr(), tt['feat_off'].data_ptr(), tt['g_off'].data_ptr(),
+             len(tasks), ut['task'].data_ptr(), ut['i0'].data_ptr(), ut['j0'].data_ptr(), ut['row0'].data_ptr(),
+             ut['rows'].data_ptr(), n_units, ut['unit0'].data_ptr(), ut['units'].data_ptr(), len(group['units']),
+             int(GRAM_USE_MFMA if mfma is None else mfma), partial.data_ptr(), G.data_ptr(), G.numel(), S.data_ptr(), _stream(device))
+        COUNTERS['kernels'] += 2
+        partials.append(partial)
+    return {'G': G, 'S': S, 'g_off': g_off[:-1], 'feat_off': feat_off[:-1], 'fs': fs, 'partials': partials}
+
+
+class KMeansBatchF:
+    """The k-means of all row-splitting tasks of one generation on float columns (header: "k-means on float columns").
+    ``tasks``: a list of ``(row_off, n, cols, seeds)`` with ``seeds`` an ``[n_restarts, n_clusters]`` array of row positions."""
+
+    MAX_ITER = KMeansBatch.MAX_ITER
+
+    def __init__(self, data: DeviceDataF, row_index, tasks, n_restarts: int, n_clusters: int):
+        self.data, self.row_index, self.R, self.C = data, row_index, n_restarts, n_clusters
+        self.T = len(tasks)
+        col_off, cols, cent_off, lab_off = [0], [], [], []
+        n_cent = n_lab = 0
+        item_task, item_p = [], []
+        for t, (row_off, n, tcols, seeds) in enumerate(tasks):
+            cols += list(tcols)
+            col_off.append(len(cols))
+            cent_off.append(n_cent)
+            lab_off.append(n_lab)
+            n_cent += n_restarts * n_clusters * len(tcols)
+            n_lab += n
+            item_task += [t] * len(tcols)
+            item_p += list(range(len(tcols)))
+        self.n_cent, self.n_lab, self.lab_off, self.cent_off = n_cent, n_lab, lab_off, cent_off
+        block_task, block_row0 = _row_blocks([t[1] for t in tasks])
+        self.n_blocks, self.n_items = len(block_task), len(item_task)
+        self.tab = upload(
+            data.device, col_off=np.asarray(col_off, np.int32), cols=np.asarray(cols, np.int32),
+            row_off=np.asarray([t[0] for t in tasks], np.int64), n=np.asarray([t[1] for t in tasks], np.int32),
+            cent_off=np.asarray(cent_off, np.int64), lab_off=np.asarray(lab_off, np.int64),
+            seeds=np.concatenate([np.asarray(t[3], np.int32).reshape(-1) for t in tasks]),
+            block_task=block_task, block_row0=block_row0,
+            item_task=np.asarray(item_task, np.int32), item_p=np.asarray(item_p, np.int32))
+
+    def run(self):
+        """``(inertia [T, R] float64, sizes [T, R, C] int32, labels [R, n_lab] device uint8, iterations)``; the centroids
+        stay in ``self.cent``."""
+        lib, d, p = load_library(), self.data, {k: v.data_ptr() for k, v in self.tab.items()}
+        dev, st = d.device, _stream(d.device)
+        head = d.head(self.row_index)
+        cent = self.cent = torch.empty(self.n_cent, dtype=torch.float64, device=dev)
+        labels = torch.empty((self.R, self.n_lab), dtype=torch.uint8, device=dev)
+        changed = torch.zeros(self.MAX_ITER, dtype=torch.int32, device=dev)
+        COUNTERS['kernels'] += 1        # (the fill of `changed`)
+        call(lib.dpl_kmeansf_init, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['seeds'], self.T,
+             self.R, self.C, cent.data_ptr(), self.n_cent, st)
+        COUNTERS['kernels'] += 1
+        iterations = 0
+        for it in range(self.MAX_ITER):
+            call(lib.dpl_kmeansf_assign, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
+                 p['block_task'], p['block_row0'], self.n_blocks, self.R, self.C, cent.data_ptr(), labels.data_ptr(),
+                 self.n_lab, 1 if it == 0 else 0, changed[it:].data_ptr(), st)
+            COUNTERS['lloyd_kernels'] += 1
+            iterations = it + 1
+            if int(read(changed[it:it + 1], lloyd=True)[0]) == 0 or it == self.MAX_ITER - 1:
+                break
+            call(lib.dpl_kmeansf_update, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
+                 p['item_task'], p['item_p'], self.n_items, self.R, self.C, labels.data_ptr(), self.n_lab, cent.data_ptr(), st)
+            COUNTERS['lloyd_kernels'] += 1
+        inertia = torch.empty((self.T, self.R), dtype=torch.float64, device=dev)
+        sizes = torch.empty((self.T, self.R, self.C), dtype=torch.int32, device=dev)
+        call(lib.dpl_kmeansf_inertia, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
+             self.T, self.R, self.C, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(), sizes.data_ptr(), st)
         COUNTERS['kernels'] += 1
         return read(inertia), read(sizes), labels, iterations

@@ -257,14 +257,18 @@ def learn_spn(
     ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``; ``split_rows`` in ``'kmeans'``, ``'random'``;
     ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``, or the function
     ``deeprob.spn.learning.splitting.rdc.rdc_cols`` itself (recognised by identity): the RDC split as the exact maximal
-    correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``.  Every other name the reference knows, every other
-    callable and continuous distributions raise ``NotImplementedError`` before any device work -- so does the STRING
-    ``'rdc'``, the default: pass ``split_cols=rdc_cols`` or ``split_cols='gvs'``.  ``'kmeans'`` is this project's own
-    k-means, not scikit-learn's: the same kind of split, not the same labels.
+    correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``.  Also built: all-continuous data, every distribution
+    ``Gaussian`` and every domain a tuple ``(lo, hi)`` (learnspn_cont.py): ``split_rows`` in ``'kmeans'``, ``'random'``,
+    ``split_cols`` ``'random'`` or the function ``rdc_cols`` (there a ridge-regularised score of its own, see
+    splitting/rdc.py), MLE Gaussian leaves; ``'gvs'`` / ``'rgvs'`` raise there (a G-test needs a table).  Every other
+    name the reference knows, every other callable, ``Uniform`` and mixed discrete / continuous data raise
+    ``NotImplementedError`` before any device work -- so does the STRING ``'rdc'``, the default: pass
+    ``split_cols=rdc_cols`` or ``split_cols='gvs'``.  ``'kmeans'`` is this project's own k-means, not
+    scikit-learn's: the same kind of split, not the same labels.
 
     :param data: The training data: a numpy array or a tensor on a HIP device, complete (no NaN).
     :param distributions: A list of distribution classes of ``deeprob.spn.structure.leaf`` (one for each feature).
-    :param domains: A list of domains (one for each feature), each ``list(range(K))``.
+    :param domains: A list of domains (one for each feature), each ``list(range(K))`` (``(lo, hi)`` for ``Gaussian``).
     :param learn_leaf: The method to use to learn a distribution leaf node: 'mle'.
     :param split_rows: The rows splitting method: 'kmeans' or 'random'.
     :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random' or the function ``rdc_cols``.
@@ -280,6 +284,11 @@ def learn_spn(
     :raises NotImplementedError: For what the reference knows and this path does not build.
     :raises HipError: If the data is a CPU tensor or the native library is missing.
     """
+    from deeprob.spn.learning.splitting.rdc import all_gaussian
+    if all_gaussian(distributions):         # all-continuous data: a path of its own (learnspn_cont.py)
+        from deeprob.spn.learning.learnspn_cont import learn_spn_cont
+        return learn_spn_cont(data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs,
+                              split_rows_kwargs, split_cols_kwargs, min_rows_slice, min_cols_slice, random_state, verbose)
     leaf_kw, rows_kw, cols_kw = check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols,
                                                 learn_leaf_kwargs, split_rows_kwargs, split_cols_kwargs, min_rows_slice,
                                                 min_cols_slice)

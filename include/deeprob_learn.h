@@ -1,6 +1,7 @@
 /*
  * deeprob_learn.h -- C ABI of libdeeprob_learn.so (gfx950 / MI355X): the device side of LearnSPN
- * (deeprob.spn.learning.learnspn.learn_spn) for discrete data.
+ * (deeprob.spn.learning.learnspn.learn_spn) for discrete data and, in its last section, for continuous
+ * (all-Gaussian) data.
  *
  * The reference is Python on numpy (deeprob/spn/learning/learnspn.py:121-222); the statistics it
  * gathers per task -- column histograms (leaf.py:162, 263; learnspn.py:132), the joint histograms
@@ -24,7 +25,7 @@
  *      tails included);
  *   3. nothing it does depends on what the outputs held on entry, except the arguments documented
  *      as updated in place: `labels` and `changed` of dpl_kmeans_assign, `cent` of
- *      dpl_kmeans_update;
+ *      dpl_kmeans_update, and the same three of the dpl_kmeansf_ entries;
  *   4. it leaves its `const` inputs alone.
  * There is no workspace.  Index arrays handed in are trusted to lie inside the arrays they index,
  * a value x >= the K stated for its column is not counted.  Counts are exact integers (LDS integer
@@ -153,6 +154,101 @@ int dpl_kmeans_inertia(const uint8_t *x, int64_t n_rows, int n_cols, const int32
                        const int64_t *task_lab_off, int n_tasks, int n_restarts, int n_clusters, int kmax,
                        const double *cent, const uint8_t *labels, int64_t n_lab, double *inertia, int32_t *sizes,
                        void *stream);
+
+/* ==== continuous data (deeprob.spn.learning.learnspn_cont: all-Gaussian learn_spn) =================
+ * `xf` is the training set as float32, COLUMN MAJOR: xf[col * n_rows + row]; `row_index`, segments and
+ * the buffer contract are those above.  No float atomics; every float64 sum below has the stated order;
+ * a run repeats bit for bit.  Scratch (`partial` of dpl_rdc_gram) is an output like any other: every
+ * element of it is written, and what it holds on return is not specified further. */
+
+/* Moments: for item i (column item_col[i] over its segment of n = item_n[i] rows), in float64 and two
+ * passes: 256 partial sums (partial l takes rows l, l + 256, ... in order, from 0.0), added in order
+ * of l, divided by n: the mean; then the same sum of (x - mean) * (x - mean), divided by n: the
+ * POPULATION variance.  moments: [n_items * 2] float64, mean at 2 i, variance at 2 i + 1.
+ * The host rules: a column with variance <= 1e-8 is constant (np.isclose(var, 0), learnspn.py:132);
+ * the leaf is Gaussian(mean, max(sqrt(variance), 1e-5)) (leaf.py:529-530). */
+int dpl_column_moments(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                       const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,
+                       double *moments, void *stream);
+
+/* ECDF ranks (utils/data.py:182, scipy.stats.rankdata(method='max')): for item i and position r of its
+ * segment, ranks[item_out_off[i] + r] = number of rows of the segment whose value is <= the value of
+ * row r.  `sorted` holds, at [item_out_off[i], + item_n[i]), the item's values in non-decreasing order
+ * (the caller sorts them on the device); the rank is the upper bound of the row's value in that run, so
+ * a run of ties gets the position of its last member ("max").  Block b covers positions block_row0[b]
+ * .. + 256 of item block_item[b].  ranks: [n_out] int32, n_out = the sum of item_n, every element
+ * written (1 <= rank <= n). */
+int dpl_ecdf_ranks(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                   const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n,
+                   const int64_t *item_out_off, int64_t n_items, const int32_t *block_item, const int32_t *block_row0,
+                   int64_t n_blocks, const float *sorted, int32_t *ranks, int64_t n_out, void *stream);
+
+/* Random-feature Gram matrices of the continuous RDC score (rdc.py:137-177).  Task t has n = task_n[t]
+ * rows and F = task_f[t] = m * k features, k per column; the ranks of its p-th column are at
+ * ranks[task_rank_off[t] + p * n ...] (dpl_ecdf_ranks order), its draws at w[task_feat_off[t] + f],
+ * b[same], f = p * k + j (float32, widened).  In float64, one operation at a time:
+ *   u = f64(rank) / f64(n);   phi[r][f] = sin(u * w[f] + b[f]);
+ *   S[f] = sum_r phi[r][f];   G[f][g] = sum_r phi[r][f] * phi[r][g].
+ * phi is never stored: UNIT u forms it for rows [unit_row0[u], + unit_rows[u]) of task unit_task[u] and
+ * the two 32-feature tiles that start at unit_i0[u] <= unit_j0[u], 32 rows at a time in LDS, and adds
+ * the products into partial[u * DPL_GRAM_PARTIAL ...]: 32 x 32 products (row major) and then 32 column
+ * sums of the tile at unit_i0 (features >= F and rows past the unit count as 0).  With use_mfma == 0 the
+ * products are added on the VALU row by row in increasing row order; with use_mfma != 0 on
+ * v_mfma_f64_16x16x4_f64, blocks of 4 rows in increasing order, the 4 rows of a block in the matrix
+ * core's own (fixed) order.  The column sums are added row by row in both.  GROUP g -- one tile pair of one task -- adds the partials of its units
+ * group_unit0[g] .. + group_units[g] in that order (the caller lists a group's units by increasing
+ * row) and writes G[task_g_off[t] + f * F + g'] for the tile and, when the two tiles differ, its
+ * mirror image; the group with unit_i0 == unit_j0 also writes S[task_feat_off[t] + f].  The caller
+ * lists every tile pair i0 <= j0 of every task, so every element of G and S is written (products
+ * commute exactly, so G is bitwise symmetric).  partial: [n_units * DPL_GRAM_PARTIAL] float64; the
+ * caller keeps n_units * DPL_GRAM_PARTIAL * 8 bytes under 256 MiB by splitting the groups of a
+ * generation, or of one wide task, over several calls.  Which of the two forms the package uses was
+ * picked by measurement ("rdc on continuous columns"). */
+#define DPL_GRAM_TILE 32
+#define DPL_GRAM_PARTIAL 1056 /* 32 * 32 + 32 */
+int dpl_rdc_gram(const int32_t *ranks, int64_t n_ranks, const float *w, const float *b, int64_t n_feat, int k,
+                 const int32_t *task_n, const int32_t *task_f, const int64_t *task_rank_off,
+                 const int64_t *task_feat_off, const int64_t *task_g_off, int n_tasks, const int32_t *unit_task,
+                 const int32_t *unit_i0, const int32_t *unit_j0, const int32_t *unit_row0, const int32_t *unit_rows,
+                 int64_t n_units, const int32_t *group_unit0, const int32_t *group_units, int64_t n_groups,
+                 int use_mfma, double *partial, double *G, int64_t n_g, double *S, void *stream);
+
+/* ---- k-means on float columns: the four entries above restated.  A column is ONE feature, unscaled
+ * (cluster.py:58-65); centroids at cent[task_cent_off[t] + (r * n_clusters + c) * ncols_t + p]; the
+ * squared distance (f64(x) - cent)^2 accumulates in float64 over the columns in order, ties to the
+ * lower index; restarts, steps and the winner are DESIGN.md's. */
+
+/* cent = the row at position seeds[(t * n_restarts + r) * n_clusters + c] of task t's segment. */
+int dpl_kmeansf_init(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                     const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                     const int32_t *task_n, const int64_t *task_cent_off, const int32_t *seeds, int n_tasks,
+                     int n_restarts, int n_clusters, double *cent, int64_t n_cent, void *stream);
+
+/* As dpl_kmeans_assign (`labels` and `changed` updated in place). */
+int dpl_kmeansf_assign(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                       const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                       const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off,
+                       const int32_t *block_task, const int32_t *block_row0, int64_t n_blocks, int n_restarts,
+                       int n_clusters, const double *cent, uint8_t *labels, int64_t n_lab, int first,
+                       int32_t *changed, void *stream);
+
+/* Centroids from labels (`cent` updated in place): item i is column position item_p[i] of task
+ * item_task[i]; per restart and cluster c the mean of the column over the rows labelled c: 256
+ * partial sums (partial l takes, in order, the rows among l, l + 256, ... that are labelled c, from
+ * 0.0), added in order of l, divided by the number of such rows; a cluster without rows keeps its
+ * centroid. */
+int dpl_kmeansf_update(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                       const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                       const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off,
+                       const int32_t *item_task, const int32_t *item_p, int64_t n_items, int n_restarts,
+                       int n_clusters, const uint8_t *labels, int64_t n_lab, double *cent, void *stream);
+
+/* As dpl_kmeans_inertia: the same 256 partial sums, and the cluster sizes. */
+int dpl_kmeansf_inertia(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                        const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
+                        const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off, int n_tasks,
+                        int n_restarts, int n_clusters, const double *cent, const uint8_t *labels, int64_t n_lab,
+                        double *inertia, int32_t *sizes, void *stream);
 
 #ifdef __cplusplus
 }
