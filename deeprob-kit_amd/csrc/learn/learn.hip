@@ -25,6 +25,7 @@ void dpl_detail::set_error(const char *fmt, ...) {
 
 namespace {
 
+using dpl_detail::common_ok;
 using dpl_detail::kMaxGrid;
 using dpl_detail::kThreads;
 using dpl_detail::set_error;
@@ -303,55 +304,35 @@ __global__ __launch_bounds__(kThreads) void kmeans_init_kernel(
     }
 }
 
-// squared distance of a row to one centroid: columns in order, values in order, one multiply and one add per feature
-__device__ __forceinline__ double sq_dist(const uint8_t *__restrict__ x, int64_t n_rows, int row,
-                                          const int32_t *__restrict__ cols, const int32_t *__restrict__ ks, int ncols,
-                                          int kmax, const double *__restrict__ cen) {
-    double d = 0.0;
-    for (int p = 0; p < ncols; ++p) {
-        const int v = x[(int64_t)cols[p] * n_rows + row], K = ks[p];
-        const double *f = cen + (int64_t)p * kmax;
-        if (K <= 2) {
-            const double u = (double)v - f[1];      // (kmax >= 2)
-            d += u * u;
-        } else {
-            for (int k = 0; k < K; ++k) {
-                const double u = ((v == k) ? 1.0 : 0.0) - f[k];
+// One-hot columns, the policy of the shared k-means kernels (learn_common.h): a centroid holds kmax value frequencies per
+// column; col_k is the domain size of every column of the generation's column table.
+struct OneHotColumns {
+    using value = uint8_t;
+    const int32_t *__restrict__ col_k;
+    int kmax;
+    __device__ int stride() const { return kmax; }
+    // squared distance of a row to one centroid: columns in order, values in order, one multiply and one add per feature
+    __device__ __forceinline__ double sq_dist(const uint8_t *__restrict__ x, int64_t n_rows, int row,
+                                              const int32_t *__restrict__ cols, int c0, int ncols,
+                                              const double *__restrict__ cen) const {
+        const int32_t *ks = col_k + c0;
+        double d = 0.0;
+        for (int p = 0; p < ncols; ++p) {
+            const int v = x[(int64_t)cols[p] * n_rows + row], K = ks[p];
+            const double *f = cen + (int64_t)p * kmax;
+            if (K <= 2) {
+                const double u = (double)v - f[1];      // (kmax >= 2)
                 d += u * u;
+            } else {
+                for (int k = 0; k < K; ++k) {
+                    const double u = ((v == k) ? 1.0 : 0.0) - f[k];
+                    d += u * u;
+                }
             }
         }
+        return d;
     }
-    return d;
-}
-
-__global__ __launch_bounds__(kThreads) void kmeans_assign_kernel(
-    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
-    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int32_t *__restrict__ col_k,
-    const int64_t *__restrict__ task_row_off, const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off,
-    const int64_t *__restrict__ task_lab_off, const int32_t *__restrict__ block_task, const int32_t *__restrict__ block_row0,
-    int n_clusters, int kmax, const double *__restrict__ cent, uint8_t *__restrict__ labels, int64_t n_lab, int first,
-    int32_t *__restrict__ changed) {
-    const int t = block_task[blockIdx.x], rs = blockIdx.y;
-    const int i = block_row0[blockIdx.x] + threadIdx.x;
-    if (i >= task_n[t]) return;
-    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0;
-    const int row = row_index[task_row_off[t] + i];
-    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols * kmax;
-    double best = 0.0;
-    int arg = 0;
-    for (int c = 0; c < n_clusters; ++c) {
-        const double d = sq_dist(x, n_rows, row, col_index + c0, col_k + c0, ncols, kmax, cen + (int64_t)c * ncols * kmax);
-        if (c == 0 || d < best) {
-            best = d;
-            arg = c;
-        }
-    }
-    uint8_t *slot = labels + (int64_t)rs * n_lab + task_lab_off[t] + i;
-    if (first || *slot != (uint8_t)arg) {
-        *slot = (uint8_t)arg;
-        *changed = 1;       // (every writer stores the same value)
-    }
-}
+};
 
 __global__ __launch_bounds__(kThreads) void kmeans_update_kernel(
     const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
@@ -380,57 +361,6 @@ __global__ __launch_bounds__(kThreads) void kmeans_update_kernel(
         if (size > 0)
             cent[task_cent_off[t] + (((int64_t)rs * n_clusters + c) * ncols + p) * kmax + k] = (double)cnt[e] / (double)size;
     }
-}
-
-__global__ __launch_bounds__(kThreads) void kmeans_inertia_kernel(
-    const uint8_t *__restrict__ x, int64_t n_rows, const int32_t *__restrict__ row_index,
-    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int32_t *__restrict__ col_k,
-    const int64_t *__restrict__ task_row_off, const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off,
-    const int64_t *__restrict__ task_lab_off, int n_restarts, int n_clusters, int kmax, const double *__restrict__ cent,
-    const uint8_t *__restrict__ labels, int64_t n_lab, double *__restrict__ inertia, int32_t *__restrict__ sizes) {
-    __shared__ double part[kThreads];
-    __shared__ int cnt[DPL_MAX_CLUSTERS];
-    const int t = blockIdx.x, rs = blockIdx.y;
-    if (threadIdx.x < DPL_MAX_CLUSTERS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0, n = task_n[t];
-    const int32_t *rows = row_index + task_row_off[t];
-    const uint8_t *lab = labels + (int64_t)rs * n_lab + task_lab_off[t];
-    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols * kmax;
-    double s = 0.0;
-    int mine[DPL_MAX_CLUSTERS];
-#pragma unroll
-    for (int c = 0; c < DPL_MAX_CLUSTERS; ++c) mine[c] = 0;
-    for (int r = threadIdx.x; r < n; r += kThreads) {
-        int c = lab[r];
-        if (c >= n_clusters) c = 0;
-        s += sq_dist(x, n_rows, rows[r], col_index + c0, col_k + c0, ncols, kmax, cen + (int64_t)c * ncols * kmax);
-#pragma unroll
-        for (int k = 0; k < DPL_MAX_CLUSTERS; ++k) mine[k] += (k == c);
-    }
-    part[threadIdx.x] = s;
-#pragma unroll
-    for (int k = 0; k < DPL_MAX_CLUSTERS; ++k)
-        if (mine[k]) atomicAdd(&cnt[k], mine[k]);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double total = part[0];
-        for (int l = 1; l < kThreads; ++l) total += part[l];
-        inertia[(int64_t)t * n_restarts + rs] = total;
-    }
-    if ((int)threadIdx.x < n_clusters) sizes[((int64_t)t * n_restarts + rs) * n_clusters + threadIdx.x] = cnt[threadIdx.x];
-}
-
-bool common_ok(const void *x, int64_t n_rows, int n_cols, const void *row_index, int64_t n_index, const char *who) {
-    if (x == nullptr || row_index == nullptr) {
-        set_error("%s: null data or row index", who);
-        return false;
-    }
-    if (n_rows < 1 || n_rows > 2147483647ll || n_cols < 1 || n_index < 1) {
-        set_error("%s: n_rows = %lld, n_cols = %d, n_index = %lld out of domain", who, (long long)n_rows, n_cols, (long long)n_index);
-        return false;
-    }
-    return true;
 }
 
 bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
@@ -530,9 +460,10 @@ int dpl_kmeans_assign(const uint8_t *x, int64_t n_rows, int n_cols, const int32_
                     block_row0 && cent && labels && changed, "dpl_kmeans_assign: null argument");
     DPL_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxGrid && n_lab >= 1, "dpl_kmeans_assign: n_blocks = %lld, n_lab = %lld out of domain",
                 (long long)n_blocks, (long long)n_lab);
-    DPL_LAUNCH("dpl_kmeans_assign", kmeans_assign_kernel, dim3((unsigned)n_blocks, (unsigned)n_restarts), dim3(kThreads), 0,
-               (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, col_k, task_row_off, task_n, task_cent_off,
-               task_lab_off, block_task, block_row0, n_clusters, kmax, cent, labels, n_lab, first, changed);
+    DPL_LAUNCH("dpl_kmeans_assign", dpl_detail::kmeans_assign_kernel<OneHotColumns>, dim3((unsigned)n_blocks, (unsigned)n_restarts),
+               dim3(kThreads), 0, (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, (OneHotColumns{col_k, kmax}),
+               task_row_off, task_n, task_cent_off, task_lab_off, block_task, block_row0, n_clusters, cent, labels, n_lab, first,
+               changed);
     return DPL_OK;
 }
 
@@ -565,9 +496,9 @@ int dpl_kmeans_inertia(const uint8_t *x, int64_t n_rows, int n_cols, const int32
                     labels && inertia && sizes, "dpl_kmeans_inertia: null argument");
     DPL_REQUIRE(n_tasks >= 1 && n_lab >= 1, "dpl_kmeans_inertia: n_tasks = %d, n_lab = %lld out of domain", n_tasks,
                 (long long)n_lab);
-    DPL_LAUNCH("dpl_kmeans_inertia", kmeans_inertia_kernel, dim3((unsigned)n_tasks, (unsigned)n_restarts), dim3(kThreads), 0,
-               (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, col_k, task_row_off, task_n, task_cent_off,
-               task_lab_off, n_restarts, n_clusters, kmax, cent, labels, n_lab, inertia, sizes);
+    DPL_LAUNCH("dpl_kmeans_inertia", dpl_detail::kmeans_inertia_kernel<OneHotColumns>, dim3((unsigned)n_tasks, (unsigned)n_restarts),
+               dim3(kThreads), 0, (hipStream_t)stream, x, n_rows, row_index, task_col_off, col_index, (OneHotColumns{col_k, kmax}),
+               task_row_off, task_n, task_cent_off, task_lab_off, n_restarts, n_clusters, cent, labels, n_lab, inertia, sizes);
     return DPL_OK;
 }
 

@@ -12,20 +12,11 @@
 
 namespace {
 
+using dpl_detail::common_ok;
 using dpl_detail::kMaxGrid;
 using dpl_detail::kThreads;
 using dpl_detail::set_error;
-
-// The block's 256 partial sums added in order of the thread index; every thread forms the total itself (broadcast LDS
-// reads, the same order), and `part` is free again on return.  Reached by all threads of the block.
-__device__ __forceinline__ double sum_in_order(double *part, double mine) {
-    part[threadIdx.x] = mine;
-    __syncthreads();
-    double total = part[0];
-    for (int l = 1; l < kThreads; ++l) total += part[l];
-    __syncthreads();
-    return total;
-}
+using dpl_detail::sum_in_order;
 
 // ---- moments ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void column_moments_kernel(
@@ -187,44 +178,22 @@ __global__ __launch_bounds__(kThreads) void kmeansf_init_kernel(
     for (int p = threadIdx.x; p < ncols; p += kThreads) out[p] = (double)xf[(int64_t)col_index[c0 + p] * n_rows + row];
 }
 
-// squared distance of a row to one centroid: columns in order, one subtraction, one multiply and one add per column
-__device__ __forceinline__ double sq_distf(const float *__restrict__ xf, int64_t n_rows, int row,
-                                           const int32_t *__restrict__ cols, int ncols, const double *__restrict__ cen) {
-    double d = 0.0;
-    for (int p = 0; p < ncols; ++p) {
-        const double u = (double)xf[(int64_t)cols[p] * n_rows + row] - cen[p];
-        d += u * u;
-    }
-    return d;
-}
-
-__global__ __launch_bounds__(kThreads) void kmeansf_assign_kernel(
-    const float *__restrict__ xf, int64_t n_rows, const int32_t *__restrict__ row_index,
-    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int64_t *__restrict__ task_row_off,
-    const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off, const int64_t *__restrict__ task_lab_off,
-    const int32_t *__restrict__ block_task, const int32_t *__restrict__ block_row0, int n_clusters,
-    const double *__restrict__ cent, uint8_t *__restrict__ labels, int64_t n_lab, int first, int32_t *__restrict__ changed) {
-    const int t = block_task[blockIdx.x], rs = blockIdx.y;
-    const int i = block_row0[blockIdx.x] + threadIdx.x;
-    if (i >= task_n[t]) return;
-    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0;
-    const int row = row_index[task_row_off[t] + i];
-    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols;
-    double best = 0.0;
-    int arg = 0;
-    for (int c = 0; c < n_clusters; ++c) {
-        const double d = sq_distf(xf, n_rows, row, col_index + c0, ncols, cen + (int64_t)c * ncols);
-        if (c == 0 || d < best) {
-            best = d;
-            arg = c;
+// Float columns, the policy of the shared k-means kernels (learn_common.h): a centroid holds one mean per column.
+struct FloatColumns {
+    using value = float;
+    __device__ int stride() const { return 1; }
+    // squared distance of a row to one centroid: columns in order, one subtraction, one multiply and one add per column
+    __device__ __forceinline__ double sq_dist(const float *__restrict__ xf, int64_t n_rows, int row,
+                                              const int32_t *__restrict__ cols, int, int ncols,
+                                              const double *__restrict__ cen) const {
+        double d = 0.0;
+        for (int p = 0; p < ncols; ++p) {
+            const double u = (double)xf[(int64_t)cols[p] * n_rows + row] - cen[p];
+            d += u * u;
         }
+        return d;
     }
-    uint8_t *slot = labels + (int64_t)rs * n_lab + task_lab_off[t] + i;
-    if (first || *slot != (uint8_t)arg) {
-        *slot = (uint8_t)arg;
-        *changed = 1;       // (every writer stores the same value)
-    }
-}
+};
 
 __global__ __launch_bounds__(kThreads) void kmeansf_update_kernel(
     const float *__restrict__ xf, int64_t n_rows, const int32_t *__restrict__ row_index,
@@ -271,52 +240,6 @@ __global__ __launch_bounds__(kThreads) void kmeansf_update_kernel(
     }
 }
 
-__global__ __launch_bounds__(kThreads) void kmeansf_inertia_kernel(
-    const float *__restrict__ xf, int64_t n_rows, const int32_t *__restrict__ row_index,
-    const int32_t *__restrict__ task_col_off, const int32_t *__restrict__ col_index, const int64_t *__restrict__ task_row_off,
-    const int32_t *__restrict__ task_n, const int64_t *__restrict__ task_cent_off, const int64_t *__restrict__ task_lab_off,
-    int n_restarts, int n_clusters, const double *__restrict__ cent, const uint8_t *__restrict__ labels, int64_t n_lab,
-    double *__restrict__ inertia, int32_t *__restrict__ sizes) {
-    __shared__ double part[kThreads];
-    __shared__ int cnt[DPL_MAX_CLUSTERS];
-    const int t = blockIdx.x, rs = blockIdx.y;
-    if (threadIdx.x < DPL_MAX_CLUSTERS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int c0 = task_col_off[t], ncols = task_col_off[t + 1] - c0, n = task_n[t];
-    const int32_t *rows = row_index + task_row_off[t];
-    const uint8_t *lab = labels + (int64_t)rs * n_lab + task_lab_off[t];
-    const double *cen = cent + task_cent_off[t] + (int64_t)rs * n_clusters * ncols;
-    double s = 0.0;
-    int mine[DPL_MAX_CLUSTERS];
-#pragma unroll
-    for (int c = 0; c < DPL_MAX_CLUSTERS; ++c) mine[c] = 0;
-    for (int r = threadIdx.x; r < n; r += kThreads) {
-        int c = lab[r];
-        if (c >= n_clusters) c = 0;
-        s += sq_distf(xf, n_rows, rows[r], col_index + c0, ncols, cen + (int64_t)c * ncols);
-#pragma unroll
-        for (int q = 0; q < DPL_MAX_CLUSTERS; ++q) mine[q] += (q == c);
-    }
-#pragma unroll
-    for (int q = 0; q < DPL_MAX_CLUSTERS; ++q)
-        if (mine[q]) atomicAdd(&cnt[q], mine[q]);
-    const double total = sum_in_order(part, s);     // (its barriers also complete cnt)
-    if (threadIdx.x == 0) inertia[(int64_t)t * n_restarts + rs] = total;
-    if ((int)threadIdx.x < n_clusters) sizes[((int64_t)t * n_restarts + rs) * n_clusters + threadIdx.x] = cnt[threadIdx.x];
-}
-
-bool commonf_ok(const void *xf, int64_t n_rows, int n_cols, const void *row_index, int64_t n_index, const char *who) {
-    if (xf == nullptr || row_index == nullptr) {
-        set_error("%s: null data or row index", who);
-        return false;
-    }
-    if (n_rows < 1 || n_rows > 2147483647ll || n_cols < 1 || n_index < 1) {
-        set_error("%s: n_rows = %lld, n_cols = %d, n_index = %lld out of domain", who, (long long)n_rows, n_cols, (long long)n_index);
-        return false;
-    }
-    return true;
-}
-
 bool kmeansf_ok(int n_restarts, int n_clusters, const char *who) {
     if (n_restarts < 1 || n_restarts > 65535 || n_clusters < 1 || n_clusters > DPL_MAX_CLUSTERS || n_restarts * n_clusters > 65535) {
         set_error("%s: n_restarts = %d, n_clusters = %d (<= %d) out of domain", who, n_restarts, n_clusters, DPL_MAX_CLUSTERS);
@@ -332,7 +255,7 @@ extern "C" {
 int dpl_column_moments(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
                        const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,
                        double *moments, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_column_moments")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_column_moments")) return DPL_EINVAL;
     DPL_REQUIRE(item_col && item_row_off && item_n && moments, "dpl_column_moments: null argument");
     DPL_REQUIRE(n_items >= 1 && n_items <= kMaxGrid, "dpl_column_moments: n_items = %lld out of domain", (long long)n_items);
     DPL_LAUNCH("dpl_column_moments", column_moments_kernel, dim3((unsigned)n_items), dim3(kThreads), 0, (hipStream_t)stream, xf,
@@ -344,7 +267,7 @@ int dpl_ecdf_ranks(const float *xf, int64_t n_rows, int n_cols, const int32_t *r
                    const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n,
                    const int64_t *item_out_off, int64_t n_items, const int32_t *block_item, const int32_t *block_row0,
                    int64_t n_blocks, const float *sorted, int32_t *ranks, int64_t n_out, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_ecdf_ranks")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_ecdf_ranks")) return DPL_EINVAL;
     DPL_REQUIRE(item_col && item_row_off && item_n && item_out_off && block_item && block_row0 && sorted && ranks,
                 "dpl_ecdf_ranks: null argument");
     DPL_REQUIRE(n_items >= 1 && n_blocks >= 1 && n_blocks <= kMaxGrid && n_out >= 1,
@@ -387,7 +310,7 @@ int dpl_kmeansf_init(const float *xf, int64_t n_rows, int n_cols, const int32_t 
                      const int32_t *task_col_off, const int32_t *col_index, const int64_t *task_row_off,
                      const int32_t *task_n, const int64_t *task_cent_off, const int32_t *seeds, int n_tasks,
                      int n_restarts, int n_clusters, double *cent, int64_t n_cent, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_init")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_init")) return DPL_EINVAL;
     if (!kmeansf_ok(n_restarts, n_clusters, "dpl_kmeansf_init")) return DPL_EINVAL;
     DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && seeds && cent,
                 "dpl_kmeansf_init: null argument");
@@ -405,15 +328,15 @@ int dpl_kmeansf_assign(const float *xf, int64_t n_rows, int n_cols, const int32_
                        const int32_t *block_task, const int32_t *block_row0, int64_t n_blocks, int n_restarts,
                        int n_clusters, const double *cent, uint8_t *labels, int64_t n_lab, int first,
                        int32_t *changed, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_assign")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_assign")) return DPL_EINVAL;
     if (!kmeansf_ok(n_restarts, n_clusters, "dpl_kmeansf_assign")) return DPL_EINVAL;
     DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && task_lab_off && block_task && block_row0 &&
                     cent && labels && changed, "dpl_kmeansf_assign: null argument");
     DPL_REQUIRE(n_blocks >= 1 && n_blocks <= kMaxGrid && n_lab >= 1, "dpl_kmeansf_assign: n_blocks = %lld, n_lab = %lld out of domain",
                 (long long)n_blocks, (long long)n_lab);
-    DPL_LAUNCH("dpl_kmeansf_assign", kmeansf_assign_kernel, dim3((unsigned)n_blocks, (unsigned)n_restarts), dim3(kThreads), 0,
-               (hipStream_t)stream, xf, n_rows, row_index, task_col_off, col_index, task_row_off, task_n, task_cent_off,
-               task_lab_off, block_task, block_row0, n_clusters, cent, labels, n_lab, first, changed);
+    DPL_LAUNCH("dpl_kmeansf_assign", dpl_detail::kmeans_assign_kernel<FloatColumns>, dim3((unsigned)n_blocks, (unsigned)n_restarts),
+               dim3(kThreads), 0, (hipStream_t)stream, xf, n_rows, row_index, task_col_off, col_index, FloatColumns{}, task_row_off,
+               task_n, task_cent_off, task_lab_off, block_task, block_row0, n_clusters, cent, labels, n_lab, first, changed);
     return DPL_OK;
 }
 
@@ -422,7 +345,7 @@ int dpl_kmeansf_update(const float *xf, int64_t n_rows, int n_cols, const int32_
                        const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off,
                        const int32_t *item_task, const int32_t *item_p, int64_t n_items, int n_restarts,
                        int n_clusters, const uint8_t *labels, int64_t n_lab, double *cent, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_update")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_update")) return DPL_EINVAL;
     if (!kmeansf_ok(n_restarts, n_clusters, "dpl_kmeansf_update")) return DPL_EINVAL;
     DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && task_lab_off && item_task && item_p &&
                     labels && cent, "dpl_kmeansf_update: null argument");
@@ -439,15 +362,15 @@ int dpl_kmeansf_inertia(const float *xf, int64_t n_rows, int n_cols, const int32
                         const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off, int n_tasks,
                         int n_restarts, int n_clusters, const double *cent, const uint8_t *labels, int64_t n_lab,
                         double *inertia, int32_t *sizes, void *stream) {
-    if (!commonf_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_inertia")) return DPL_EINVAL;
+    if (!common_ok(xf, n_rows, n_cols, row_index, n_index, "dpl_kmeansf_inertia")) return DPL_EINVAL;
     if (!kmeansf_ok(n_restarts, n_clusters, "dpl_kmeansf_inertia")) return DPL_EINVAL;
     DPL_REQUIRE(task_col_off && col_index && task_row_off && task_n && task_cent_off && task_lab_off && cent && labels &&
                     inertia && sizes, "dpl_kmeansf_inertia: null argument");
     DPL_REQUIRE(n_tasks >= 1 && n_lab >= 1, "dpl_kmeansf_inertia: n_tasks = %d, n_lab = %lld out of domain", n_tasks,
                 (long long)n_lab);
-    DPL_LAUNCH("dpl_kmeansf_inertia", kmeansf_inertia_kernel, dim3((unsigned)n_tasks, (unsigned)n_restarts), dim3(kThreads), 0,
-               (hipStream_t)stream, xf, n_rows, row_index, task_col_off, col_index, task_row_off, task_n, task_cent_off,
-               task_lab_off, n_restarts, n_clusters, cent, labels, n_lab, inertia, sizes);
+    DPL_LAUNCH("dpl_kmeansf_inertia", dpl_detail::kmeans_inertia_kernel<FloatColumns>, dim3((unsigned)n_tasks, (unsigned)n_restarts),
+               dim3(kThreads), 0, (hipStream_t)stream, xf, n_rows, row_index, task_col_off, col_index, FloatColumns{}, task_row_off,
+               task_n, task_cent_off, task_lab_off, n_restarts, n_clusters, cent, labels, n_lab, inertia, sizes);
     return DPL_OK;
 }
 

@@ -103,14 +103,16 @@ def upload(device, **arrays):
 
 
 class DeviceData:
-    """The training set on the device: uint8 domain positions, column major (see the header)."""
+    """The training set on the device, column major: uint8 domain positions, or float32 values (see the header,
+    "continuous data").  The dtype tells the two apart; every operator asserts the one it takes."""
 
     def __init__(self, x_cm: torch.Tensor, n_rows: int, n_cols: int):
         if not x_cm.is_cuda:
             raise HipError("data lives on '{}': the deeprob HIP path only works on a HIP device (there is no CPU "
                            "fallback)".format(x_cm.device))
-        assert x_cm.dtype == torch.uint8 and x_cm.is_contiguous() and x_cm.numel() == n_rows * n_cols
+        assert x_cm.dtype in (torch.uint8, torch.float32) and x_cm.is_contiguous() and x_cm.numel() == n_rows * n_cols
         self.x, self.n_rows, self.n_cols, self.device = x_cm, int(n_rows), int(n_cols), x_cm.device
+        self.is_float = x_cm.dtype == torch.float32
 
     def head(self, row_index: torch.Tensor):
         assert row_index.dtype == torch.int32 and row_index.is_contiguous() and row_index.device == self.device
@@ -121,43 +123,54 @@ def _stream(device):
     return hip.stream_ptr(device)
 
 
+def _items(device, item_col, item_row_off, item_n, **more):
+    """The ``col`` / ``off`` / ``n`` tables of a launch over items (one column of one row segment each), with whatever
+    else the launch needs, in one upload."""
+    return upload(device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
+                  n=np.asarray(item_n, np.int32), **more)
+
+
+def _row_blocks(ns):
+    """(item of each 256-row block, its first row) for items of ``ns`` rows."""
+    item, row0 = [], []
+    for i, n in enumerate(ns):
+        for r0 in range(0, int(n), 256):
+            item.append(i)
+            row0.append(r0)
+    return np.asarray(item, np.int32), np.asarray(row0, np.int32)
+
+
 def column_counts(data: DeviceData, row_index, item_col, item_row_off, item_n, kmax: int) -> torch.Tensor:
     """``[n_items, kmax]`` int32 counts (``dpl_column_counts``); the item tables are host arrays."""
-    lib = load_library()
-    n_items = len(item_col)
-    t = upload(data.device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
-               n=np.asarray(item_n, np.int32))
-    counts = torch.empty((n_items, kmax), dtype=torch.int32, device=data.device)
-    call(lib.dpl_column_counts, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(), n_items,
-         kmax, counts.data_ptr(), _stream(data.device))
+    assert not data.is_float
+    t = _items(data.device, item_col, item_row_off, item_n)
+    counts = torch.empty((len(item_col), kmax), dtype=torch.int32, device=data.device)
+    call(load_library().dpl_column_counts, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
+         len(item_col), kmax, counts.data_ptr(), _stream(data.device))
     COUNTERS['kernels'] += 1
     return counts
 
 
-def pair_g(data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> torch.Tensor:
-    """``[n_pairs]`` float64 G statistics (``dpl_pair_g``); the pair tables are host arrays."""
-    lib = load_library()
-    n_pairs = len(col_i)
+def _pair_statistic(entry, data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> torch.Tensor:
+    """``[n_pairs]`` float64 from the entry point ``entry`` over column pairs; the six pair tables are host arrays."""
+    assert not data.is_float
     t = upload(data.device, ci=np.asarray(col_i, np.int32), cj=np.asarray(col_j, np.int32), off=np.asarray(row_off, np.int64),
                n=np.asarray(n, np.int32), ki=np.asarray(ki, np.int32), kj=np.asarray(kj, np.int32))
-    g = torch.empty(n_pairs, dtype=torch.float64, device=data.device)
-    call(lib.dpl_pair_g, *data.head(row_index), t['ci'].data_ptr(), t['cj'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
-         t['ki'].data_ptr(), t['kj'].data_ptr(), n_pairs, g.data_ptr(), _stream(data.device))
+    out = torch.empty(len(col_i), dtype=torch.float64, device=data.device)
+    call(getattr(load_library(), entry), *data.head(row_index), t['ci'].data_ptr(), t['cj'].data_ptr(), t['off'].data_ptr(),
+         t['n'].data_ptr(), t['ki'].data_ptr(), t['kj'].data_ptr(), len(col_i), out.data_ptr(), _stream(data.device))
     COUNTERS['kernels'] += 1
-    return g
+    return out
+
+
+def pair_g(data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> torch.Tensor:
+    """``[n_pairs]`` float64 G statistics (``dpl_pair_g``)."""
+    return _pair_statistic('dpl_pair_g', data, row_index, col_i, col_j, row_off, n, ki, kj)
 
 
 def pair_maxcorr(data: DeviceData, row_index, col_i, col_j, row_off, n, ki, kj) -> torch.Tensor:
-    """``[n_pairs]`` float64 maximal correlations (``dpl_pair_maxcorr``); the pair tables are host arrays."""
-    lib = load_library()
-    n_pairs = len(col_i)
-    t = upload(data.device, ci=np.asarray(col_i, np.int32), cj=np.asarray(col_j, np.int32), off=np.asarray(row_off, np.int64),
-               n=np.asarray(n, np.int32), ki=np.asarray(ki, np.int32), kj=np.asarray(kj, np.int32))
-    score = torch.empty(n_pairs, dtype=torch.float64, device=data.device)
-    call(lib.dpl_pair_maxcorr, *data.head(row_index), t['ci'].data_ptr(), t['cj'].data_ptr(), t['off'].data_ptr(),
-         t['n'].data_ptr(), t['ki'].data_ptr(), t['kj'].data_ptr(), n_pairs, score.data_ptr(), _stream(data.device))
-    COUNTERS['kernels'] += 1
-    return score
+    """``[n_pairs]`` float64 maximal correlations (``dpl_pair_maxcorr``)."""
+    return _pair_statistic('dpl_pair_maxcorr', data, row_index, col_i, col_j, row_off, n, ki, kj)
 
 
 def partition_rows(row_index, src_off, src_n, label_off, label, dst_off, dst_n, labels, n_out: int) -> torch.Tensor:
@@ -177,125 +190,102 @@ def partition_rows(row_index, src_off, src_n, label_off, label, dst_off, dst_n, 
 
 
 class KMeansBatch:
-    """The k-means of all row-splitting tasks of one generation (header: "k-means").  ``tasks``: a list of
-    ``(row_off, n, cols, ks, seeds)`` with ``seeds`` an ``[n_restarts, n_clusters]`` array of row positions."""
+    """The k-means of all row-splitting tasks of one generation (header: "k-means", "k-means on float columns").
+    ``tasks``: a list of ``(row_off, n, cols, ks, seeds)`` with ``seeds`` an ``[n_restarts, n_clusters]`` array of row
+    positions.  uint8 data: ``ks`` the domain sizes of ``cols`` and a centroid ``kmax`` value frequencies per column
+    (``dpl_kmeans_*``); float32 data: ``ks`` and ``kmax`` None and a centroid one mean per column (``dpl_kmeansf_*``)."""
 
     MAX_ITER = 100
 
-    def __init__(self, data: DeviceData, row_index, tasks, n_restarts: int, n_clusters: int, kmax: int):
-        self.data, self.row_index, self.R, self.C, self.kmax = data, row_index, n_restarts, n_clusters, max(int(kmax), 2)
-        self.T = len(tasks)
-        col_off, cols, ks, cent_off, lab_off = [0], [], [], [], []
+    def __init__(self, data: DeviceData, row_index, tasks, n_restarts: int, n_clusters: int, kmax: int = None):
+        assert data.is_float == (kmax is None)
+        self.data, self.row_index, self.R, self.C, self.T = data, row_index, n_restarts, n_clusters, len(tasks)
+        self.kmax = None if kmax is None else max(int(kmax), 2)
+        col_off, cols, ks, cent_off, lab_off, item_task, item_p = [0], [], [], [], [], [], []
         n_cent = n_lab = 0
-        for row_off, n, tcols, tks, seeds in tasks:
+        for t, (row_off, n, tcols, tks, seeds) in enumerate(tasks):
+            assert data.is_float == (tks is None)
             cols += list(tcols)
-            ks += list(tks)
+            ks += [] if tks is None else list(tks)
             col_off.append(len(cols))
             cent_off.append(n_cent)
             lab_off.append(n_lab)
-            n_cent += n_restarts * n_clusters * len(tcols) * self.kmax
+            n_cent += n_restarts * n_clusters * len(tcols) * (self.kmax or 1)
             n_lab += n
-        self.n_cent, self.n_lab = n_cent, n_lab
-        block_task, block_row0, item_task, item_p = [], [], [], []
-        for t, (row_off, n, tcols, _, _) in enumerate(tasks):
-            for r0 in range(0, n, 256):
-                block_task.append(t)
-                block_row0.append(r0)
             item_task += [t] * len(tcols)
             item_p += list(range(len(tcols)))
+        self.n_cent, self.n_lab, self.lab_off, self.cent_off = n_cent, n_lab, lab_off, cent_off
+        block_task, block_row0 = _row_blocks([t[1] for t in tasks])
         self.n_blocks, self.n_items = len(block_task), len(item_task)
         self.tab = upload(
-            data.device, col_off=np.asarray(col_off, np.int32), cols=np.asarray(cols, np.int32), ks=np.asarray(ks, np.int32),
+            data.device, col_off=np.asarray(col_off, np.int32), cols=np.asarray(cols, np.int32),
+            **({} if data.is_float else {'ks': np.asarray(ks, np.int32)}),
             row_off=np.asarray([t[0] for t in tasks], np.int64), n=np.asarray([t[1] for t in tasks], np.int32),
             cent_off=np.asarray(cent_off, np.int64), lab_off=np.asarray(lab_off, np.int64),
             seeds=np.concatenate([np.asarray(t[4], np.int32).reshape(-1) for t in tasks]),
-            block_task=np.asarray(block_task, np.int32), block_row0=np.asarray(block_row0, np.int32),
+            block_task=block_task, block_row0=block_row0,
             item_task=np.asarray(item_task, np.int32), item_p=np.asarray(item_p, np.int32))
-        self.lab_off = lab_off
 
     def run(self):
-        """``(inertia [T, R] float64, sizes [T, R, C] int32, labels [R, n_lab] device uint8, iterations)``."""
+        """``(inertia [T, R] float64, sizes [T, R, C] int32, labels [R, n_lab] device uint8, iterations)``; the centroids
+        stay in ``self.cent``."""
         lib, d, p = load_library(), self.data, {k: v.data_ptr() for k, v in self.tab.items()}
+        init, assign, update, inertia_of = (getattr(lib, ('dpl_kmeansf_' if d.is_float else 'dpl_kmeans_') + name)
+                                            for name in ('init', 'assign', 'update', 'inertia'))
+        ks, kmax = (() if d.is_float else (p['ks'],)), (() if d.is_float else (self.kmax,))
         dev, st = d.device, _stream(d.device)
         head = d.head(self.row_index)
-        cent = torch.empty(self.n_cent, dtype=torch.float64, device=dev)
+        cent = self.cent = torch.empty(self.n_cent, dtype=torch.float64, device=dev)
         labels = torch.empty((self.R, self.n_lab), dtype=torch.uint8, device=dev)
         changed = torch.zeros(self.MAX_ITER, dtype=torch.int32, device=dev)
         COUNTERS['kernels'] += 1        # (the fill of `changed`)
-        call(lib.dpl_kmeans_init, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['seeds'], self.T,
-             self.R, self.C, self.kmax, cent.data_ptr(), self.n_cent, st)
+        call(init, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['seeds'], self.T, self.R,
+             self.C, *kmax, cent.data_ptr(), self.n_cent, st)
         COUNTERS['kernels'] += 1
         iterations = 0
         for it in range(self.MAX_ITER):
-            call(lib.dpl_kmeans_assign, *head, p['col_off'], p['cols'], p['ks'], p['row_off'], p['n'], p['cent_off'],
-                 p['lab_off'], p['block_task'], p['block_row0'], self.n_blocks, self.R, self.C, self.kmax, cent.data_ptr(),
-                 labels.data_ptr(), self.n_lab, 1 if it == 0 else 0, changed[it:].data_ptr(), st)
+            call(assign, *head, p['col_off'], p['cols'], *ks, p['row_off'], p['n'], p['cent_off'], p['lab_off'],
+                 p['block_task'], p['block_row0'], self.n_blocks, self.R, self.C, *kmax, cent.data_ptr(), labels.data_ptr(),
+                 self.n_lab, 1 if it == 0 else 0, changed[it:].data_ptr(), st)
             COUNTERS['lloyd_kernels'] += 1
             iterations = it + 1
             if int(read(changed[it:it + 1], lloyd=True)[0]) == 0 or it == self.MAX_ITER - 1:
                 break
-            call(lib.dpl_kmeans_update, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
-                 p['item_task'], p['item_p'], self.n_items, self.R, self.C, self.kmax, labels.data_ptr(), self.n_lab,
+            call(update, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
+                 p['item_task'], p['item_p'], self.n_items, self.R, self.C, *kmax, labels.data_ptr(), self.n_lab,
                  cent.data_ptr(), st)
             COUNTERS['lloyd_kernels'] += 1
         inertia = torch.empty((self.T, self.R), dtype=torch.float64, device=dev)
         sizes = torch.empty((self.T, self.R, self.C), dtype=torch.int32, device=dev)
-        call(lib.dpl_kmeans_inertia, *head, p['col_off'], p['cols'], p['ks'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
-             self.T, self.R, self.C, self.kmax, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(),
-             sizes.data_ptr(), st)
+        call(inertia_of, *head, p['col_off'], p['cols'], *ks, p['row_off'], p['n'], p['cent_off'], p['lab_off'], self.T,
+             self.R, self.C, *kmax, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(), sizes.data_ptr(), st)
         COUNTERS['kernels'] += 1
         return read(inertia), read(sizes), labels, iterations
 
 
 # ---- continuous data (the last section of the header) ---------------------------------------------------------------------
-class DeviceDataF:
-    """The training set on the device as float32, column major (see the header, "continuous data")."""
-
-    def __init__(self, x_cm: torch.Tensor, n_rows: int, n_cols: int):
-        if not x_cm.is_cuda:
-            raise HipError("data lives on '{}': the deeprob HIP path only works on a HIP device (there is no CPU "
-                           "fallback)".format(x_cm.device))
-        assert x_cm.dtype == torch.float32 and x_cm.is_contiguous() and x_cm.numel() == n_rows * n_cols
-        self.x, self.n_rows, self.n_cols, self.device = x_cm, int(n_rows), int(n_cols), x_cm.device
-
-    head = DeviceData.head
-
-
-def column_moments(data: DeviceDataF, row_index, item_col, item_row_off, item_n) -> torch.Tensor:
+def column_moments(data: DeviceData, row_index, item_col, item_row_off, item_n) -> torch.Tensor:
     """``[n_items, 2]`` float64: mean and population variance of every item (``dpl_column_moments``)."""
-    lib = load_library()
-    n_items = len(item_col)
-    t = upload(data.device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
-               n=np.asarray(item_n, np.int32))
-    moments = torch.empty((n_items, 2), dtype=torch.float64, device=data.device)
-    call(lib.dpl_column_moments, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(), n_items,
-         moments.data_ptr(), _stream(data.device))
+    assert data.is_float
+    t = _items(data.device, item_col, item_row_off, item_n)
+    moments = torch.empty((len(item_col), 2), dtype=torch.float64, device=data.device)
+    call(load_library().dpl_column_moments, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
+         len(item_col), moments.data_ptr(), _stream(data.device))
     COUNTERS['kernels'] += 1
     return moments
 
 
-def _row_blocks(ns):
-    """(item of each 256-row block, its first row) for items of ``ns`` rows."""
-    item, row0 = [], []
-    for i, n in enumerate(ns):
-        for r0 in range(0, int(n), 256):
-            item.append(i)
-            row0.append(r0)
-    return np.asarray(item, np.int32), np.asarray(row0, np.int32)
-
-
-def ecdf_ranks(data: DeviceDataF, row_index, item_col, item_row_off, item_n):
+def ecdf_ranks(data: DeviceData, row_index, item_col, item_row_off, item_n):
     """``(ranks, out_off)``: the int32 "max" ranks of every item, item i at ``ranks[out_off[i] : out_off[i] + item_n[i]]``
     in segment order (``dpl_ecdf_ranks``).  The values of all items are gathered and sorted on the device with
     ``torch.sort`` (by value, then stably by item); no row is sorted on the host."""
+    assert data.is_float
     lib = load_library()
     n_items = len(item_col)
-    ns = np.asarray(item_n, np.int64)
-    out_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum(np.asarray(item_n, np.int64))]).astype(np.int64)
     total = int(out_off[-1])
-    block_item, block_row0 = _row_blocks(ns)
-    t = upload(data.device, col=np.asarray(item_col, np.int32), off=np.asarray(item_row_off, np.int64),
-               n=ns.astype(np.int32), out=out_off[:-1].copy(), bi=block_item, br=block_row0)
+    block_item, block_row0 = _row_blocks(item_n)
+    t = _items(data.device, item_col, item_row_off, item_n, out=out_off[:-1].copy(), bi=block_item, br=block_row0)
     item_of = torch.repeat_interleave(torch.arange(n_items, device=data.device), t['n'].long(), output_size=total)
     pos = torch.arange(total, device=data.device) - t['out'][item_of]
     rows = row_index[t['off'][item_of] + pos].long()
@@ -373,68 +363,3 @@ def rdc_gram(ranks: torch.Tensor, tasks, k: int, w: np.ndarray, b: np.ndarray, r
         COUNTERS['kernels'] += 2
         partials.append(partial)
     return {'G': G, 'S': S, 'g_off': g_off[:-1], 'feat_off': feat_off[:-1], 'fs': fs, 'partials': partials}
-
-
-class KMeansBatchF:
-    """The k-means of all row-splitting tasks of one generation on float columns (header: "k-means on float columns").
-    ``tasks``: a list of ``(row_off, n, cols, seeds)`` with ``seeds`` an ``[n_restarts, n_clusters]`` array of row positions."""
-
-    MAX_ITER = KMeansBatch.MAX_ITER
-
-    def __init__(self, data: DeviceDataF, row_index, tasks, n_restarts: int, n_clusters: int):
-        self.data, self.row_index, self.R, self.C = data, row_index, n_restarts, n_clusters
-        self.T = len(tasks)
-        col_off, cols, cent_off, lab_off = [0], [], [], []
-        n_cent = n_lab = 0
-        item_task, item_p = [], []
-        for t, (row_off, n, tcols, seeds) in enumerate(tasks):
-            cols += list(tcols)
-            col_off.append(len(cols))
-            cent_off.append(n_cent)
-            lab_off.append(n_lab)
-            n_cent += n_restarts * n_clusters * len(tcols)
-            n_lab += n
-            item_task += [t] * len(tcols)
-            item_p += list(range(len(tcols)))
-        self.n_cent, self.n_lab, self.lab_off, self.cent_off = n_cent, n_lab, lab_off, cent_off
-        block_task, block_row0 = _row_blocks([t[1] for t in tasks])
-        self.n_blocks, self.n_items = len(block_task), len(item_task)
-        self.tab = upload(
-            data.device, col_off=np.asarray(col_off, np.int32), cols=np.asarray(cols, np.int32),
-            row_off=np.asarray([t[0] for t in tasks], np.int64), n=np.asarray([t[1] for t in tasks], np.int32),
-            cent_off=np.asarray(cent_off, np.int64), lab_off=np.asarray(lab_off, np.int64),
-            seeds=np.concatenate([np.asarray(t[3], np.int32).reshape(-1) for t in tasks]),
-            block_task=block_task, block_row0=block_row0,
-            item_task=np.asarray(item_task, np.int32), item_p=np.asarray(item_p, np.int32))
-
-    def run(self):
-        """``(inertia [T, R] float64, sizes [T, R, C] int32, labels [R, n_lab] device uint8, iterations)``; the centroids
-        stay in ``self.cent``."""
-        lib, d, p = load_library(), self.data, {k: v.data_ptr() for k, v in self.tab.items()}
-        dev, st = d.device, _stream(d.device)
-        head = d.head(self.row_index)
-        cent = self.cent = torch.empty(self.n_cent, dtype=torch.float64, device=dev)
-        labels = torch.empty((self.R, self.n_lab), dtype=torch.uint8, device=dev)
-        changed = torch.zeros(self.MAX_ITER, dtype=torch.int32, device=dev)
-        COUNTERS['kernels'] += 1        # (the fill of `changed`)
-        call(lib.dpl_kmeansf_init, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['seeds'], self.T,
-             self.R, self.C, cent.data_ptr(), self.n_cent, st)
-        COUNTERS['kernels'] += 1
-        iterations = 0
-        for it in range(self.MAX_ITER):
-            call(lib.dpl_kmeansf_assign, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
-                 p['block_task'], p['block_row0'], self.n_blocks, self.R, self.C, cent.data_ptr(), labels.data_ptr(),
-                 self.n_lab, 1 if it == 0 else 0, changed[it:].data_ptr(), st)
-            COUNTERS['lloyd_kernels'] += 1
-            iterations = it + 1
-            if int(read(changed[it:it + 1], lloyd=True)[0]) == 0 or it == self.MAX_ITER - 1:
-                break
-            call(lib.dpl_kmeansf_update, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
-                 p['item_task'], p['item_p'], self.n_items, self.R, self.C, labels.data_ptr(), self.n_lab, cent.data_ptr(), st)
-            COUNTERS['lloyd_kernels'] += 1
-        inertia = torch.empty((self.T, self.R), dtype=torch.float64, device=dev)
-        sizes = torch.empty((self.T, self.R, self.C), dtype=torch.int32, device=dev)
-        call(lib.dpl_kmeansf_inertia, *head, p['col_off'], p['cols'], p['row_off'], p['n'], p['cent_off'], p['lab_off'],
-             self.T, self.R, self.C, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(), sizes.data_ptr(), st)
-        COUNTERS['kernels'] += 1
-        return read(inertia), read(sizes), labels, iterations

@@ -1,19 +1,23 @@
-"""LearnSPN (reference deeprob/spn/learning/learnspn.py:41-222) for discrete data, with the statistics of every task on
-the HIP device and the task queue, every random draw and the graph on the host.  Returns a
-:class:`deeprob.spn.structure.io.FlatSpn`.
+"""LearnSPN (reference deeprob/spn/learning/learnspn.py:41-222), with the statistics of every task on the HIP device and
+the task queue, every random draw and the graph on the host.  Returns a :class:`deeprob.spn.structure.io.FlatSpn`.
 
 The reference pops one task at a time from a FIFO queue.  The queue is breadth first, so the tasks of one GENERATION
 (one depth of the task tree, a retry counting as a child) are consecutive in it and their children follow in the same
-order; a generation is processed here as a whole: column counts of all its tasks in one launch, the operations decided
-from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the G
-statistics (or, for ``rdc_cols``, the maximal correlations) of all column-splitting tasks in one launch, the k-means of
-all row-splitting tasks together, and one partition launch that writes the next generation's row-index array.  See DESIGN.md, "LearnSPN on the device".
+order; a generation is processed here as a whole: column statistics of all its tasks in one launch, the operations decided
+from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the
+statistics of all column-splitting tasks, the k-means of all row-splitting tasks together, and one partition launch that
+writes the next generation's row-index array.  The loop is written once; what depends on the kind of the columns --
+discrete (:class:`DiscreteColumns`, below) or Gaussian (``learnspn_cont.GaussianColumns``) -- is asked of a column-kind
+object.  See DESIGN.md, "LearnSPN on the device".
 """
 from collections import deque
 from typing import List, Optional, Union
 
 import numpy as np
+import torch
 
+from deeprob.hip import HipError, learn as L
+from deeprob.spn.learning.splitting import rdc as R
 from deeprob.spn.structure.leaf import LeafType, Bernoulli, Categorical
 
 #: what ``get_learn_leaf_method`` / ``get_split_rows_method`` / ``get_split_cols_method`` of the reference know
@@ -30,8 +34,10 @@ _last_info = {}
 
 
 def last_info() -> dict:
-    """What the last ``learn_spn`` recorded: ``generations``, ``launches`` (kernel launches, host reads and uploads outside
-    the Lloyd loop), ``lloyd_launches``, ``tasks_per_generation`` and the split of ``launches``."""
+    """What the last ``learn_spn`` recorded: ``generations``, ``tasks_per_generation``, ``kernels`` (launches of the learn
+    library outside the Lloyd loop; ``torch.sort`` and the gathers in front of it are not counted), ``reads``, ``uploads``,
+    ``launches`` (the sum of the three), ``lloyd_launches`` and ``lloyd_iterations``; on discrete data also
+    ``launches_per_generation``, the bound DESIGN.md derives for ``launches`` there."""
     return dict(_last_info)
 
 
@@ -67,7 +73,6 @@ def check_random_state(random_state):
 
 def check_discrete(distributions, domains, who='learn_spn'):
     """Every distribution is Bernoulli or Categorical and every domain ``list(range(K))`` with ``K <= DPL_MAX_K``."""
-    from deeprob.hip import learn as L
     for dist in distributions:
         if getattr(dist, 'LEAF_TYPE', None) != LeafType.DISCRETE or dist not in (Bernoulli, Categorical):
             raise NotImplementedError("{} leaves are not built by {} on the HIP path (built: Bernoulli, Categorical)"
@@ -82,10 +87,11 @@ def check_discrete(distributions, domains, who='learn_spn'):
             raise ValueError("The domain of the Bernoulli variable {} must be [0, 1], got {}".format(i, dom))
 
 
-def check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs, split_rows_kwargs,
-                    split_cols_kwargs, min_rows_slice, min_cols_slice):
+def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs,
+                    split_rows_kwargs, split_cols_kwargs, min_rows_slice, min_cols_slice):
     """The argument checks of ``learn_spn`` in the reference's order (learnspn.py:80-96), then what this path does not
-    build; returns ``(leaf kwargs, rows kwargs, cols kwargs)`` with the defaults filled in.  Touches no device."""
+    build for columns of ``kind``; returns ``(leaf kwargs, rows kwargs, cols kwargs)`` with the defaults filled in.
+    Touches no device."""
     if len(distributions) == 0:
         raise ValueError("The list of distribution classes must be non-empty")
     if len(domains) == 0:
@@ -101,32 +107,26 @@ def check_arguments(data, distributions, domains, learn_leaf, split_rows, split_
         raise ValueError("Each data column should correspond to a random variable having a distribution and a domain")
     _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
     _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
-    from deeprob.spn.learning.splitting.rdc import rdc_cols, check_parameters, D_DEFAULT, K_DEFAULT, S_DEFAULT
-    rdc = split_cols is rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
+    rdc = split_cols is R.rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
     if not rdc:
-        _method(split_cols, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
+        kind.check_split_cols(split_cols)
     leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
     rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
     if rdc:
-        cols_kw = _kwargs(split_cols_kwargs, {'d': D_DEFAULT, 'k': K_DEFAULT, 's': S_DEFAULT}, 'rdc_cols')
+        cols_kw = _kwargs(split_cols_kwargs, {'d': R.D_DEFAULT, 'k': R.K_DEFAULT, 's': R.S_DEFAULT}, 'rdc_cols')
     else:
         cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
-    if leaf_kw['alpha'] < 0.0:
+    if kind.smoothed_leaves and leaf_kw['alpha'] < 0.0:
         raise ValueError("The Laplace smoothing factor must be non-negative")
-    from deeprob.hip import learn as L
     if split_rows == 'kmeans' and not 1 <= int(rows_kw['n']) <= L.DPL_MAX_CLUSTERS:
         raise ValueError("k-means on the HIP path takes 1..{} clusters".format(L.DPL_MAX_CLUSTERS))
-    check_discrete(distributions, domains)
-    if rdc:
-        check_parameters([len(dom) for dom in domains], **cols_kw)
+    kind.check_columns(cols_kw if rdc else None)
     return leaf_kw, rows_kw, cols_kw
 
 
 def _to_device(data, ks):
     """The data as uint8 domain positions, column major, on the device (one upload); ValueError on NaN or on a value
     outside its domain; HipError for a CPU tensor."""
-    import torch
-    from deeprob.hip import HipError, learn as L
     if isinstance(data, torch.Tensor):
         if not data.is_cuda:
             raise HipError("data lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no "
@@ -159,25 +159,20 @@ class _Task:
         self.row_off = 0
 
 
+def item_tables(tasks):
+    """(column, row offset, rows) of every column of every task: the items of a launch over columns."""
+    return ([s for t in tasks for s in t.scope], [t.row_off for t in tasks for _ in t.scope],
+            [t.n for t in tasks for _ in t.scope])
+
+
 def new_node(cls, scope, **kw):
     return dict({'class': cls, 'scope': list(scope), 'children': []}, **kw)
 
 
-def mle_leaf(dist, var, counts, n, alpha):
-    """learning/leaf.py:64-68 with structure/leaf.py:162 (Bernoulli) / :261-264 (Categorical) from the column's counts."""
-    if dist is Bernoulli:
-        return new_node('Bernoulli', [var], params={'p': (float(counts[1]) + alpha) / (n + 2 * alpha)})
-    k = len(counts)
-    probs = np.empty(k, np.float32)
-    for i in range(k):
-        probs[i] = (int(counts[i]) + alpha) / (n + k * alpha)
-    return new_node('Categorical', [var], params={'categories': list(range(k)), 'probabilities': [float(q) for q in probs]})
-
-
-def naive_factorization(distributions, scope, counts, n, alpha):
+def naive_factorization(kind, scope, stats, n, alpha):
     node = new_node('Product', scope)
     for i, s in enumerate(scope):
-        node['children'].append(mle_leaf(distributions[s], s, counts[i], n, alpha))
+        node['children'].append(kind.leaf(s, stats[i], n, alpha))
     return node
 
 
@@ -234,6 +229,107 @@ def component(adjacent, start):
     return seen
 
 
+class DiscreteColumns:
+    """What ``learn_spn`` asks of the kind of its columns, for ``Bernoulli`` / ``Categorical`` columns: the checks and the
+    upload, the statistics of a generation's columns, the leaves, the column-split draws and clusters, the k-means batch."""
+
+    launches_per_generation = LAUNCHES_PER_GENERATION
+    smoothed_leaves = True                  # (alpha is used, so it is checked)
+
+    def __init__(self, distributions, domains):
+        self.distributions, self.domains = distributions, domains
+
+    # ---- the checks of check_arguments that depend on the kind, in its order
+    def check_split_cols(self, name):
+        _method(name, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
+
+    def check_columns(self, rdc_kw):
+        check_discrete(self.distributions, self.domains)
+        if rdc_kw is not None:
+            R.check_parameters([len(dom) for dom in self.domains], **rdc_kw)
+
+    def upload(self, data):
+        L.load_library()
+        self.ks = [len(d) for d in self.domains]
+        self.kmax = max(2, max(self.ks))
+        self.data = _to_device(data, self.ks)
+        return self.data
+
+    # ---- a generation
+    def column_stats(self, row_index, item_col, item_off, item_n):
+        """(the ``[kmax]`` counts, whether it is constant) of every item, from one launch and one read."""
+        counts = L.read(L.column_counts(self.data, row_index, item_col, item_off, item_n, self.kmax))
+        return counts, counts.max(axis=1) == np.asarray(item_n)         # a constant column: np.var == 0
+
+    def leaf(self, var, counts, n, alpha):
+        """learning/leaf.py:64-68 with structure/leaf.py:162 (Bernoulli) / :261-264 (Categorical) from the column's counts."""
+        if self.distributions[var] is Bernoulli:
+            return new_node('Bernoulli', [var], params={'p': (float(counts[1]) + alpha) / (n + 2 * alpha)})
+        k = self.ks[var]
+        probs = np.empty(k, np.float32)
+        for i in range(k):
+            probs[i] = (int(counts[i]) + alpha) / (n + k * alpha)
+        return new_node('Categorical', [var], params={'categories': list(range(k)), 'probabilities': [float(q) for q in probs]})
+
+    def draw_split_cols(self, random_state, t, split_cols, cols_kw):
+        """The draws of a column split that is not 'random' (gvs.py:30, 76, 89; rdc.py:170-176): (columns tested, start,
+        coin)."""
+        nf = len(t.scope)
+        if split_cols == 'rdc':
+            R.consume_draws(random_state, [self.ks[s] for s in t.scope], int(cols_kw['k']))
+            return np.arange(nf), None, None
+        k = int(max(np.sqrt(nf), 2))
+        if split_cols == 'gvs' or k == nf:
+            return np.arange(nf), random_state.randint(0, nf), None
+        perm = random_state.permutation(np.arange(nf))[:k]
+        start = random_state.randint(0, k)
+        return perm, start, random_state.rand()
+
+    def split_cols_clusters(self, row_index, tasks, split_cols, cols_kw):
+        """The column clusters of every gvs / rgvs / rdc task: the G statistics (or maximal correlations) of all their
+        column pairs in one launch, then per task the adjacency and its component (gvs.py:31-50) or components."""
+        ks, ci, cj, off, n = np.asarray(self.ks), [], [], [], []
+        for t in tasks:
+            cols = np.asarray(t.scope)[t.draw[0]]
+            ia, ib = np.triu_indices(len(cols), 1)          # the pairs a < b, in the order of two nested loops
+            ci, cj = ci + list(cols[ia]), cj + list(cols[ib])
+            off, n = off + [t.row_off] * len(ia), n + [t.n] * len(ia)
+        ci, cj = np.asarray(ci, np.int64), np.asarray(cj, np.int64)
+        pair_stat = L.pair_maxcorr if split_cols == 'rdc' else L.pair_g
+        g_all = L.read(pair_stat(self.data, row_index, ci, cj, off, n, ks[ci], ks[cj])) if len(ci) else np.zeros(0)
+        out, g_pos = [], 0
+        for t in tasks:
+            (sub, start, coin), nf = t.draw, len(t.scope)
+            k = len(sub)
+            ia, ib = np.triu_indices(k, 1)
+            g = g_all[g_pos:g_pos + len(ia)]
+            g_pos += len(ia)
+            if split_cols == 'rdc':
+                dependent = g > cols_kw['d']                                              # rdc.py:43
+            else:
+                k_of = ks[np.asarray(t.scope)[sub]]
+                dof = (k_of[ia] - 1) * (k_of[ib] - 1)
+                dependent = ~(g < 2.0 * dof * cols_kw['p'])                               # gvs.py:203-205, :42
+            adjacent = np.zeros((k, k), bool)
+            adjacent[ia, ib] = adjacent[ib, ia] = dependent
+            if split_cols == 'rdc':
+                clusters = R.components(adjacent)                                         # rdc.py:46-48
+            else:
+                part = np.zeros(k, np.int64)
+                part[list(component(adjacent, int(start)))] = 1
+                if coin is None:
+                    clusters = part
+                else:
+                    clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
+                    clusters[sub] = part
+            out.append(clusters)
+        return out
+
+    def kmeans_batch(self, row_index, tasks, n_clusters):
+        return L.KMeansBatch(self.data, row_index, [(t.row_off, t.n, t.scope, [self.ks[s] for s in t.scope], t.draw) for t in tasks],
+                             KMEANS_RESTARTS, n_clusters, self.kmax)
+
+
 def learn_spn(
     data,
     distributions: list,
@@ -284,26 +380,20 @@ def learn_spn(
     :raises NotImplementedError: For what the reference knows and this path does not build.
     :raises HipError: If the data is a CPU tensor or the native library is missing.
     """
-    from deeprob.spn.learning.splitting.rdc import all_gaussian
-    if all_gaussian(distributions):         # all-continuous data: a path of its own (learnspn_cont.py)
-        from deeprob.spn.learning.learnspn_cont import learn_spn_cont
-        return learn_spn_cont(data, distributions, domains, learn_leaf, split_rows, split_cols, learn_leaf_kwargs,
-                              split_rows_kwargs, split_cols_kwargs, min_rows_slice, min_cols_slice, random_state, verbose)
-    leaf_kw, rows_kw, cols_kw = check_arguments(data, distributions, domains, learn_leaf, split_rows, split_cols,
+    if R.all_gaussian(distributions):
+        from deeprob.spn.learning.learnspn_cont import GaussianColumns
+        kind = GaussianColumns(distributions, domains)
+    else:
+        kind = DiscreteColumns(distributions, domains)
+    leaf_kw, rows_kw, cols_kw = check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, split_cols,
                                                 learn_leaf_kwargs, split_rows_kwargs, split_cols_kwargs, min_rows_slice,
                                                 min_cols_slice)
     random_state = check_random_state(random_state)
-    import torch
-    from deeprob.hip import learn as L
-    from deeprob.spn.learning.splitting import rdc as R
     if split_cols is R.rdc_cols:
         split_cols = 'rdc'
-    L.load_library()
-    ks_all = [len(d) for d in domains]
-    dev_data = _to_device(data, ks_all)
+    dev_data = kind.upload(data)
     device = dev_data.device
     n_total, n_features = dev_data.n_rows, dev_data.n_cols
-    kmax = max(2, max(ks_all))
     alpha = float(leaf_kw['alpha'])
     L.reset_counters()
     row_index = torch.arange(n_total, dtype=torch.int32, device=device)
@@ -313,18 +403,12 @@ def learn_spn(
     tasks_per_generation, lloyd_iterations = [], 0
     while generation:
         tasks_per_generation.append(len(generation))
-        # ---- column counts of every task, the operation of every task (learnspn.py:130-147) -------------------------
-        item_col, item_off, item_n = [], [], []
+        # ---- column statistics of every task, the operation of every task (learnspn.py:130-147) ----------------------
+        stats, constant = kind.column_stats(row_index, *item_tables(generation))
+        first = 0
         for t in generation:
-            item_col += t.scope
-            item_off += [t.row_off] * len(t.scope)
-            item_n += [t.n] * len(t.scope)
-        counts = L.read(L.column_counts(dev_data, row_index, item_col, item_off, item_n, kmax))
-        o = 0
-        for t in generation:
-            t.counts = [counts[o + i, :ks_all[s]] for i, s in enumerate(t.scope)]
-            o += len(t.scope)
-            zero_var = np.array([int(c.max()) == t.n for c in t.counts])     # a constant column: np.var == 0
+            t.counts, zero_var = stats[first:first + len(t.scope)], constant[first:first + len(t.scope)]
+            first += len(t.scope)
             t.draw = zero_var
             if zero_var.all():
                 t.op = 'naive'
@@ -336,9 +420,8 @@ def learn_spn(
                 t.op = 'rows'
             else:
                 t.op = 'cols'
-        # ---- the draws, in queue order (gvs.py:30, 76, 89; random.py:31-32, 56-57; k-means seeds) ---------------------
+        # ---- the draws, in queue order (random.py:31-32, 56-57; k-means seeds; the kind's column-split draws) -------
         for t in generation:
-            nf = len(t.scope)
             if t.op == 'rows' and split_rows == 'random':
                 p = random_state.beta(rows_kw['a'], rows_kw['b'])
                 t.draw = random_state.binomial(1, p, size=t.n)
@@ -349,48 +432,24 @@ def learn_spn(
                 t.draw = np.stack([random_state.choice(t.n, c, replace=False) for _ in range(KMEANS_RESTARTS)])
             elif t.op == 'cols' and split_cols == 'random':
                 p = random_state.beta(cols_kw['a'], cols_kw['b'])
-                t.draw = random_state.binomial(1, p, size=nf)
-            elif t.op == 'cols' and split_cols == 'rdc':
-                R.consume_draws(random_state, [ks_all[s] for s in t.scope], int(cols_kw['k']))      # rdc.py:170-176
-                t.draw = (np.arange(nf), None, None)
+                t.draw = random_state.binomial(1, p, size=len(t.scope))
             elif t.op == 'cols':
-                k = int(max(np.sqrt(nf), 2))
-                if split_cols == 'gvs' or k == nf:
-                    t.draw = (np.arange(nf), random_state.randint(0, nf), None)
-                else:
-                    perm = random_state.permutation(np.arange(nf))[:k]
-                    start = random_state.randint(0, k)
-                    t.draw = (perm, start, random_state.rand())
-        # ---- G statistics of every gvs / rgvs task, or maximal correlations of every rdc task -------------------------
-        gvs_tasks = [t for t in generation if t.op == 'cols' and split_cols != 'random']
-        pair_stat = L.pair_maxcorr if split_cols == 'rdc' else L.pair_g
-        pc = {k: [] for k in ('ci', 'cj', 'off', 'n', 'ki', 'kj')}
-        for t in gvs_tasks:
-            sub = [t.scope[i] for i in t.draw[0]]
-            for a in range(len(sub)):
-                for b in range(a + 1, len(sub)):
-                    pc['ci'].append(sub[a])
-                    pc['cj'].append(sub[b])
-                    pc['off'].append(t.row_off)
-                    pc['n'].append(t.n)
-                    pc['ki'].append(ks_all[sub[a]])
-                    pc['kj'].append(ks_all[sub[b]])
-        g_all = L.read(pair_stat(dev_data, row_index, pc['ci'], pc['cj'], pc['off'], pc['n'], pc['ki'], pc['kj'])) \
-            if pc['ci'] else np.zeros(0)
+                t.draw = kind.draw_split_cols(random_state, t, split_cols, cols_kw)
+        # ---- the column clusters of every column-splitting task that is not 'random' ---------------------------------
+        tested = [t for t in generation if t.op == 'cols' and split_cols != 'random']
+        clusters_of = {id(t): c for t, c in zip(tested, kind.split_cols_clusters(row_index, tested, split_cols, cols_kw))}
         # ---- k-means of every row-splitting task ----------------------------------------------------------------------
         km_tasks = [t for t in generation if t.op == 'rows' and split_rows == 'kmeans']
         km_labels, km_result = None, {}
         if km_tasks:
-            batch = L.KMeansBatch(dev_data, row_index,
-                                  [(t.row_off, t.n, t.scope, [ks_all[s] for s in t.scope], t.draw) for t in km_tasks],
-                                  KMEANS_RESTARTS, int(rows_kw['n']), kmax)
+            batch = kind.kmeans_batch(row_index, km_tasks, int(rows_kw['n']))
             inertia, sizes, km_labels, iters = batch.run()
             lloyd_iterations += iters
             for i, t in enumerate(km_tasks):
                 best = int(np.argmin(inertia[i]))              # the lowest inertia, the first one on a tie
                 km_result[id(t)] = (best * batch.n_lab + batch.lab_off[i], sizes[i, best])
         # ---- the nodes and the children of every task, in queue order (learnspn.py:149-210) -------------------------
-        children, host_labels, n_host_labels, g_pos = [], [], 0, 0
+        children, host_labels, n_host_labels = [], [], 0
 
         def child(task, parent_task, label_off=0, label=-1):
             task.child_src = (parent_task.row_off, parent_task.n, label_off, label)
@@ -402,17 +461,14 @@ def learn_spn(
                 zero_var = t.draw
                 node = new_node('Product', scope)
                 rem = [i for i in range(nf) if zero_var[i]]
-                node['children'].append(naive_factorization(distributions, [scope[i] for i in rem],
-                                                            [t.counts[i] for i in rem], t.n, alpha))
+                node['children'].append(naive_factorization(kind, [scope[i] for i in rem], [t.counts[i] for i in rem], t.n,
+                                                            alpha))
                 child(_Task(node, t.n, [scope[i] for i in range(nf) if not zero_var[i]], is_first=t.is_first), t)
                 t.parent['children'].append(node)
-            elif t.op == 'leaf':
-                if nf == 1:
-                    t.parent['children'].append(mle_leaf(distributions[scope[0]], scope[0], t.counts[0], t.n, alpha))
-                else:
-                    t.parent['children'].append(naive_factorization(distributions, scope, t.counts, t.n, alpha))
-            elif t.op == 'naive':
-                t.parent['children'].append(naive_factorization(distributions, scope, t.counts, t.n, alpha))
+            elif t.op == 'leaf' and nf == 1:
+                t.parent['children'].append(kind.leaf(scope[0], t.counts[0], t.n, alpha))
+            elif t.op in ('leaf', 'naive'):
+                t.parent['children'].append(naive_factorization(kind, scope, t.counts, t.n, alpha))
             elif t.op == 'rows':
                 if split_rows == 'random':
                     labels = t.draw.astype(np.uint8)
@@ -431,35 +487,7 @@ def learn_spn(
                     child(_Task(node, int(sizes_t[c]), scope), t, label_off, c)
                 t.parent['children'].append(node)
             else:
-                if split_cols == 'random':
-                    clusters = np.asarray(t.draw)
-                else:
-                    sub, start, coin = t.draw
-                    k = len(sub)
-                    n_pairs = k * (k - 1) // 2
-                    g = g_all[g_pos:g_pos + n_pairs]
-                    g_pos += n_pairs
-                    adjacent = np.zeros((k, k), bool)
-                    q = 0
-                    for a in range(k):
-                        for b in range(a + 1, k):
-                            if split_cols == 'rdc':
-                                dependent = bool(g[q] > cols_kw['d'])                     # rdc.py:43
-                            else:
-                                dof = (ks_all[scope[sub[a]]] - 1) * (ks_all[scope[sub[b]]] - 1)
-                                dependent = not (g[q] < 2.0 * dof * cols_kw['p'])         # gvs.py:203-205, :42
-                            adjacent[a, b] = adjacent[b, a] = dependent
-                            q += 1
-                    if split_cols == 'rdc':
-                        clusters = R.components(adjacent)                                 # rdc.py:46-48
-                    else:
-                        part = np.zeros(k, np.int64)
-                        part[list(component(adjacent, int(start)))] = 1
-                        if coin is None:
-                            clusters = part
-                        else:
-                            clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
-                            clusters[sub] = part
+                clusters = np.asarray(t.draw) if split_cols == 'random' else clusters_of[id(t)]
                 present = np.unique(clusters)
                 if len(present) == 1:
                     child(_Task(t.parent, t.n, scope, no_cols_split=True, no_rows_split=False), t)
@@ -486,5 +514,7 @@ def learn_spn(
     _last_info.update(generations=len(tasks_per_generation), launches=c['kernels'] + c['reads'] + c['uploads'],
                       kernels=c['kernels'], reads=c['reads'], uploads=c['uploads'],
                       lloyd_launches=c['lloyd_kernels'] + c['lloyd_reads'], lloyd_iterations=lloyd_iterations,
-                      tasks_per_generation=tasks_per_generation, launches_per_generation=LAUNCHES_PER_GENERATION)
+                      tasks_per_generation=tasks_per_generation)
+    if kind.launches_per_generation is not None:
+        _last_info['launches_per_generation'] = kind.launches_per_generation
     return to_flat(tmp_node['children'][0])

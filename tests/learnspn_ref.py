@@ -108,45 +108,125 @@ def inertia_sum(d):
     return float(total)
 
 
-def kmeans(data, ks, rs, n=2, stats=None):
-    """Labels of the winning restart.  ``stats['gap']``: the smallest relative gap between a row's two nearest centroids
-    over all assignments of winning restarts."""
+def kmeans_restart(data, ks, seed, n):
+    """One restart from the rows ``seed``: (labels, inertia, sizes, smallest relative gap between a row's two nearest
+    centroids over all its assignment steps)."""
     data = np.asarray(data).astype(np.int64)
     nrows, ncols = data.shape
     kmax = max(2, max(ks))
-    seeds = [rs.choice(nrows, n, replace=False) for _ in range(RESTARTS)]
+    cen = np.zeros((n, ncols, kmax))
+    for c in range(n):
+        for p in range(ncols):
+            cen[c, p, data[seed[c], p]] = 1.0
+    labels, gap = None, np.inf
+    for it in range(MAX_ITER):
+        dist = np.stack([sq_dist(data, ks, cen[c]) for c in range(n)], axis=1)
+        new = np.argmin(dist, axis=1)                    # (the first minimum: ties to the lower index)
+        if n > 1:
+            two = np.sort(dist, axis=1)[:, :2]
+            gap = min(gap, float(np.min((two[:, 1] - two[:, 0]) / np.maximum(two[:, 1], 1e-300))))
+        same = labels is not None and np.array_equal(new, labels)
+        labels = new
+        if same or it == MAX_ITER - 1:
+            break
+        for c in range(n):
+            rows = data[labels == c]
+            if len(rows) == 0:
+                continue
+            for p in range(ncols):
+                cen[c, p, :] = np.bincount(rows[:, p], minlength=kmax).astype(np.float64) / float(len(rows))
+    own = np.zeros(nrows)
+    for c in range(n):
+        own[labels == c] = sq_dist(data[labels == c], ks, cen[c])
+    return labels, inertia_sum(own), np.bincount(labels, minlength=n), gap
+
+
+def kmeans(data, ks, rs, n=2, stats=None):
+    """Labels of the winning restart.  ``stats['gap']``: the smallest relative gap between a row's two nearest centroids
+    over all assignments of winning restarts."""
+    seeds = [rs.choice(len(data), n, replace=False) for _ in range(RESTARTS)]
     best = None
     for seed in seeds:
-        cen = np.zeros((n, ncols, kmax))
-        for c in range(n):
-            for p in range(ncols):
-                cen[c, p, data[seed[c], p]] = 1.0
-        labels, gap = None, np.inf
-        for it in range(MAX_ITER):
-            dist = np.stack([sq_dist(data, ks, cen[c]) for c in range(n)], axis=1)
-            new = np.argmin(dist, axis=1)                    # (the first minimum: ties to the lower index)
-            if n > 1:
-                two = np.sort(dist, axis=1)[:, :2]
-                gap = min(gap, float(np.min((two[:, 1] - two[:, 0]) / np.maximum(two[:, 1], 1e-300))))
-            same = labels is not None and np.array_equal(new, labels)
-            labels = new
-            if same or it == MAX_ITER - 1:
-                break
-            for c in range(n):
-                rows = data[labels == c]
-                if len(rows) == 0:
-                    continue
-                for p in range(ncols):
-                    cen[c, p, :] = np.bincount(rows[:, p], minlength=kmax).astype(np.float64) / float(len(rows))
-        own = np.zeros(nrows)
-        for c in range(n):
-            own[labels == c] = sq_dist(data[labels == c], ks, cen[c])
-        inertia = inertia_sum(own)
-        if best is None or inertia < best[0]:
-            best = (inertia, labels, gap)
+        run = kmeans_restart(data, ks, seed, n)
+        if best is None or run[1] < best[1]:
+            best = run
     if stats is not None:
-        stats['gap'] = min(stats.get('gap', np.inf), best[2])
-    return best[1]
+        stats['gap'] = min(stats.get('gap', np.inf), best[3])
+    return best[0]
+
+
+# ---- a k-means case without distance ties, for the device test of the k-means entries alone -------------------------------
+KMEANS_CASE_KS = [2, 2, 5, 3, 2]
+KMEANS_CASE_RESTARTS = 2
+#: n_clusters -> (rows, columns) of the three tasks of the generation: two 256-row blocks with a ragged second one,
+#: exactly one block, and a few rows; the column subsets differ and each holds a binary and a wider column
+KMEANS_CASE_TASKS = {c: [(300, [3, 0, 4, 2, 1]), (256, [2, 3, 1, 0]), (5 if c <= 5 else 8, [4, 2, 3])] for c in (1, 2, 8)}
+KMEANS_CASE_SEEDS = list(range(16))      # the table: per task, the first seed whose restated gap is >= 1e-6 is the fixture
+_kmeans_cases = {}
+
+
+def kmeans_case_task(n, cols, n_clusters, seed):
+    """(rows [n, 5] uint8, seeds [restarts, n_clusters] row positions) of one task, or None.  Discrete rows tie between
+    one-hot seeds, so the rows are picked: the seeds of the two restarts are rows of distinct values none of which is as
+    near to two seeds of the other restart, and the other rows are drawn from a mixture and kept if their nearest seed is
+    unique in both restarts.  That settles the first assignment step only; the caller checks the restated gap."""
+    rs, ks = np.random.RandomState(seed), np.asarray(KMEANS_CASE_KS)[cols]
+    pool, _ = mixture(KMEANS_CASE_KS, 4000, seed, n_clusters=max(3, n_clusters), noise=0.3)
+    cost = np.where(ks <= 2, 1, 2)
+
+    def tied(rows, seed_rows):
+        d = np.sort(((pool[rows][:, None, cols] != pool[seed_rows][None, :, cols]) * cost).sum(2), axis=1)
+        return d[:, 0] == d[:, 1] if n_clusters > 1 else np.zeros(len(rows), bool)
+
+    distinct = np.unique(pool[:, cols], axis=0, return_index=True)[1]
+    if len(distinct) < 2 * n_clusters:
+        return None
+    for _ in range(4000):
+        first, second = np.split(rs.permutation(distinct)[:2 * n_clusters], 2)
+        if n == n_clusters:
+            second = rs.permutation(first)
+        if not tied(first, second).any() and not tied(second, first).any():
+            break
+    else:
+        return None
+    seed_rows = np.unique(np.concatenate([first, second]))
+    others = np.setdiff1d(np.arange(len(pool)), seed_rows)
+    others = others[~tied(others, first) & ~tied(others, second)][:n - len(seed_rows)]
+    picked = rs.permutation(np.concatenate([seed_rows, others]))
+    if len(picked) != n:
+        return None
+    position = {int(r): i for i, r in enumerate(picked)}
+    return pool[picked], np.array([[position[int(r)] for r in restart] for restart in (first, second)])
+
+
+def kmeans_case(n_clusters):
+    """The fixture of one ``n_clusters``: ``(x uint8 [rows, 5], segments, tasks, want, gap)`` -- the matrix, the matrix rows
+    of each task (disjoint, unsorted, scattered over the matrix), per task ``(n, columns, seeds)``, per task and restart
+    ``kmeans_restart``'s result, and the smallest restated gap.  Built once; None if the seed table gives no such case."""
+    if n_clusters not in _kmeans_cases:
+        blocks, tasks, want = [], [], []
+        for n, cols in KMEANS_CASE_TASKS[n_clusters]:
+            for seed in KMEANS_CASE_SEEDS:
+                made = kmeans_case_task(n, cols, n_clusters, seed)
+                if made is None:
+                    continue
+                runs = [kmeans_restart(made[0][:, cols], [KMEANS_CASE_KS[c] for c in cols], s, n_clusters) for s in made[1]]
+                if min(run[3] for run in runs) >= 1e-6:
+                    break
+            else:
+                _kmeans_cases[n_clusters] = None
+                return None
+            blocks.append(made[0])
+            tasks.append((n, cols, made[1]))
+            want.append(runs)
+        stacked = np.concatenate(blocks)
+        where = np.random.RandomState(n_clusters).permutation(len(stacked))       # stacked row i is matrix row where[i]
+        x = np.empty_like(stacked)
+        x[where] = stacked
+        offs = np.concatenate([[0], np.cumsum([len(b) for b in blocks])])
+        segments = [where[offs[i]:offs[i + 1]] for i in range(len(blocks))]
+        _kmeans_cases[n_clusters] = (x, segments, tasks, want, min(run[3] for runs in want for run in runs))
+    return _kmeans_cases[n_clusters]
 
 
 # ---- leaves and the graph ------------------------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ def case():
                       rs.rand(N_ROWS)], axis=1).astype(np.float32)
         segs = [np.sort(rs.permutation(N_ROWS)[:n]) if i % 2 else rs.permutation(N_ROWS)[:n] for i, (n, _) in enumerate(TASKS)]
         offs = np.concatenate([[0], np.cumsum([len(s) for s in segs])])
-        data = L.DeviceDataF(torch.from_numpy(np.ascontiguousarray(x.T)).cuda().reshape(-1), N_ROWS, x.shape[1])
+        data = L.DeviceData(torch.from_numpy(np.ascontiguousarray(x.T)).cuda().reshape(-1), N_ROWS, x.shape[1])
         row_index = torch.from_numpy(np.concatenate(segs).astype(np.int32)).cuda()
         _cache['case'] = (x, data, row_index, segs, offs)
     return _cache['case']
@@ -102,20 +102,20 @@ def test_float_kmeans_against_the_restatement(n_clusters, pattern):
     for t, cols in KMEANS_TASKS[n_clusters]:
         n = TASKS[t][0]
         seeds = np.stack([rs.choice(n, n_clusters, replace=False) for _ in range(restarts)])
-        tasks.append((offs[t], n, cols, seeds))
+        tasks.append((offs[t], n, cols, None, seeds))
         local = x[segs[t]][:, cols].astype(np.float64)
         want.append([ref.kmeans_restart(local, seeds[r], n_clusters) for r in range(restarts)])
     gap = min(run[4] for runs in want for run in runs)
     assert gap >= 1e-9, 'the restated distances must have no ties'
     with contract(pattern, record=False) as c:
         c.frozen(data.x, row_index)
-        batch = L.KMeansBatchF(data, row_index, tasks, restarts, n_clusters)
+        batch = L.KMeansBatch(data, row_index, tasks, restarts, n_clusters)
         inertia, sizes, labels, iterations = batch.run()
         c.expect_written(labels, batch.cent)
         c.check()
     labels, cent = labels.cpu().numpy(), batch.cent.cpu().numpy()
     assert iterations >= 2 or n_clusters == 1
-    for i, (_, n, cols, _) in enumerate(tasks):
+    for i, (_, n, cols, _, _) in enumerate(tasks):
         for r in range(restarts):
             w_labels, w_cent, w_inertia, w_sizes, _ = want[i][r]
             assert np.array_equal(labels[r, batch.lab_off[i]:batch.lab_off[i] + n], w_labels), (i, r)

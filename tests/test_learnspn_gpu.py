@@ -143,6 +143,40 @@ def test_partition_rows_is_stable(pattern):
     assert np.array_equal(out.cpu().numpy(), want)
 
 
+@pytest.mark.parametrize('pattern', [0xFF, 0x7F])
+@pytest.mark.parametrize('n_clusters', sorted(ref.KMEANS_CASE_TASKS))
+def test_discrete_kmeans_against_the_restatement(n_clusters, pattern):
+    """``dpl_kmeans_*`` alone: one generation of three tasks (300, 256 and 5 or 8 rows) on one matrix with domain sizes
+    2, 2, 5, 3, 2 -- both branches of the distance, kmax = 5 above some K -- against ``kmeans_restart`` per restart.  The
+    case has no distance ties (tests/learnspn_ref.py:kmeans_case; test_learnspn_host.py asserts its gap >= 1e-6), so labels
+    and sizes are exact; the inertia is the same float64 sum in the same order, compared at the float test's 1e-12."""
+    from deeprob.hip import learn as L
+    assert max(ref.KMEANS_CASE_TASKS) == L.DPL_MAX_CLUSTERS
+    x, segments, tasks, want, _ = ref.kmeans_case(n_clusters)
+    ks = ref.KMEANS_CASE_KS
+    data = L.DeviceData(torch.from_numpy(np.ascontiguousarray(x.T)).cuda().reshape(-1), *x.shape)
+    row_index = torch.from_numpy(np.concatenate(segments).astype(np.int32)).cuda()
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in segments])])
+    with contract(pattern, record=False) as c:
+        c.frozen(data.x, row_index)
+        batch = L.KMeansBatch(data, row_index, [(offs[i], n, cols, [ks[col] for col in cols], seeds)
+                                                for i, (n, cols, seeds) in enumerate(tasks)],
+                              ref.KMEANS_CASE_RESTARTS, n_clusters, max(ks))
+        inertia, sizes, labels, iterations = batch.run()
+        c.expect_written(labels, batch.cent)
+        c.check()
+    labels = labels.cpu().numpy()
+    assert iterations >= 2 or n_clusters == 1
+    for i, (n, _, _) in enumerate(tasks):
+        for r in range(ref.KMEANS_CASE_RESTARTS):
+            w_labels, w_inertia, w_sizes, _ = want[i][r]
+            assert np.array_equal(labels[r, batch.lab_off[i]:batch.lab_off[i] + n], w_labels), (i, r)
+            assert np.array_equal(sizes[i, r], w_sizes), (i, r)
+            err = abs(inertia[i, r] - w_inertia) / (abs(w_inertia) if w_inertia else 1.0)
+            print('task', i, 'restart', r, 'inertia', inertia[i, r], 'restated', w_inertia, 'rel err', err)
+            assert err <= 1e-12, (i, r)
+
+
 # ---- the learned graphs ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('estimator', [False, True], ids=['learn_spn', 'learn_estimator'])
 @pytest.mark.parametrize('name', CONFIGS)

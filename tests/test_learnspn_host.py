@@ -94,6 +94,30 @@ def test_compute_data_domains_matches_golden():
     assert compute_data_domains(g['data'].astype(np.float32), dists) == json.loads(str(g['domains_json']))
 
 
+@pytest.mark.parametrize('n_clusters', sorted(ref.KMEANS_CASE_TASKS))
+def test_kmeans_case_meets_the_preconditions_of_the_device_test(n_clusters):
+    """The fixture of test_discrete_kmeans_against_the_restatement: the seed table gives a case for every task, every
+    restart's restated centroid gap is >= 1e-6, and the case has the shape that test relies on."""
+    from deeprob.hip import learn as L
+    assert sorted(ref.KMEANS_CASE_TASKS) == [1, 2, L.DPL_MAX_CLUSTERS]
+    case = ref.kmeans_case(n_clusters)
+    assert case is not None, 'no seed of the table has a centroid gap of 1e-6'
+    x, segments, tasks, want, gap = case
+    print('n_clusters', n_clusters, 'centroid gap', gap)
+    assert gap >= 1e-6 and all(run[3] >= 1e-6 for runs in want for run in runs)
+    ks = ref.KMEANS_CASE_KS
+    assert ks == [2, 2, 5, 3, 2] and x.dtype == np.uint8 and x.shape[1] == 5 and np.all(x < np.asarray(ks))
+    assert [n for n, _, _ in tasks] == [300, 256, 5 if n_clusters <= 5 else 8]
+    assert len(set(tuple(cols) for _, cols, _ in tasks)) == 3
+    rows = np.concatenate(segments)
+    assert len(np.unique(rows)) == len(rows)
+    for seg, (n, cols, seeds), runs in zip(segments, tasks, want):
+        assert len(seg) == n and not np.array_equal(seg, np.sort(seg)) and seg.max() - seg.min() >= n
+        assert cols != sorted(cols) and min(ks[c] for c in cols) <= 2 < max(ks[c] for c in cols)
+        assert seeds.shape == (ref.KMEANS_CASE_RESTARTS, n_clusters) and len(runs) == ref.KMEANS_CASE_RESTARTS
+        assert all(len(np.unique(s)) == n_clusters and s.max() < n for s in seeds)
+
+
 # ---- arguments ---------------------------------------------------------------------------------------------------------
 def _args():
     from deeprob.spn.structure.leaf import Bernoulli
