@@ -1,4 +1,4 @@
-// Top-down pass of a RAT-SPN in ONE launch: RatSpn.mpe and RatSpn.sample.
+// Top-down pass of a RAT-SPN in ONE launch: RatSpn.mpe, RatSpn.sample and RatSpn.sample_conditional.
 //
 // reference: deeprob/spn/models/ratspn.py:124-162 (mpe) and :164-182 (sample) -- a python loop over the layers, root to
 // leaves, each layer a handful of index operations on [B, groups] tensors: RootLayer.mpe / .sample
@@ -18,6 +18,23 @@
 // slot 1 = the root's choice, slot G + g = the choice of region g (of G) of a sum level, slots 2^depth + 2 f, + 1 = the two
 // uniforms of variable f's leaf (Box-Muller: z = sqrt(-2 log(1 - u1)) cos(2 pi u2); Bernoulli: u1 < p).  A categorical
 // choice is the inverse CDF over exp(log-softmax weights) in index order.
+//
+// Mode 2 (RatSpn.sample_conditional; no counterpart in the reference's tensorized model, the node-graph sampler draws the
+// same way) draws every sum node's input from the exact posterior under the evidence, in its own instance of the kernel
+// (ratspn_topdown_kernel<true>; modes 0 / 1 run the instance <false>, whose instructions are those of the untemplated
+// kernel).  One node among
+// `count` inputs:
+//   1. s(n) = fl(fl(a_i + a_j) + lw(n)): the scores of mode 0, fp32, the same operand order;
+//   2. m = max_n s(n) over the wave (exact; a NaN score makes m NaN);
+//   3. m = -inf or NaN (no input is possible under this evidence): the choice of mode 1 for this node, by the bare weights;
+//   4. otherwise e(n) = expf(s(n) - m) (scores of a 784-variable model sit near -1000, where expf(s(n)) is 0 for every n)
+//      and the inverse CDF of mode 1 with e(n) in place of expf(lw(n)): the same contiguous lane chunks, in-order sums in a
+//      chunk, the same __shfl_up scan, target = u * total, the first n with target < c, the last input when rounding leaves
+//      none;
+//   5. u from the counter slots of mode 1, unchanged (the two uniforms of an observed variable are not used).
+// The scores are recomputed for every pass over them (maximum, chunk sums, the owner lane's rescan) rather than kept: the
+// activations of one sample are a few KiB, hot in L1 / L2 after the first pass, and a count of 2048 would need 32 registers a
+// lane.  The leaves are those of mode 1 with the observed x[b, f] kept.
 #include "common.h"
 #include <math.h>
 #include <algorithm>
@@ -27,12 +44,12 @@ namespace dpk {
 constexpr int kTdMaxDepth = 10;      // 2^depth <= in_features (RegionGraph): 784 variables allow depth 9
 
 struct TopDownArgs {
-    int mode, dist;                  // 0 = mpe, 1 = sample; 0 = Gaussian, 1 = Bernoulli leaves
+    int mode, dist;                  // 0 = mpe, 1 = sample, 2 = posterior sample; 0 = Gaussian, 1 = Bernoulli leaves
     int64_t B;
     int D, depth, reps, I, S, C, d;
     const float *x;                  // [B, D] evidence, NaN = to be completed; null: nothing observed
     const int64_t *y;                // [B] class of the root to descend from; null: class 0
-    const float *act[kTdMaxDepth];   // [0] leaf layer output [B, reps 2^depth, I]; [t] sum level t output [B, reps 2^(depth-t), S]  (mpe)
+    const float *act[kTdMaxDepth];   // [0] leaf layer output [B, reps 2^depth, I]; [t] sum level t output [B, reps 2^(depth-t), S]  (modes 0, 2)
     const float *logw[kTdMaxDepth + 1];   // [t], 1 <= t < depth: log_softmax of sum level t's weight [P_t, S, N^2]; [depth]: root [C, reps N^2]
     const int *src;                  // [reps, D]: position (region within the repetition) * d + j holding variable f
     const float *p0, *p1;            // leaf parameters [reps 2^depth, I, d]: loc, scale / logits, null
@@ -61,28 +78,23 @@ __device__ __forceinline__ void wave_argmax(float &v, int &n) {
     }
 }
 
-// One node's choice among `count` inputs: value(n) = its score (mpe) / its log-weight (sample).  Returns the chosen n in
-// every lane.
-template <typename ScoreFn, typename LogwFn>
-__device__ __forceinline__ int td_choose(int mode, int count, int lane, float u, ScoreFn score, LogwFn logw) {
-    if (mode == 0) {
-        float bv = -INFINITY;
-        int bn = 0x7fffffff;
-        for (int n = lane; n < count; n += 64) {
-            const float v = score(n);
-            if (bn == 0x7fffffff || v > bv) {
-                bv = v;
-                bn = n;
-            }
-        }
-        wave_argmax(bv, bn);
-        return bn;
+// NaN-propagating maximum over the wave (mode 2: an impossible or undefined node must be seen, not skipped)
+__device__ __forceinline__ float wave_max_nan(float m) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float t = __shfl_xor(m, o, 64);
+        m = (t > m || t != t) ? t : m;
     }
-    // inverse CDF in index order: lane l owns the contiguous chunk [l ch, (l + 1) ch)
+    return m;
+}
+
+// inverse CDF in index order over the non-negative weight(n): lane l owns the contiguous chunk [l ch, (l + 1) ch)
+template <typename WeightFn>
+__device__ __forceinline__ int td_inverse_cdf(int count, int lane, float u, WeightFn weight) {
     const int ch = (count + 63) / 64;
     const int n0 = min(lane * ch, count), n1 = min(n0 + ch, count);
     float s = 0.f;
-    for (int n = n0; n < n1; ++n) s += expf(logw(n));
+    for (int n = n0; n < n1; ++n) s += weight(n);
     float inc = s;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -99,7 +111,7 @@ __device__ __forceinline__ int td_choose(int mode, int count, int lane, float u,
         if (lane == owner) {
             float c = inc - s;
             for (int n = n0; n < n1; ++n) {
-                c += expf(logw(n));
+                c += weight(n);
                 if (target < c) {
                     mine = n;
                     break;
@@ -111,6 +123,38 @@ __device__ __forceinline__ int td_choose(int mode, int count, int lane, float u,
     return pick;
 }
 
+// One node's choice among `count` inputs: value(n) = its score (mpe) / its log-weight (sample) / its score relative to the
+// best one (POSTERIOR, the kernel of mode 2).  Returns the chosen n in every lane.
+template <bool POSTERIOR, typename ScoreFn, typename LogwFn>
+__device__ __forceinline__ int td_choose(int mode, int count, int lane, float u, ScoreFn score, LogwFn logw) {
+    if (!POSTERIOR && mode == 0) {
+        float bv = -INFINITY;
+        int bn = 0x7fffffff;
+        for (int n = lane; n < count; n += 64) {
+            const float v = score(n);
+            if (bn == 0x7fffffff || v > bv) {
+                bv = v;
+                bn = n;
+            }
+        }
+        wave_argmax(bv, bn);
+        return bn;
+    }
+    if (POSTERIOR) {
+        float m = -INFINITY;
+        for (int n = lane; n < count; n += 64) {
+            const float v = score(n);
+            m = (v > m || v != v) ? v : m;
+        }
+        m = wave_max_nan(m);
+        // (wave-uniform; false for -inf and for NaN: then the bare weights below)
+        if (m > -INFINITY) return td_inverse_cdf(count, lane, u, [&](int n) { return expf(score(n) - m); });
+    }
+    return td_inverse_cdf(count, lane, u, [&](int n) { return expf(logw(n)); });
+}
+
+// POSTERIOR = false: modes 0 and 1; true: mode 2
+template <bool POSTERIOR>
 __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a) {
     extern __shared__ int td_nodes[];               // [wave][2][2^depth]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -129,7 +173,7 @@ __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a
             const int N = t == 0 ? a.I : a.S, NN = N * N, R = 2 * a.reps;
             const float *A = a.act[t] ? a.act[t] + b * (int64_t)R * N : nullptr;
             const float *lw = a.logw[a.depth] + (int64_t)cls * a.reps * NN;
-            const int n = td_choose(
+            const int n = td_choose<POSTERIOR>(
                 a.mode, a.reps * NN, lane, a.mode ? td_uniform(a.seed, ctr0 + 1) : 0.f,
                 [&](int q) {
                     const int p = q / NN, e = q - p * NN, i = e / N, j = e - i * N;
@@ -154,7 +198,7 @@ __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a
             for (int gl = 0; gl < G; ++gl) {
                 const int g = rep * G + gl, o = cur[gl];
                 const float *lw = a.logw[t] + ((int64_t)g * a.S + o) * NN;
-                const int n = td_choose(
+                const int n = td_choose<POSTERIOR>(
                     a.mode, NN, lane, a.mode ? td_uniform(a.seed, ctr0 + (unsigned long long)(G + gl)) : 0.f,
                     [&](int q) {
                         const int i = q / N, j = q - i * N;
@@ -217,18 +261,18 @@ extern "C" int dpk_ratspn_topdown(int32_t mode, int32_t dist, int64_t B, int32_t
                                   const float *const *act, const float *const *logw, const int32_t *src,
                                   const float *p0, const float *p1, uint64_t seed, float *out, int32_t *choice,
                                   void *stream) {
-    DPK_REQUIRE(mode == 0 || mode == 1, DPK_EINVAL, "ratspn_topdown: mode %d", mode);
+    DPK_REQUIRE(mode >= 0 && mode <= 2, DPK_EINVAL, "ratspn_topdown: mode %d", mode);
     DPK_REQUIRE(dist == 0 || dist == 1, DPK_EINVAL, "ratspn_topdown: dist %d", dist);
     DPK_REQUIRE(B >= 0 && D > 0 && depth >= 1 && depth <= kTdMaxDepth && reps > 0 && I > 0 && S > 0 && C > 0 && d > 0,
                 DPK_EINVAL, "ratspn_topdown: bad sizes");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(logw && src && p0 && out && (dist == 1 || mode == 0 || p1), DPK_EINVAL, "ratspn_topdown: null pointer");
-    DPK_REQUIRE(mode == 1 || act, DPK_EINVAL, "ratspn_topdown: mpe needs the bottom-up activations");
+    DPK_REQUIRE(mode == 1 || act, DPK_EINVAL, "ratspn_topdown: modes 0 and 2 need the bottom-up activations");
     TopDownArgs a{};
     a.mode = mode; a.dist = dist; a.B = B; a.D = D; a.depth = depth; a.reps = reps; a.I = I; a.S = S; a.C = C; a.d = d;
     a.x = x; a.y = y; a.src = src; a.p0 = p0; a.p1 = p1; a.seed = seed; a.out = out; a.choice = choice;
     for (int t = 0; t < depth; ++t) {
-        a.act[t] = (mode == 0) ? act[t] : nullptr;
+        a.act[t] = (mode != 1) ? act[t] : nullptr;
         DPK_REQUIRE(mode == 1 || a.act[t], DPK_EINVAL, "ratspn_topdown: activations of level %d missing", t);
     }
     for (int t = 1; t <= depth; ++t) {
@@ -238,7 +282,12 @@ extern "C" int dpk_ratspn_topdown(int32_t mode, int32_t dist, int64_t B, int32_t
     const size_t lds = (size_t)4 * 2 * ((size_t)1 << depth) * sizeof(int);
     const int64_t groups = (B + 3) / 4;
     const unsigned grid = (unsigned)std::min<int64_t>(groups, (int64_t)device_cus() * 16);
-    DPK_LAUNCH(ratspn_topdown_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-    DPK_CHECK_LAUNCH("ratspn_topdown_kernel");
+    if (mode == 2) {
+        DPK_LAUNCH(ratspn_topdown_kernel<true>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        DPK_CHECK_LAUNCH("ratspn_topdown_kernel<true>");
+    } else {
+        DPK_LAUNCH(ratspn_topdown_kernel<false>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+        DPK_CHECK_LAUNCH("ratspn_topdown_kernel<false>");
+    }
     return DPK_OK;
 }

@@ -608,9 +608,10 @@ def ratspn_topdown(mode: int, dist: int, n_samples: int, lctx: LeafContext, x: O
                    acts, logws, src: torch.Tensor, p0: torch.Tensor, p1: Optional[torch.Tensor], seed: int = 0,
                    want_choice: bool = False):
     """RatSpn.mpe (mode 0) / RatSpn.sample (mode 1) top-down in one launch (reference: deeprob/spn/models/ratspn.py:124-182
-    and the layers' mpe / sample methods).  ``acts``: [leaf output, sum level 1 output, ...] (mode 0); ``logws``: log-softmax
-    weights of the sum levels 1 .. depth-1, then of the root.  Returns the completed / generated ``[B, D]`` tensor (and the
-    ``[B, 1 + 2^depth]`` choices when asked)."""
+    and the layers' mpe / sample methods), and RatSpn.sample_conditional (mode 2: ``x``, ``acts`` and ``seed`` together -- every
+    sum input drawn in proportion to weight * value under the evidence).  ``acts``: [leaf output, sum level 1 output, ...]
+    (modes 0 and 2); ``logws``: log-softmax weights of the sum levels 1 .. depth-1, then of the root.  Returns the completed /
+    generated ``[B, D]`` tensor (and the ``[B, 1 + 2^depth]`` choices when asked)."""
     import ctypes
     lib = load_library()
     depth = lctx.depth
@@ -624,7 +625,7 @@ def ratspn_topdown(mode: int, dist: int, n_samples: int, lctx: LeafContext, x: O
         return t
 
     act_arr = (ctypes.c_void_p * depth)()
-    if mode == 0:
+    if mode != 1:
         if len(acts) != depth:
             raise ValueError('ratspn_topdown: %d activation tensors for depth %d' % (len(acts), depth))
         for t, a in enumerate(acts):

@@ -346,6 +346,37 @@ class RatSpn(ProbabilisticModel):
                                   self._topdown_src(), p0, p1, seed=ops.draw_seed() if seed is None else int(seed))
 
     @torch.no_grad()
+    def sample_conditional(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, seed: Optional[int] = None) -> torch.Tensor:
+        """One exact draw from p(x_missing | x_observed, y) per row: the NaN entries of ``x`` are drawn, the observed ones are
+        returned as they are (the node-graph path's ``sampling.sample(root, x)`` for the tensorized model; the reference has
+        no counterpart).  The bottom-up pass of ``mpe``, then one top-down launch that draws every sum node's input in
+        proportion to weight * value of the input under the evidence.  Without labels the class of a row is drawn from
+        softmax(root outputs) (uniform class prior, as ``sample`` assumes) by ``torch.multinomial``, i.e. torch's generator;
+        ``seed`` fixes the kernel's counter-based draws: a row's draws depend on (seed, row index) and its evidence only."""
+        leaf = self._leaf_params()
+        if leaf is None:
+            raise NotImplementedError('sample_conditional: a user-defined leaf layer ({}) has no one-launch top-down pass'
+                                      .format(type(self.base_layer).__name__))
+        if self.training and (self.in_dropout is not None or self.sum_dropout is not None):
+            raise NotImplementedError('sample_conditional: training mode with in_dropout / sum_dropout set '
+                                      '(call eval() first: the posterior is that of the model without dropout)')
+        x = ops.require_device_f32(x, 'x')
+        acts = self._upward_for_mpe(x)
+        if self.out_classes == 1 or x.shape[0] == 0:
+            y = None
+        elif y is None:
+            top = ops.prodroot_forward(acts[-1], self.root_layer.weight, self.root_layer._ws)
+            if top is None:
+                top = self.root_layer(self.layers[-1](acts[-1]))
+            post = torch.softmax(top, dim=1)
+            # (evidence impossible under every class: softmax gives NaN; such a row takes its class uniformly)
+            post = torch.where(torch.isfinite(post).all(dim=1, keepdim=True), post, torch.full_like(post, 1.0 / self.out_classes))
+            y = torch.multinomial(post, 1).squeeze(1)
+        dist, p0, p1 = leaf
+        return ops.ratspn_topdown(2, dist, x.shape[0], self._fused_ctx, x, y, acts, self._topdown_logw(),
+                                  self._topdown_src(), p0, p1, seed=ops.draw_seed() if seed is None else int(seed))
+
+    @torch.no_grad()
     def _mpe_layerwise(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The layer-by-layer form (user-defined leaf layers, training-mode dropout): the layers' own ``mpe`` methods."""
         evidence = x
