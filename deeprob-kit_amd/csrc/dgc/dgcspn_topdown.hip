@@ -1,0 +1,394 @@
+// Top-down pass of a DGC-SPN in ONE launch: DgcSpn.sample (mode 1) and DgcSpn.sample_conditional (mode 2).
+//
+// reference: deeprob/spn/models/dgcspn.py raises NotImplementedError in `sample` and has no conditional sampler; the
+// circuit is the one its forward evaluates (SpatialGaussianLayer, SpatialProductLayer, SpatialSumLayer, SpatialRootLayer of
+// deeprob/spn/layers/dgcspn.py).  Every root input (c, h, w) is a product that reaches every pixel at most once through the
+// dilated 2x2 windows, so an ancestral draw is well defined; it needs one chosen-channel-or-none map per level.
+//
+// The pass.  Inputs, all fp32 NCHW on the device: the evidence x [B, C, H, W] (NaN = to be drawn; null = everything is
+// drawn), act[0] = the leaf layer's output [B, K, H, W], act[t] = the output of the t-th SpatialSumLayer, logw[t] = the
+// log_softmax(weight, 1) of that sum layer, the root's log_softmax(weight, 1) [classes, Cr Hr Wr], y [B] int64 (null =
+// class 0), the leaf loc / scale [K, C, H, W], and the geometry of every product level j = 0 .. L-1 (in and out shape, the
+// four pads, stride, dilation, the depthwise flag; include/deeprob_dgc.h).  Sum layer t sits on product level t - 1.
+//
+// Product maps are never materialised.  A product value is formed where it is needed as the fp32 sum of its four taps in
+// row-major tap order (th, tw): ((v0 + v1) + v2) + v3.
+//   - The input coordinate of a tap is out * stride + t * dilation - pad_before.
+//   - A tap outside [0, in) contributes 0 and has no child.
+//   - A depthwise level reads channel oc at every tap; any other level decodes the output channel in itertools.product
+//     order: tap t = 2 th + tw gets digit (oc / Cin^(3 - t)) % Cin.
+//
+// Per sample, top to bottom:
+//   Root.  s(i) = prod_value_{L-1}(i) + logw_root[y, i] for i over the flattened last product map (c, h, w).  One i is drawn
+//     by inverse CDF over exp(s - max s) in index order.  It activates its taps: position (ih, iw) of the map of sum layer
+//     L - 1 with the tap's channel.
+//   Every sum layer t = L-1 .. 1.  Each active position (o, h, w) draws its input channel c by inverse CDF over
+//     exp(s - max), s(c) = prod_value_{t-1}(c, h, w) + logw[t][o, c, h, w] (fp32, this operand order).
+//     If the maximum is -inf or NaN the draw is by the bare weights, the inverse CDF over exp(logw) (step 3 of the RAT-SPN
+//     definition, csrc/ratspn_topdown.hip).  The chosen product activates its taps with the decoded channels, in the map
+//     of sum layer t - 1, or for t = 1 in the leaf map.
+//   Leaves.  A pixel (h, w) reached with component k treats each of its C input channels separately: an observed entry is
+//     copied bit for bit, a NaN entry is loc[k, c, h, w] + scale[k, c, h, w] * z with z = sqrt(-2 log(1 - u1)) cos(2 pi u2)
+//     (Box-Muller from two counter-based uniforms, as in csrc/ratspn_topdown.hip).
+//   Pixels out of scope.  A pixel that no path reaches (a 'valid' stride-2 level of an odd map drops its last row and column)
+//     is returned as given: its evidence value, or NaN when everything is drawn; its entry of `choice` is -1.
+//   Inverse CDF.  target = u * total, the first n with target < c(n) in index order, the last input when rounding leaves
+//     none; total and c(n) are fp32 sums in index order (a node of more than 64 inputs: the wave scan of
+//     csrc/ratspn_topdown.hip, in-order sums in contiguous lane chunks, then a scan over the lanes).
+//   Draws.  u(ctr) = the library's counter-based uniform td_uniform(seed, ctr), ctr = row * slots_per_row + slot; slot 0 is
+//     the root's, slot base_t + h * Wout_{t-1} + w that of sum layer t at (h, w) (base_1 = 1, base_{t+1} = base_t +
+//     Hout_{t-1} Wout_{t-1}), slots base_L + 2 ((c H + h) W + w), + 1 the two uniforms of leaf entry (c, h, w).  A row's
+//     output depends on (seed, row index, y) and its evidence only.
+//   Mode 1 (no evidence) takes every activation as log 1: act == null, every draw is by the bare weights, no bottom-up pass.
+//
+// Shape of the kernel: one work-group of 256 threads per sample, grid-stride over samples.  The state between two levels is
+// the list of the active positions of a map with their channels, (channel << 16 | position) -- the chosen-channel map in
+// sparse form: an active node of a decomposable circuit owns at least one pixel, so a list never holds more than
+// min(positions of the map, 4^(levels above)) entries.  Two lists ping-pong in LDS, appended to through one LDS counter per
+// level (integer atomics; the order of a list does not matter: a node's draw depends on its own position's counter only),
+// one barrier per level.  A node of at most 64 inputs is one lane's loop; a wider one (a non-depthwise level has Cin^4
+// inputs, the root Cr Hr Wr) is scanned by a wave.  The scores are recomputed for every pass over them rather than kept:
+// one sample's maps are a few KiB, hot in L1 / L2 after the first pass, and nothing is indexed dynamically in registers.
+#include "dgc_common.h"
+#include <algorithm>
+
+namespace dpg_detail {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kWide = 64;            // a node of more inputs than this is scanned by a wave
+
+struct Level {
+    int cin, hin, win, cout, hout, wout, pl, pt, stride, dil, dw;
+    int cin2, cin3;                  // Cin^2, Cin^3 (channel decode of a level that is not depthwise)
+};
+
+struct TopDownArgs {
+    int64_t B;
+    int C, H, W, K, L, classes, cap;
+    Level lv[DPG_MAX_LEVELS];
+    const float *x;
+    const int64_t *y;
+    const float *act[DPG_MAX_LEVELS];
+    const float *logw[DPG_MAX_LEVELS + 1];
+    const float *loc, *scale;
+    unsigned long long seed, slots;
+    unsigned base[DPG_MAX_LEVELS + 1];   // [t], 1 <= t < L: first slot of sum layer t; [L]: first leaf slot
+    float *out;
+    int *choice;
+};
+
+__device__ __forceinline__ int tap_channel(const Level &g, int oc, int t) {
+    if (g.dw) return oc;
+    const int q = t == 0 ? oc / g.cin3 : t == 1 ? oc / g.cin2 : t == 2 ? oc / g.cin : oc;
+    return q % g.cin;
+}
+
+// fp32 value of product (oc, oh, ow) of level g over the sample's input map A [Cin, Hin, Win]: ((v0 + v1) + v2) + v3
+__device__ __forceinline__ float prod_value(const Level &g, const float *A, int oc, int oh, int ow) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int ih = oh * g.stride + (t >> 1) * g.dil - g.pt, iw = ow * g.stride + (t & 1) * g.dil - g.pl;
+        float v = 0.f;
+        if ((unsigned)ih < (unsigned)g.hin && (unsigned)iw < (unsigned)g.win)
+            v = A[((int64_t)tap_channel(g, oc, t) * g.hin + ih) * g.win + iw];
+        s = t == 0 ? v : s + v;
+    }
+    return s;
+}
+
+// the taps of product (oc, oh, ow) inside the input map join the list of the level below
+__device__ __forceinline__ void activate(const Level &g, int oc, int oh, int ow, int *list, int *count, int cap) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int ih = oh * g.stride + (t >> 1) * g.dil - g.pt, iw = ow * g.stride + (t & 1) * g.dil - g.pl;
+        if ((unsigned)ih < (unsigned)g.hin && (unsigned)iw < (unsigned)g.win) {
+            const int k = atomicAdd(count, 1);
+            // (k >= cap cannot happen in a decomposable circuit; a table that describes none must not write past the list)
+            if (k < cap) list[k] = (tap_channel(g, oc, t) << 16) | (ih * g.win + iw);
+        }
+    }
+}
+
+// NaN-propagating maximum over the wave (an impossible or undefined node must be seen, not skipped)
+__device__ __forceinline__ float wave_max_nan(float m) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float t = __shfl_xor(m, o, 64);
+        m = (t > m || t != t) ? t : m;
+    }
+    return m;
+}
+
+// inverse CDF in index order over the non-negative weight(n), by a wave: lane l owns the contiguous chunk [l ch, (l + 1) ch)
+template <typename WeightFn>
+__device__ __forceinline__ int wave_inverse_cdf(int count, int lane, float u, WeightFn weight) {
+    const int ch = (count + 63) / 64;
+    const int n0 = min(lane * ch, count), n1 = min(n0 + ch, count);
+    float s = 0.f;
+    for (int n = n0; n < n1; ++n) s += weight(n);
+    float inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    const float total = __shfl(inc, 63, 64);
+    const float target = u * total;
+    const unsigned long long hit = __ballot(target < inc && n1 > n0);
+    int pick = count - 1;                          // (target >= total by rounding: the last input)
+    if (hit != 0ull) {
+        const int owner = __ffsll((long long)hit) - 1;
+        int mine = n1 - 1;
+        if (lane == owner) {
+            float c = inc - s;
+            for (int n = n0; n < n1; ++n) {
+                c += weight(n);
+                if (target < c) {
+                    mine = n;
+                    break;
+                }
+            }
+        }
+        pick = __shfl(mine, owner, 64);
+    }
+    return pick;
+}
+
+// the same by one lane
+template <typename WeightFn>
+__device__ __forceinline__ int lane_inverse_cdf(int count, float u, WeightFn weight) {
+    float total = 0.f;
+    for (int n = 0; n < count; ++n) total += weight(n);
+    const float target = u * total;
+    float c = 0.f;
+    for (int n = 0; n < count; ++n) {
+        c += weight(n);
+        if (target < c) return n;
+    }
+    return count - 1;
+}
+
+// One node's draw among `count` inputs, by a wave (every lane returns the pick) or by one lane.
+template <bool POSTERIOR, typename ScoreFn, typename LogwFn>
+__device__ __forceinline__ int wave_choose(int count, int lane, float u, ScoreFn score, LogwFn logw) {
+    if (POSTERIOR) {
+        float m = -INFINITY;
+        for (int n = lane; n < count; n += 64) {
+            const float v = score(n);
+            m = (v > m || v != v) ? v : m;
+        }
+        m = wave_max_nan(m);
+        // (wave-uniform; false for -inf and for NaN: then the bare weights below)
+        if (m > -INFINITY) return wave_inverse_cdf(count, lane, u, [&](int n) { return expf(score(n) - m); });
+    }
+    return wave_inverse_cdf(count, lane, u, [&](int n) { return expf(logw(n)); });
+}
+
+template <bool POSTERIOR, typename ScoreFn, typename LogwFn>
+__device__ __forceinline__ int lane_choose(int count, float u, ScoreFn score, LogwFn logw) {
+    if (POSTERIOR) {
+        float m = -INFINITY;
+        for (int n = 0; n < count; ++n) {
+            const float v = score(n);
+            m = (v > m || v != v) ? v : m;         // (once NaN, m stays NaN)
+        }
+        if (m > -INFINITY) return lane_inverse_cdf(count, u, [&](int n) { return expf(score(n) - m); });
+    }
+    return lane_inverse_cdf(count, u, [&](int n) { return expf(logw(n)); });
+}
+
+// POSTERIOR = false: mode 1 (act is not read); true: mode 2
+template <bool POSTERIOR>
+__global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownArgs a) {
+    extern __shared__ int td_lists[];               // [2][cap]
+    __shared__ int td_count[DPG_MAX_LEVELS];        // entries of the list of map j (the input map of product level j)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int HW = a.H * a.W, CHW = a.C * HW, L = a.L, cap = a.cap;
+    for (int64_t b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const unsigned long long ctr0 = (unsigned long long)b * a.slots;
+        float *out = a.out + b * CHW;
+        const float *x = a.x ? a.x + b * CHW : nullptr;
+        int *choice = a.choice ? a.choice + b * (int64_t)(1 + HW) : nullptr;
+        // ---- every pixel as given (out of scope until a path reaches it), every list empty ----
+        for (int i = tid; i < CHW; i += kThreads) out[i] = x ? x[i] : NAN;
+        if (choice != nullptr)
+            for (int i = tid; i < HW; i += kThreads) choice[1 + i] = -1;
+        if (tid < L) td_count[tid] = 0;
+        int *cur = td_lists, *nxt = td_lists + cap;
+        __syncthreads();
+        // ---- root: one of the Cr Hr Wr products of the last level, by wave 0 ----
+        if (wave == 0) {
+            const Level &g = a.lv[L - 1];
+            const int hw = g.hout * g.wout, count = g.cout * hw;
+            // (a label outside [0, classes) is clamped: a kernel cannot raise, and must not read past the table)
+            const int cls = a.y ? min(max((int)a.y[b], 0), a.classes - 1) : 0;
+            const float *A = POSTERIOR ? a.act[L - 1] + b * ((int64_t)g.cin * g.hin * g.win) : nullptr;
+            const float *lw = a.logw[L] + (int64_t)cls * count;
+            const int n = wave_choose<POSTERIOR>(
+                count, lane, td_uniform(a.seed, ctr0),
+                [&](int q) {
+                    const int oc = q / hw, p = q - oc * hw, oh = p / g.wout;
+                    return prod_value(g, A, oc, oh, p - oh * g.wout) + lw[q];
+                },
+                [&](int q) { return lw[q]; });
+            if (lane == 0) {
+                if (choice != nullptr) choice[0] = n;
+                const int oc = n / hw, p = n - oc * hw, oh = p / g.wout;
+                activate(g, oc, oh, p - oh * g.wout, cur, &td_count[L - 1], cap);
+            }
+        }
+        __syncthreads();
+        // ---- sum layers, top to bottom: layer t sits on product level t - 1, its active positions are list t ----
+        for (int t = L - 1; t >= 1; --t) {
+            const Level &g = a.lv[t - 1];
+            const int hw = g.hout * g.wout, count = g.cout;
+            const int ncur = min(td_count[t], cap);
+            const float *A = POSTERIOR ? a.act[t - 1] + b * ((int64_t)g.cin * g.hin * g.win) : nullptr;
+            const unsigned long long ctr = ctr0 + a.base[t];
+            if (count > kWide) {
+                for (int e = wave; e < ncur; e += kWaves) {
+                    const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
+                    const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
+                    const int c = wave_choose<POSTERIOR>(
+                        count, lane, td_uniform(a.seed, ctr + (unsigned)p),
+                        [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
+                        [&](int n) { return lw[(int64_t)n * hw]; });
+                    if (lane == 0) activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
+                }
+            } else {
+                for (int e = tid; e < ncur; e += kThreads) {
+                    const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
+                    const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
+                    const int c = lane_choose<POSTERIOR>(
+                        count, td_uniform(a.seed, ctr + (unsigned)p),
+                        [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
+                        [&](int n) { return lw[(int64_t)n * hw]; });
+                    activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
+                }
+            }
+            __syncthreads();
+            int *sw = cur;
+            cur = nxt;
+            nxt = sw;
+        }
+        // ---- leaves: every reached pixel from its component, channel by channel ----
+        const int n0 = min(td_count[0], cap);
+        for (int e = tid; e < n0; e += kThreads) {
+            const int pk = cur[e], p = pk & 0xffff, k = pk >> 16;
+            if (choice != nullptr) choice[1 + p] = k;
+            for (int c = 0; c < a.C; ++c) {
+                const int f = c * HW + p;
+                const float xv = x ? x[f] : NAN;
+                if (xv != xv) {
+                    const int64_t po = (int64_t)k * CHW + f;
+                    const unsigned long long slot = ctr0 + a.base[L] + 2ull * (unsigned long long)f;
+                    const float u1 = td_uniform(a.seed, slot), u2 = td_uniform(a.seed, slot + 1ull);
+                    const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.28318530717958647692f * u2);
+                    out[f] = fmaf(a.scale[po], z, a.loc[po]);
+                }
+            }
+        }
+        // (the lists and their counters are rewritten only after every thread has passed the reads above)
+        __syncthreads();
+    }
+}
+
+int cus() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+}
+
+}  // namespace dpg_detail
+
+using namespace dpg_detail;
+
+extern "C" const char *dpg_last_error(void) { return g_error; }
+
+extern "C" int dpg_abi_version(void) { return 1; }
+
+extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H, int32_t W, int32_t K, int32_t n_levels,
+                                  const int32_t *geom, int32_t classes, const float *x, const int64_t *y,
+                                  const float *const *act, const float *const *logw, const float *loc, const float *scale,
+                                  uint64_t seed, float *out, int32_t *choice, void *stream) {
+    DPG_REQUIRE(mode == DPG_MODE_PRIOR || mode == DPG_MODE_POSTERIOR, "dpg_dgcspn_topdown: mode %d", mode);
+    DPG_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && K > 0 && classes > 0, "dpg_dgcspn_topdown: bad sizes");
+    DPG_REQUIRE(n_levels >= 1 && n_levels <= DPG_MAX_LEVELS, "dpg_dgcspn_topdown: %d levels are outside 1..%d", n_levels,
+                DPG_MAX_LEVELS);
+    DPG_REQUIRE(geom != nullptr && logw != nullptr, "dpg_dgcspn_topdown: null table");
+    DPG_REQUIRE((int64_t)C * H * W <= (1 << 28), "dpg_dgcspn_topdown: an image of more than 2^28 entries");
+    TopDownArgs a{};
+    a.B = B; a.C = C; a.H = H; a.W = W; a.K = K; a.L = n_levels; a.classes = classes;
+    a.x = mode == DPG_MODE_POSTERIOR ? x : nullptr;
+    a.y = y; a.loc = loc; a.scale = scale; a.seed = seed; a.out = out; a.choice = choice;
+    int64_t cap = 4, slots = 1;
+    for (int j = 0; j < n_levels; ++j) {
+        const int32_t *r = geom + (size_t)j * DPG_GEOM_INTS;
+        Level &g = a.lv[j];
+        g.cin = r[0]; g.hin = r[1]; g.win = r[2]; g.cout = r[3]; g.hout = r[4]; g.wout = r[5];
+        g.pl = r[6]; g.pt = r[8]; g.stride = r[10]; g.dil = r[11]; g.dw = r[12] != 0;
+        DPG_REQUIRE(g.cin >= 1 && g.cin <= 32767 && g.hin >= 1 && g.win >= 1 && (int64_t)g.hin * g.win <= 65535 &&
+                        g.hout >= 1 && g.wout >= 1 && (int64_t)g.hout * g.wout <= 65535 && g.stride >= 1 && g.stride <= 65535 && g.dil >= 1 &&
+                        g.dil <= 65535,
+                    "dpg_dgcspn_topdown: level %d: sizes out of domain", j);
+        // (with these bounds out * stride + dilation - pad stays far inside int)
+        for (int q = 6; q < 10; ++q)
+            DPG_REQUIRE(r[q] >= -65535 && r[q] <= 65535, "dpg_dgcspn_topdown: level %d: pad %d out of domain", j, r[q]);
+        // (the pads after a map shape its output only; they are checked through the output shape)
+        const int64_t eff = (int64_t)g.dil + 1;
+        const int64_t span_h = (int64_t)r[8] + r[9] + g.hin - eff + 1, span_w = (int64_t)r[6] + r[7] + g.win - eff + 1;
+        DPG_REQUIRE(span_h >= 1 && span_w >= 1 && g.hout == (span_h + g.stride - 1) / g.stride &&
+                        g.wout == (span_w + g.stride - 1) / g.stride,
+                    "dpg_dgcspn_topdown: level %d: the output shape does not follow from pads, stride and dilation", j);
+        if (g.dw) {
+            DPG_REQUIRE(g.cout == g.cin, "dpg_dgcspn_topdown: level %d: depthwise with %d -> %d channels", j, g.cin, g.cout);
+        } else {
+            const int64_t c2 = (int64_t)g.cin * g.cin, c4 = c2 * c2;
+            DPG_REQUIRE(g.cin <= 181 && g.cout == c4, "dpg_dgcspn_topdown: level %d: %d channels do not give %d = Cin^4", j,
+                        g.cin, g.cout);
+            g.cin2 = (int)c2;
+            g.cin3 = (int)(c2 * g.cin);
+        }
+        DPG_REQUIRE((int64_t)g.cout * g.hout * g.wout <= 0x7fffffff, "dpg_dgcspn_topdown: level %d: map too large", j);
+        if (j == 0)
+            DPG_REQUIRE(g.cin == K && g.hin == H && g.win == W, "dpg_dgcspn_topdown: level 0 does not read the leaf map");
+        else
+            DPG_REQUIRE(g.hin == a.lv[j - 1].hout && g.win == a.lv[j - 1].wout,
+                        "dpg_dgcspn_topdown: level %d does not read the map of level %d", j, j - 1);
+        // entries of list j: at most the positions of the map, at most 4 per active node above
+        const int64_t above = std::min<int64_t>((int64_t)1 << (2 * std::min(n_levels - j, 8)), 65536);
+        cap = std::max<int64_t>(cap, std::min<int64_t>((int64_t)g.hin * g.win, above));
+        if (j + 1 < n_levels) {
+            a.base[j + 1] = (unsigned)slots;
+            slots += (int64_t)g.hout * g.wout;
+        }
+    }
+    a.base[n_levels] = (unsigned)slots;
+    a.slots = (unsigned long long)(slots + 2 * (int64_t)C * H * W);
+    // (two lists of `cap` ints: 32 KiB at the most, inside the 64 KiB a launch gets without asking for more)
+    DPG_REQUIRE(cap <= 4096, "dpg_dgcspn_topdown: %lld active positions at one level are more than the 4096 the lists hold",
+                (long long)cap);
+    a.cap = (int)cap;
+    if (B == 0) return DPG_OK;
+    DPG_REQUIRE(loc && scale && out, "dpg_dgcspn_topdown: null pointer");
+    DPG_REQUIRE(mode == DPG_MODE_PRIOR || act, "dpg_dgcspn_topdown: mode 2 needs the bottom-up activations");
+    for (int t = 0; t < n_levels; ++t) {
+        a.act[t] = mode == DPG_MODE_POSTERIOR ? act[t] : nullptr;
+        DPG_REQUIRE(mode == DPG_MODE_PRIOR || a.act[t], "dpg_dgcspn_topdown: activations of level %d missing", t);
+    }
+    for (int t = 1; t <= n_levels; ++t) {
+        a.logw[t] = logw[t];
+        DPG_REQUIRE(a.logw[t], "dpg_dgcspn_topdown: log-weights of level %d missing", t);
+    }
+    const size_t lds = (size_t)2 * a.cap * sizeof(int);
+    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)cus() * 8);
+    if (mode == DPG_MODE_POSTERIOR)
+        DPG_LAUNCH("dgcspn_topdown_kernel<true>", dgcspn_topdown_kernel<true>, dim3(grid), dim3(kThreads), lds,
+                   (hipStream_t)stream, a);
+    else
+        DPG_LAUNCH("dgcspn_topdown_kernel<false>", dgcspn_topdown_kernel<false>, dim3(grid), dim3(kThreads), lds,
+                   (hipStream_t)stream, a);
+    return DPG_OK;
+}

@@ -1,0 +1,127 @@
+"""ctypes binding of ``libdeeprob_dgc.so`` (the C ABI declared in ``include/deeprob_dgc.h``, prefix ``dpg_``): the
+top-down pass of a DGC-SPN.  The prototypes and the ``DPG_*`` constants are read from the header with the parser of
+``deeprob.hip``; nothing of them is written down a second time.  There is no CPU fallback: a missing library raises.
+"""
+import ctypes
+import os
+
+import torch
+
+from deeprob import hip
+from deeprob.hip import HipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_dgc.h'))
+LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_dgc.so'))
+
+
+def _read_header():
+    if not os.path.isfile(HEADER_PATH):
+        raise HipError("deeprob_dgc.h not found at {} -- it is the declaration of the C ABI this binding is built "
+                       "from".format(HEADER_PATH))
+    with open(HEADER_PATH) as f:
+        return hip.parse_header(f.read(), prefix='dpg', header='deeprob_dgc.h')
+
+
+SIGNATURES, CONSTANTS, _ = _read_header()
+globals().update(CONSTANTS)
+
+_lib = None
+
+
+def load_library() -> ctypes.CDLL:
+    """Load ``libdeeprob_dgc.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.isfile(LIB_PATH):
+        raise HipError(
+            "libdeeprob_dgc.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
+            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
+    lib = ctypes.CDLL(LIB_PATH)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _lib = lib
+    return lib
+
+
+def call(fn, *args) -> int:
+    rc = fn(*args)
+    if rc < 0:
+        msg = load_library().dpg_last_error()
+        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
+    return rc
+
+
+def product_geometry(layers):
+    """``[L][DPG_GEOM_INTS]`` rows of the header's geometry table for these SpatialProductLayers, bottom to top."""
+    rows = []
+    for p in layers:
+        if tuple(p.kernel_size) != (2, 2) or p.stride[0] != p.stride[1] or p.dilation[0] != p.dilation[1]:
+            raise ValueError("the top-down pass covers 2x2 windows with one stride and one dilation, got kernel {} stride {} "
+                             "dilation {}".format(p.kernel_size, p.stride, p.dilation))
+        rows.append(list(p.in_features) + list(p.out_features) + list(p.pad) + [p.stride[0], p.dilation[0], int(p.depthwise)])
+    assert all(len(r) == DPG_GEOM_INTS for r in rows)
+    return rows
+
+
+def dgcspn_topdown(mode: int, n_samples: int, in_features, geom, classes: int, x, y, acts, logws, loc: torch.Tensor,
+                   scale: torch.Tensor, seed: int, want_choice: bool = False, labels_trusted: bool = False):
+    """``dpg_dgcspn_topdown``: DgcSpn.sample (mode 1) / DgcSpn.sample_conditional (mode 2) top-down in one launch.
+    ``geom``: :func:`product_geometry`; ``acts``: [leaf output, sum layer 1 output, ...] NCHW (mode 2); ``logws``: the
+    log-softmax weights of the sum layers 1 .. L-1, then of the root.  Returns ``[B, C, H, W]`` (and the ``[B, 1 + H W]``
+    int32 choices when asked).  A label outside ``[0, classes)`` raises ``ValueError`` (``labels_trusted``: the caller drew
+    them itself, no check and no read-back)."""
+    if not loc.is_cuda:
+        raise HipError("the model lives on '{}': the deeprob HIP path only samples on a HIP device (there is no CPU "
+                       "fallback)".format(loc.device))
+    lib = load_library()
+    C, H, W = (int(v) for v in in_features)
+    L, B, device = len(geom), int(n_samples), loc.device
+    keep = []
+
+    def dev(t, name, shape=None):
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError("dgcspn_topdown: expected {} of shape {}, got {}".format(name, tuple(shape), tuple(t.shape)))
+        t = hip.require_device_f32(t.detach(), name)
+        if t.device != device:
+            raise HipError("{} lives on '{}', the model on '{}'".format(name, t.device, device))
+        keep.append(t)
+        return t
+
+    if len(logws) != L:
+        raise ValueError('dgcspn_topdown: %d weight tensors for %d levels' % (len(logws), L))
+    act_arr = (ctypes.c_void_p * L)()
+    xd = None
+    if mode == DPG_MODE_POSTERIOR:
+        if len(acts) != L:
+            raise ValueError('dgcspn_topdown: %d activation tensors for %d levels' % (len(acts), L))
+        xd = dev(x, 'x', (B, C, H, W))
+        for t, a in enumerate(acts):
+            act_arr[t] = hip.ptr(dev(a, 'act[%d]' % t, (B,) + tuple(geom[t][0:3])))
+    logw_arr = (ctypes.c_void_p * (L + 1))()
+    for t, w in enumerate(logws[:-1], start=1):
+        logw_arr[t] = hip.ptr(dev(w, 'logw[%d]' % t, (geom[t][0],) + tuple(geom[t - 1][3:6])))
+    logw_arr[L] = hip.ptr(dev(logws[-1], 'root logw', (classes, geom[-1][3] * geom[-1][4] * geom[-1][5])))
+    K = geom[0][0]
+    locd, scaled = dev(loc, 'loc', (K, C, H, W)), dev(scale, 'scale', (K, C, H, W))
+    yd = None
+    if y is not None:
+        yd = y.to(device=device, dtype=torch.int64).contiguous()
+        if tuple(yd.shape) != (B,):
+            raise ValueError("dgcspn_topdown: expected y of shape ({},), got {}".format(B, tuple(yd.shape)))
+        # (the kernel clamps a label so as not to read past the root's table; a wrong label is the caller's error and is
+        # reported here, at the cost of one read-back of two numbers)
+        if B > 0 and not labels_trusted:
+            lo, hi = (int(v) for v in torch.stack([yd.min(), yd.max()]).tolist())
+            if lo < 0 or hi >= classes:
+                raise ValueError("dgcspn_topdown: labels must lie in [0, {}), got {} .. {}".format(classes, lo, hi))
+    garr = (ctypes.c_int32 * (L * DPG_GEOM_INTS))(*[int(v) for row in geom for v in row])
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
+    choice = torch.empty((B, 1 + H * W), dtype=torch.int32, device=device) if want_choice else None
+    call(lib.dpg_dgcspn_topdown, mode, B, C, H, W, K, L, ctypes.cast(garr, ctypes.c_void_p), classes, hip.ptr(xd), hip.ptr(yd),
+         ctypes.cast(act_arr, ctypes.c_void_p), ctypes.cast(logw_arr, ctypes.c_void_p), hip.ptr(locd), hip.ptr(scaled),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, hip.ptr(out), hip.ptr(choice), hip.stream_ptr(device))
+    return (out, choice) if want_choice else out

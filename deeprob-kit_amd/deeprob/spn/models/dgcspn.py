@@ -218,8 +218,91 @@ class DgcSpn(ProbabilisticModel):
             estimates = torch.sum(torch.unsqueeze(z_grad, dim=2) * self.base_layer.loc, dim=1)
             return torch.where(torch.isnan(x), estimates, x)
 
-    def sample(self, n_samples: int, y: Optional[torch.Tensor] = None) -> torch.Tensor:
-        raise NotImplementedError("Sampling is not implemented for DGC-SPNs")
+    # ---- top-down pass: one launch (csrc/dgc/dgcspn_topdown.hip) -----------------------------------------------------------
+    def _product_layers(self):
+        return [layer for layer in self.layers if isinstance(layer, SpatialProductLayer)]
+
+    def _topdown_logw(self):
+        """log_softmax of every sum layer's weight (bottom to top) and of the root's, formed by the same torch call as the
+        forward forms them (layers/dgcspn.py: SpatialSumLayer / SpatialRootLayer)."""
+        out = [torch.log_softmax(layer.weight, dim=1) for layer in self.layers if isinstance(layer, SpatialSumLayer)]
+        out.append(torch.log_softmax(self.root_layer.weight, dim=1))
+        return out
+
+    def _upward_for_sampling(self, x: torch.Tensor):
+        """The leaf map and every sum layer's output, NCHW (no product map is kept): the fused product + sum level where it
+        applies, else the two layers."""
+        from deeprob.hip import ops_spatial
+        h = self.base_layer(x)
+        acts = [h]
+        for i in range(0, len(self.layers) - 1, 2):
+            prod, ssum = self.layers[i], self.layers[i + 1]
+            y = ops_spatial.spatial_prodsum(h, prod, ssum.weight, ssum._ws, out_pixel_major=False)
+            if y is None:
+                y = ssum(prod(h))
+            h = y
+            acts.append(h)
+        return acts
+
+    def _check_topdown(self, what: str):
+        from deeprob.hip import HipError
+        if self.training and (self.in_dropout is not None or self.sum_dropout is not None):
+            raise NotImplementedError('{}: training mode with in_dropout / sum_dropout set (call eval() first: the '
+                                      'distribution is that of the model without dropout)'.format(what))
+        device = self.root_layer.weight.device
+        if device.type != 'cuda':
+            raise HipError("{}: the model lives on '{}': the deeprob HIP path only samples on a HIP device (there is no "
+                           "CPU fallback)".format(what, device))
+        return device
+
+    @torch.no_grad()
+    def sample(self, n_samples: int, y: Optional[torch.Tensor] = None, seed: Optional[int] = None) -> torch.Tensor:
+        """``[n_samples, C, H, W]`` ancestral samples, top-down in one launch (the reference raises here:
+        dgcspn.py ``sample``).  ``y``: the class of every sample (drawn with ``torch.randint`` when missing, ignored by a
+        model with one root; a label outside ``[0, out_classes)`` raises ``ValueError``).  The draws come from the library's
+        counter-based hash (``seed``: fix them, e.g. to replay a batch).  A pixel outside every scope -- the last row and column of an odd map under a pooling level -- is NaN."""
+        from deeprob.hip import dgc, ops
+        device = self._check_topdown('sample')
+        drawn = y is None
+        if self.out_classes == 1:
+            y = None
+        elif y is None:
+            y = torch.randint(self.out_classes, [n_samples], device=device)
+        geom = dgc.product_geometry(self._product_layers())
+        return dgc.dgcspn_topdown(dgc.DPG_MODE_PRIOR, n_samples, self.in_features, geom, self.out_classes, None, y, None,
+                                  self._topdown_logw(), self.base_layer.loc, self.base_layer.scale,
+                                  ops.draw_seed() if seed is None else int(seed), labels_trusted=drawn)
+
+    @torch.no_grad()
+    def sample_conditional(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, seed: Optional[int] = None) -> torch.Tensor:
+        """One exact draw from p(x_missing | x_observed, y) per row: the NaN entries of ``x [B,C,H,W]`` are drawn, the observed
+        ones are returned as they are (the reference has no counterpart; ``mpe`` returns posterior means).  The bottom-up
+        pass -- leaf map and every sum layer's output -- then one top-down launch that draws every sum node's input in
+        proportion to weight * value of the input under the evidence.  Without labels the class of a row is drawn from
+        softmax(root outputs) by ``torch.multinomial`` (rows whose evidence is impossible under every class take it
+        uniformly; a given label outside ``[0, out_classes)`` raises ``ValueError``); ``seed`` fixes the kernel's counter-based
+        draws: a row's draws depend on (seed, row index) and its evidence only.  A pixel outside every scope is returned as given."""
+        from deeprob.hip import dgc, ops, ops_spatial
+        device = self._check_topdown('sample_conditional')
+        x = ops.require_device_f32(x, 'x')
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.in_features):
+            raise ValueError("expected inputs [B, {}], got {}".format(tuple(self.in_features), tuple(x.shape)))
+        acts = self._upward_for_sampling(x)
+        drawn = y is None
+        if self.out_classes == 1 or x.shape[0] == 0:
+            y = None
+        elif y is None:
+            top = ops_spatial.spatial_prodroot(acts[-1], self.layers[-1], self.root_layer.weight, self.root_layer._ws2)
+            if top is None:
+                top = self.root_layer(self.layers[-1](acts[-1]))
+            post = torch.softmax(top, dim=1)
+            # (evidence impossible under every class: softmax gives NaN; such a row takes its class uniformly)
+            post = torch.where(torch.isfinite(post).all(dim=1, keepdim=True), post, torch.full_like(post, 1.0 / self.out_classes))
+            y = torch.multinomial(post, 1).squeeze(1)
+        geom = dgc.product_geometry(self._product_layers())
+        return dgc.dgcspn_topdown(dgc.DPG_MODE_POSTERIOR, x.shape[0], self.in_features, geom, self.out_classes, x, y, acts,
+                                  self._topdown_logw(), self.base_layer.loc, self.base_layer.scale,
+                                  ops.draw_seed() if seed is None else int(seed), labels_trusted=drawn)
 
     def loss(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.out_classes == 1:
