@@ -39,6 +39,8 @@ int ensure_dynamic_lds(const void *kernel, int bytes);
 bool slow_hint_next(const void *ws_key, int **dev_word, int *launch_seq);
 // releases what the library keeps per workspace address (hint slot, params_gate slots) for keys in [base, base + bytes)
 void workspace_forget(const void *base, int64_t bytes);
+// (ratspn_gemm_slice.hip: the streams remembered for the workspaces in [lo, hi))
+void slice_lanes_forget(const void *lo, const void *hi);
 
 // ---- device-side check of cached parameter tables (DPK_FLAG_PARAMS_VERIFY) ------------------------------------------
 // The host can only tell that a parameter MAY have changed from its address / version counter; a write through

@@ -370,8 +370,9 @@ bool gemm_marginal_shape_ok(int D, int NT);
 // ratspn_gemm_slice.hip: persistent 32-sample blocks, the feature axis split over seven waves with the mean table in registers
 bool gemm_slice_shape_ok(int D, int reps, int I, int S, int NT);
 int64_t gemm_slice_min_batch();
-int ratspn_gemm_slice_forward(const GemmArgs &a, const GemmPrepArgs &p, int I, int S, int NT, hipStream_t st);
-bool gemm_slice_checks_inline(int64_t B, int np, int d);
+int ratspn_gemm_slice_forward(const GemmArgs &a, const GemmPrepArgs &p, int I, int S, int NT, int lanes, hipStream_t st);
+int gemm_slice_lanes(const void *ws_key, uint32_t flags, hipStream_t st);   // this launch and the launches beside it
+bool gemm_slice_checks_inline(int64_t B, int np, int d, int lanes);
 // ratspn_gemm_wide.hip: 8-channel models, a wave per repetition
 bool gemm_wide_shape_ok(int D, int reps, int I, int S, int C);
 int ratspn_gemm_wide_forward(const GemmArgs &a, const GemmPrepArgs &p, int S, hipStream_t st);
@@ -403,6 +404,8 @@ int ratspn_gemm_forward(const RatWs &w, const float *x, int64_t B, int D, const 
     // (the slice mapping: clean evidence only -- a block that meets NaN is evaluated exactly and sets the hint)
     const bool slice = !wide && !emitting && !marginal_ring && gemm_slice_min_batch() >= 0 && B >= gemm_slice_min_batch() &&
                        gemm_slice_shape_ok(D, reps, I, S, NT);
+    // (how many launches share the compute units -- the caller's word, or what the other streams are doing: ratspn_gemm_slice.hip)
+    const int slice_lanes = slice ? gemm_slice_lanes(w.gctl, flags, st) : 1;
     const bool small = !wide && !slice && B <= gemm_small_max_batch() && gemm_small_shape_ok(D, NT);
     if (emitting && !wide && !small) {   // (training forward: the 32-sample kernels)
         set_error("ratspn_forward_train: channels=%d at %lld samples not built (dpk_ratspn_small_batch_max)", I, (long long)B);
@@ -437,7 +440,7 @@ int ratspn_gemm_forward(const RatWs &w, const float *x, int64_t B, int D, const 
     const bool ring_inline = ring_vi && ring_plain && (int64_t)np <= std::min<int64_t>(cdiv(B, kGemmTile), device_cus());
     const bool verify_inline = inline_allowed && (flags & DPK_FLAG_PARAMS_VERIFY) && !(flags & DPK_FLAG_PARAMS_CACHED) &&
                                ((wide && gemm_wide_takes_tile32(B, D, reps, C, marginal, emitting)) || small || ring_inline ||
-                                (slice && gemm_slice_checks_inline(B, np, p.d)));
+                                (slice && gemm_slice_checks_inline(B, np, p.d, slice_lanes)));
     if (verify_inline) {
         p.mode = kPrepInline;
         p.np = np;
@@ -465,7 +468,7 @@ int ratspn_gemm_forward(const RatWs &w, const float *x, int64_t B, int D, const 
         if (emitting) { a.emit_leaf = emit->leaf; a.emit_sum = emit->sum; a.emit_out = emit->out; }
         if (wide) return ratspn_gemm_wide_forward(a, p, S, st);
         if (small) return ratspn_gemm_small_forward(a, p, reps, I, S, NT, st);
-        if (slice) return ratspn_gemm_slice_forward(a, p, I, S, NT, st);
+        if (slice) return ratspn_gemm_slice_forward(a, p, I, S, NT, slice_lanes, st);
         return ratspn_gemm_marginal_forward(a, reps, I, S, NT, st);
     }
     ring::GemmArgs a{};

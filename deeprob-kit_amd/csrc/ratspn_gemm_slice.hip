@@ -40,9 +40,13 @@
 // Results agree with the other two mappings to fp32 rounding, not bit for bit (seven partial sums in a fixed order).
 #include "ratspn_gemm_fused.h"
 #include "ratspn_gemm_prep.h"
+#include "../../include/deeprob_slice.h"
 #include <stdlib.h>
 #include <algorithm>
+#include <atomic>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 
 namespace dpk {
 
@@ -865,8 +869,159 @@ static int64_t &slice_batch_min_ref() {
 }
 int64_t gemm_slice_min_batch() { return slice_batch_min_ref(); }
 
+// ---- how many work-groups a launch takes (concurrent launches share the compute units) ---------------------
+// A launch that has the chip to itself (lanes == 1) takes min(ntiles, cus) work-groups, one per compute unit (160 KB of LDS:
+// no two are co-resident).  A launch that runs beside lanes - 1 others takes its share of the compute units and walks more
+// blocks per work-group: the cost per launch and work-group (prologue, first block, idle last block period) is then paid once
+// per 2 x or 3 x as many blocks, while the other lanes stream.  gmax = the share (at least the np hashing work-groups of
+// an in-launch table check: those are blockIdx < np); the grid is the FEWEST work-groups that finish in the same number of
+// block rounds as gmax would.  Never more than gmax: work-groups beyond a lane's share start only when others have ended.
+static int slice_gmax(int64_t ntiles, int cus, int lanes, int np) {
+    const int share = std::max(1, cus / std::max(1, lanes));
+    return (int)std::max<int64_t>(share, std::min<int64_t>(np, ntiles));
+}
+int slice_grid(int64_t ntiles, int cus, int lanes, int np) {
+    if (ntiles <= 0 || cus <= 0) return 0;
+    if (lanes <= 1) return (int)std::min<int64_t>(ntiles, cus);
+    const int gmax = slice_gmax(ntiles, cus, lanes, np);
+    const int64_t rounds = cdiv(ntiles, (int64_t)gmax);
+    const int64_t grid = cdiv(ntiles, rounds);
+    return (int)std::max<int64_t>(grid, std::min<int64_t>(np, ntiles));
+}
+
+// ---- the lane count of a launch ------------------------------------------------------------------------------------------
+// Process-wide override (dps_slice_lanes, include/deeprob_slice.h; DPK_SLICE_LANES in the environment sets the initial value): 0 = the caller's
+// stated value (DPK_FLAG_SLICE_LANES_*), else auto; 1 = always the whole chip; n = always n lanes.
+constexpr int kSliceLanesMax = DPS_LANES_MAX;        // (the flag field's four bits)
+constexpr int kSliceAutoLanesMax = DPS_AUTO_LANES_MAX;     // auto mode: 1 + busy peers, at most this
+constexpr int kSliceAutoStreak = DPS_AUTO_STREAK;       // ... and only once the peers were busy at this many consecutive launches of the workspace
+constexpr int kSliceAutoRecheck = DPS_AUTO_RECHECK;   // a lane that shares looks at its peers again at every this-many-th launch
+constexpr int kSlicePeers = 8;            // workspaces remembered per device
+constexpr int kSliceDevices = 64;
+static int slice_lanes_initial() {
+    const char *e = getenv("DPK_SLICE_LANES");
+    const int v = e ? atoi(e) : 0;
+    return v < 0 ? 0 : std::min(v, kSliceLanesMax);
+}
+static std::atomic<int> &slice_lanes_ref() {
+    static std::atomic<int> v{slice_lanes_initial()};
+    return v;
+}
+static std::atomic<int> g_slice_last_grid{0}, g_slice_last_lanes{0};
+
+// Auto mode (eager launches that state nothing).  Per device, the stream of each workspace's last eager slice launch.  At a
+// launch of workspace W on stream s every OTHER workspace whose last stream differs from s is a candidate peer; it is busy
+// when hipStreamQuery on its stream says "not ready".  W takes a share (1 + busy peers) only after its peers were busy at
+// kSliceAutoStreak consecutive launches of W, and goes back to the whole chip at the first launch that finds them idle: two
+// batches on two streams, a lone stream and a synchronised caller all keep the whole chip; a sustained loop over two streams
+// settles at cus / 2 per launch.  What this cannot see: a lane that shares beside a peer whose launches are much shorter
+// gives compute units away -- the hysteresis and the override are for that.
+namespace {
+struct SlicePeer {
+    const void *ws;
+    hipStream_t st;
+    int streak;              // consecutive looks that found a peer busy
+    int lanes;               // what the last look decided
+    int since;               // launches since the last look
+    unsigned long long seq;
+};
+struct SliceRegistry {
+    std::mutex mu;
+    std::vector<SlicePeer> dev[kSliceDevices];
+    unsigned long long seq = 0;
+};
+SliceRegistry &slice_registry() {
+    static SliceRegistry r;
+    return r;
+}
+}  // namespace
+
+void slice_lanes_forget(const void *lo, const void *hi) {
+    SliceRegistry &r = slice_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    for (auto &v : r.dev)
+        v.erase(std::remove_if(v.begin(), v.end(), [&](const SlicePeer &e) { return (const char *)e.ws >= (const char *)lo && (const char *)e.ws < (const char *)hi; }),
+                v.end());
+}
+
+static int slice_lanes_auto(const void *ws_key, hipStream_t st) {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kSliceDevices) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    SliceRegistry &r = slice_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    std::vector<SlicePeer> &v = r.dev[d];
+    // A lane that shares looks again only at every kSliceAutoRecheck-th launch.  hipStreamQuery is not free for the stream it
+    // asks about: the runtime puts a marker behind the stream's last kernel to learn whether it has ended, and a marker
+    // behind every launch of the peer cost the two-stream loop 1.3 us per step (41.8 against 40.5 with the lane count
+    // fixed at 2, same process).  An idle stream gets no marker: a lane that has the chip to itself looks at every launch.
+    for (SlicePeer &e : v)
+        if (e.ws == ws_key && e.st == st && e.lanes > 1 && e.since + 1 < kSliceAutoRecheck) {
+            ++e.since;
+            e.seq = ++r.seq;
+            return e.lanes;
+        }
+    int busy = 0;
+    for (size_t i = 0; i < v.size();) {
+        bool gone = false;
+        if (v[i].ws != ws_key && v[i].st != st) {   // (launches on one stream follow one another: no peer)
+            // (a peer stream under capture must not be queried: the query would invalidate the capture)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            hipError_t e = hipStreamIsCapturing(v[i].st, &cs);
+            if (e == hipSuccess && cs == hipStreamCaptureStatusNone) e = hipStreamQuery(v[i].st);
+            if (e == hipErrorNotReady) ++busy;
+            if (e != hipSuccess) (void)hipGetLastError();
+            gone = e != hipSuccess && e != hipErrorNotReady;   // (a stream that is no more: the peer is dropped)
+        }
+        if (gone) {
+            v[i] = v.back();
+            v.pop_back();
+        } else {
+            ++i;
+        }
+    }
+    size_t me = 0;
+    while (me < v.size() && v[me].ws != ws_key) ++me;
+    if (me >= v.size()) {
+        if ((int)v.size() >= kSlicePeers) {   // (full: the workspace that launched longest ago makes room)
+            size_t old = 0;
+            for (size_t i = 1; i < v.size(); ++i)
+                if (v[i].seq < v[old].seq) old = i;
+            v[old] = v.back();
+            v.pop_back();
+        }
+        v.push_back(SlicePeer{ws_key, st, 0, 1, 0, 0ull});
+        me = v.size() - 1;
+    }
+    SlicePeer &m = v[me];
+    m.st = st;
+    m.seq = ++r.seq;
+    m.streak = busy > 0 ? std::min(m.streak + 1, kSliceAutoStreak) : 0;
+    m.lanes = m.streak >= kSliceAutoStreak ? std::min(1 + busy, kSliceAutoLanesMax) : 1;
+    m.since = 0;
+    return m.lanes;
+}
+
+// The lane count of the slice launch of workspace `ws_key` on `st`.  Inside a stream capture nothing is queried: the stated
+// value, or 1.
+int gemm_slice_lanes(const void *ws_key, uint32_t flags, hipStream_t st) {
+    const int forced = slice_lanes_ref().load(std::memory_order_relaxed);
+    if (forced >= 1) return forced;
+    const int stated = (int)((flags & DPK_FLAG_SLICE_LANES_MASK) >> DPK_FLAG_SLICE_LANES_SHIFT);
+    if (stated >= 1) return stated;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    if (cs != hipStreamCaptureStatusNone) return 1;
+    return slice_lanes_auto(ws_key, st);
+}
+
 template <int I, int S, int NT>
-static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, hipStream_t st) {
+static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, int lanes, hipStream_t st) {
     size_t lds = (size_t)slice_lds_bytes(NT, a0.reps * 2 * S * I * I);
     if (p.np > 0 && gemm_prep_lds_bytes(a0.D, I, a0.d) > lds) lds = gemm_prep_lds_bytes(a0.D, I, a0.d);
     DPK_REQUIRE(lds <= 160 * 1024, DPK_EUNSUPPORTED, "ratspn_gemm_slice: %zu bytes of LDS", lds);
@@ -877,16 +1032,18 @@ static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, hipStrea
     profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
     if (ev0) (void)hipEventRecord(ev0, st);
     // a work-group remembers the blocks it leaves to the exact evaluation in a 64-bit mask: at most 64 blocks per
-    // work-group and launch, i.e. 524 288 samples per launch on 256 compute units -- larger batches take several launches
+    // work-group and launch, i.e. 524 288 samples per launch on 256 work-groups -- larger batches take several launches
     // (the caller keeps the in-launch table check to single-launch batches: gemm_slice_checks_inline)
-    const int64_t per_launch = (int64_t)64 * 32 * cus;
+    const int64_t per_launch = (int64_t)64 * 32 * slice_gmax(cdiv(a0.B, 32), cus, lanes, p.np);
     for (int64_t off = 0; off < a0.B; off += per_launch) {
         GemmArgs a = a0;
         a.x = a0.x + off * a0.D;
         a.out = a0.out + off * a0.C;
         a.B = std::min(per_launch, a0.B - off);
         a.ntiles = cdiv(a.B, 32);
-        const int grid = a.ntiles < cus ? a.ntiles : cus;
+        const int grid = slice_grid(a.ntiles, cus, lanes, p.np);
+        DPK_REQUIRE(grid >= 1 && grid >= std::min<int64_t>(p.np, a.ntiles) && cdiv((int64_t)a.ntiles, (int64_t)grid) <= 64, DPK_ELAUNCH,
+                    "ratspn_gemm_slice: grid %d for %lld blocks", grid, (long long)a.ntiles);
         GemmPrepArgs pp = p;
         pp.readers = grid;
 #ifdef DPK_TIMELINE
@@ -900,21 +1057,26 @@ static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, hipStrea
 #endif
         DPK_LAUNCH(kern, dim3(grid), dim3(kSliceThreads), lds, st, a, pp);
         DPK_CHECK_LAUNCH("ratspn_gemm_slice_kernel");
+        g_slice_last_grid.store(grid, std::memory_order_relaxed);
+        g_slice_last_lanes.store(lanes, std::memory_order_relaxed);
     }
     if (ev1) (void)hipEventRecord(ev1, st);
     return DPK_OK;
 }
 
-// whether a launch of B samples can carry its own table check: one launch, at least np work-groups (the eighth wave of
-// work-group g fingerprints table work-group g's inputs: ranges of at most kFpK x 64 words -- d <= 256 features per region)
-bool gemm_slice_checks_inline(int64_t B, int np, int d) {
+// whether a launch of B samples on `lanes` lanes can carry its own table check: one launch, at least np work-groups (the
+// eighth wave of work-group g fingerprints table work-group g's inputs: ranges of at most kFpK x 64 words -- d <= 256
+// features per region).  Decides on the grid gemm_slice_launch takes.
+bool gemm_slice_checks_inline(int64_t B, int np, int d, int lanes) {
     const int cus = device_cus();
-    return B <= (int64_t)64 * 32 * cus && cdiv(B, 32) >= np && 8 * d <= kFpK * 64;
+    const int64_t ntiles = cdiv(B, 32);
+    return B <= (int64_t)64 * 32 * slice_gmax(ntiles, cus, lanes, np) && ntiles >= np &&
+           slice_grid(ntiles, cus, lanes, np) >= np && 8 * d <= kFpK * 64;
 }
 
 // The caller (ratspn_gemm_forward) has built / checked the tables and filled the argument block.
-int ratspn_gemm_slice_forward(const GemmArgs &a, const GemmPrepArgs &p, int I, int S, int NT, hipStream_t st) {
-    if (I == 2 && S == 2 && NT == 2) return gemm_slice_launch<2, 2, 2>(a, p, st);
+int ratspn_gemm_slice_forward(const GemmArgs &a, const GemmPrepArgs &p, int I, int S, int NT, int lanes, hipStream_t st) {
+    if (I == 2 && S == 2 && NT == 2) return gemm_slice_launch<2, 2, 2>(a, p, std::max(1, lanes), st);
     set_error("ratspn_gemm_slice: (channels=%d, sums=%d) not built", I, S);
     return DPK_EUNSUPPORTED;
 }
@@ -927,3 +1089,15 @@ extern "C" int64_t dpk_ratspn_slice_batch_min(int64_t samples) {
     v = samples < -1 ? dpk::slice_batch_initial() : samples;   // (-1: off, below: back to the initial value)
     return prev;
 }
+
+// ---- include/deeprob_slice.h ------------------------------------------------------------------------------------------------
+extern "C" int32_t dps_slice_grid(int64_t ntiles, int32_t cus, int32_t lanes, int32_t np) {
+    return dpk::slice_grid(ntiles, cus, lanes, np);
+}
+extern "C" int32_t dps_slice_lanes(int32_t lanes) {
+    std::atomic<int> &v = dpk::slice_lanes_ref();
+    const int next = lanes < 0 ? dpk::slice_lanes_initial() : std::min<int>(lanes, dpk::kSliceLanesMax);
+    return v.exchange(next, std::memory_order_relaxed);
+}
+extern "C" int32_t dps_slice_last_grid(void) { return dpk::g_slice_last_grid.load(std::memory_order_relaxed); }
+extern "C" int32_t dps_slice_last_lanes(void) { return dpk::g_slice_last_lanes.load(std::memory_order_relaxed); }

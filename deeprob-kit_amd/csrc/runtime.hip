@@ -199,6 +199,7 @@ GatePools &gate_pools() {
 // the slot's accumulator and ticket are per table set, not per stream.
 void workspace_forget(const void *base, int64_t bytes) {
     const char *lo = (const char *)base, *hi = lo + bytes;
+    slice_lanes_forget(lo, hi);
     {
         GatePools &gp = gate_pools();
         std::lock_guard<std::mutex> lock(gp.mu);

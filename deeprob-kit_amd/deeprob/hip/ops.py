@@ -10,7 +10,8 @@ import torch
 
 from deeprob.hip import (
     load_library, call, check, ptr, stream_ptr, require_device_f32, Workspace, HipError, DPK_EUNSUPPORTED,
-    DPK_FLAG_STRUCT_CACHED, DPK_FLAG_UNIT_SCALE, DPK_FLAG_PARAMS_CACHED, DPK_FLAG_LL_SUM_SPREAD, LL_SPREAD, tensors_key,
+    DPK_FLAG_STRUCT_CACHED, DPK_FLAG_UNIT_SCALE, DPK_FLAG_PARAMS_CACHED, DPK_FLAG_LL_SUM_SPREAD, DPK_FLAG_SLICE_LANES_SHIFT, DPK_FLAG_SLICE_LANES_MASK,
+    LL_SPREAD, tensors_key,
     trust_versions,
 )
 
@@ -458,6 +459,21 @@ def ratspn_forward_fused(x, mask, pad_mask, loc, scale, sum_weights, root_weight
     return lctx.ws.outcome(rc, lib.dpk_ratspn_forward, out, forget_structure=True)
 
 
+def slice_lanes_flag(lanes: Optional[int]) -> int:
+    """The lane count of a caller as the bit field of ``dpk_ratspn_forward``'s flags (0 for None: not stated)."""
+    if lanes is None:
+        return 0
+    lanes = int(lanes)
+    if not 1 <= lanes <= (DPK_FLAG_SLICE_LANES_MASK >> DPK_FLAG_SLICE_LANES_SHIFT):
+        raise ValueError('lanes must lie in 1 .. {}, got {}'.format(DPK_FLAG_SLICE_LANES_MASK >> DPK_FLAG_SLICE_LANES_SHIFT, lanes))
+    return (lanes << DPK_FLAG_SLICE_LANES_SHIFT) & DPK_FLAG_SLICE_LANES_MASK
+
+
+def slice_lanes_of(flags: int) -> int:
+    """The lane count stated in ``flags`` (0: none)."""
+    return (int(flags) & DPK_FLAG_SLICE_LANES_MASK) >> DPK_FLAG_SLICE_LANES_SHIFT
+
+
 class FusedForwardPlan:
     """A bound ``dpk_ratspn_forward`` call for one resident input buffer: the pointer / size validation and the
     argument marshalling of :func:`ratspn_forward_fused` are done once, every later step is a single C call
@@ -469,7 +485,11 @@ class FusedForwardPlan:
     """
 
     def __init__(self, x, mask, pad_mask, loc, scale, sum_weights, root_weight, lctx: LeafContext,
-                 static_params: bool = False):
+                 static_params: bool = False, lanes: Optional[int] = None):
+        # lanes: how many launches share the compute units -- this plan's and the ones it runs beside (other streams, the
+        # other chains of a captured window); travels in the flags (DPK_FLAG_SLICE_LANES_*, read by the slice mapping only).
+        # None: not stated -- an eager launch looks at the other streams itself, a captured one takes the whole chip.
+        self.lanes_flag = slice_lanes_flag(lanes)
         # static_params: the caller guarantees that the parameter BYTES do not change while the plan lives (a frozen
         # model serving / evaluating): later runs pass DPK_FLAG_PARAMS_CACHED and skip the device-side fingerprint
         self.static_params = bool(static_params)
@@ -483,6 +503,7 @@ class FusedForwardPlan:
         self.device = x.device
         self.out = torch.empty((B, lctx.C), dtype=torch.float32, device=x.device)
         ws, flags = lctx.workspace(x.device, mask, pad_mask, scale)
+        flags |= self.lanes_flag
         self.lctx, self.ws = lctx, ws
         self.args = [ptr(x), B, lctx.D, ptr(mask), ptr(self.tensors[2]), ptr(self.tensors[3]), ptr(self.tensors[4]),
                      ptr(sw[0]) if len(sw) > 0 else None, ptr(sw[1]) if len(sw) > 1 else None,

@@ -109,7 +109,8 @@ class ShardedLogLikelihood:
     """
 
     def __init__(self, model=None, group=None, local_sum_fn: Optional[Callable] = None,
-                 static_inputs: bool = False, reduce_every: int = 32, static_params: bool = False):
+                 static_inputs: bool = False, reduce_every: int = 32, static_params: bool = False,
+                 lanes: Optional[int] = None):
         self.model = model
         self.group = group
         self.local_sum_fn = local_sum_fn
@@ -126,6 +127,10 @@ class ShardedLogLikelihood:
         # static_params: the model is frozen for the evaluator's lifetime (no write to a parameter, through .data
         # included): the bound calls skip the device-side fingerprint of the cached parameter tables
         self.static_params = static_params
+        # lanes: how many evaluators of this kind run side by side on the device, this one included (other streams, the
+        # chains of a graphed window): the bound RAT-SPN calls then take their share of the compute units instead of
+        # queueing for all of them (``RatSpn.fused_plan``).  None: not stated (eager launches look for themselves)
+        self.lanes = lanes
         self._plans = {}
         self._pending: List[Tuple[torch.Tensor, Optional[object]]] = []
         self.last_ll: Optional[torch.Tensor] = None
@@ -168,7 +173,7 @@ class ShardedLogLikelihood:
                 key = (x.data_ptr(), x.shape[0])
                 plan = self._plans.get(key)
                 if plan is None or (plan is not False and not plan.valid()):
-                    plan = self.model.fused_plan(x, static_params=self.static_params) or False
+                    plan = self.model.fused_plan(x, static_params=self.static_params, lanes=self.lanes) or False
                     self._plans[key] = plan
                 if plan is not False:
                     ll = plan.run(acc)
@@ -257,9 +262,13 @@ class GraphedEvaluationWindow:
     k has completely finished, so its prologue and the predecessor's tail (HBM idle in both) are in series -- at the
     strong-scaling shard sizes (one to four blocks per compute unit) that is most of a step.  Measured, default mode
     (tools/bench_two_streams_graph.py): 12.5 -> 11.1 -> 10.2 us per step at 8 192 samples with 1 / 2 / 3 chains, 16.7 ->
-    14.3 at 16 384, 25.8 -> 22.9 at 32 768, 42.9 -> 40.8 -> 39.5 at 65 536; identical results."""
+    14.3 at 16 384, 25.8 -> 22.9 at 32 768, 42.9 -> 40.8 -> 39.5 at 65 536; identical results.
 
-    def __init__(self, evaluator: 'ShardedLogLikelihood', xs: List[torch.Tensor], always_reduce: bool = False, chains: int = 1):
+    ``lanes``: the lane count the chains' RAT-SPN launches state (``ShardedLogLikelihood(lanes=)``; None = 2, see below);
+    ignored with one chain."""
+
+    def __init__(self, evaluator: 'ShardedLogLikelihood', xs: List[torch.Tensor], always_reduce: bool = False, chains: int = 1,
+                 lanes: Optional[int] = None):
         if evaluator.local_sum_fn is not None:
             raise ValueError("GraphedEvaluationWindow captures the HIP evaluation path, not a custom local_sum_fn")
         self.evaluator, self.xs = evaluator, list(xs)
@@ -279,7 +288,16 @@ class GraphedEvaluationWindow:
             # co-resident; rebuilds the tables in place if a parameter was written) -- and the steps run on the verified
             # tables (static_params).  A write to a parameter between two replays is seen; none happens during a replay.
             models = [evaluator.model] + [workspace_replica(evaluator.model) for _ in range(chains - 1)]
-            self.lanes = [ShardedLogLikelihood(m, static_inputs=True, static_params=True) for m in models]
+            # Every chain's launches state how many of them share the compute units (a captured launch cannot look for
+            # itself).  TWO, whatever the number of chains: two launches are co-resident on half the chip each and the
+            # next chain's launch takes a half as soon as one comes free -- no compute unit is left over (three shares of
+            # 85 leave one, and 2048 blocks on 85 work-groups take 25 rounds where 24.1 would do) and the launch gap stays
+            # hidden.  Measured, three chains, same process (tools/bench_slice_lanes.py --window-lanes 2 4), us per step at
+            # 65 536 / 32 768 / 16 384 / 8 192 samples: whole chip 40.8 / 24.2 / 15.6 / 10.9, two lanes 38.6 / 21.3 / 12.9 /
+            # 8.5, three 40.5 / 22.4 / 13.7 / 9.3, four 45.0 / 24.8 / 14.5 / 9.1.
+            if lanes is None:
+                lanes = 2
+            self.lanes = [ShardedLogLikelihood(m, static_inputs=True, static_params=True, lanes=lanes) for m in models]
         side = torch.cuda.Stream(device=dev)
         branches = [side] + [torch.cuda.Stream(device=dev) for _ in range(chains - 1)]
         # (inputs / parameters still being written on the caller's stream must be complete before the warm pass reads them:

@@ -104,6 +104,15 @@ extern "C" {
                                      the 32-sample kernels (round 4), as a ~5 us launch in front of the ring kernels --, the coupling tables use a fingerprint kernel + gated table
                                      kernels, entry points whose tables are cheap simply rebuild them.              */
 
+#define DPK_FLAG_SLICE_LANES_SHIFT 8   /* dpk_ratspn_forward: bits 8..11 of `flags` hold the caller's LANE COUNT -- this launch */
+#define DPK_FLAG_SLICE_LANES_MASK 3840 /* and the launches it runs beside (other streams, other chains of a captured graph);
+                                         0 = not stated.  Read by the slice mapping only (csrc/ratspn_gemm_slice.hip): a
+                                         launch on n lanes takes about 1/n of the compute units and walks n times as many
+                                         blocks per work-group.  Per-sample results do not depend on it, bit for bit; the
+                                         fp64 sum does to rounding (order of the atomics).  Not stated: an eager launch looks
+                                         at the other streams itself, a captured one takes the whole chip
+                                         (include/deeprob_slice.h).  Plain integers: (lanes << 8) & 3840.                    */
+
 const char *dpk_last_error(void);
 int dpk_abi_version(void);
 
