@@ -12,6 +12,7 @@
 namespace {
 
 using dpc_detail::lse2;
+using dpc_detail::uniform01;
 
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
@@ -122,15 +123,6 @@ struct QueryArgs {
     int64_t row0;
     float *work, *out;
 };
-
-// the generator of dpk_flat_spn_topdown (csrc/flat_spn_queries.hip)
-__device__ __forceinline__ float uniform01(u64 seed, u64 ctr) {
-    u64 z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
-}
 
 // m_j: the children's contributions, pulled in list order
 __device__ __forceinline__ void pull(const QueryArgs &a, const float *t, int j, float &m0, float &m1) {
@@ -253,7 +245,7 @@ extern "C" {
 
 const char *dpc_last_error(void) { return dpc_detail::g_error; }
 
-int dpc_abi_version(void) { return 1; }
+int dpc_abi_version(void) { return 2; }
 
 int dpc_pack_bits(const float *x, int64_t n, int d, uint64_t *planes, void *stream) {
     DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pack_bits: d = %d is outside 1..%d", d, DPC_MAX_D);

@@ -1,5 +1,7 @@
 // What the translation units of libdeeprob_clt.so share: the thread-local error text behind dpc_last_error(), the
-// argument and launch checks, lse2 of the header's order of operations, and the shape of the segmented pair-count tile.
+// argument and launch checks, lse2 / lse64 of the header's order of operations, the counter-based uniform of the samplers,
+// the shape of the segmented pair-count tile, and a cutset network's leaf: its tables, the gather path and the upward pass
+// (cnet.hip evaluates with them, cnet_queries.hip evaluates and then walks back down).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -36,6 +38,91 @@ __device__ __forceinline__ float lse2(float a, float b) {
     const float hi = fmaxf(a, b), lo = fminf(a, b);
     if (hi == -INFINITY) return -INFINITY;
     return hi + log1pf(expf(lo - hi));
+}
+
+__device__ __forceinline__ double lse64(double x, double y) {
+    const double hi = fmax(x, y), lo = fmin(x, y);
+    if (hi == -INFINITY) return -INFINITY;
+    return hi + log1p(exp(lo - hi));
+}
+
+// the generator of dpk_flat_spn_topdown (csrc/flat_spn_queries.hip)
+__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long ctr) {
+    unsigned long long z = seed + ctr * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+// ---- a leaf of a cutset network: one thread per row, codes as q[col * B], the pass's state as t[(2 j + l) * B] ----------
+struct Leaf {
+    int d;
+    const int32_t *col, *bfs, *parent, *child_off, *child_idx;
+    const float *params;
+};
+
+__device__ __forceinline__ Leaf leaf_of(const int32_t *leaf_meta, const int32_t *leaf_ints, const float *leaf_params, int l) {
+    const int32_t *m = leaf_meta + 3 * (int64_t)l;
+    const int d = m[0];
+    const int32_t *ints = leaf_ints + m[1];
+    return {d, ints, ints + d, ints + 2 * d, ints + 3 * d, ints + 4 * d + 1, leaf_params + m[2]};
+}
+
+// s += params[i][x_parent(i)][x_i] over the leaf's positions in order; false (and s unspecified) if an entry is missing
+__device__ __forceinline__ bool leaf_gather(const Leaf &f, const uint8_t *q, int64_t B, double &s) {
+    for (int i = 0; i < f.d; ++i) {
+        const int pa = f.parent[i];
+        const int ci = q[(int64_t)f.col[i] * B], cp = pa < 0 ? 0 : q[(int64_t)f.col[pa] * B];
+        if (ci == DPC_MISSING) return false;
+        s += (double)f.params[i * 4 + cp * 2 + ci];
+    }
+    return true;
+}
+
+__device__ __forceinline__ void leaf_pull(const Leaf &f, const float *t, int64_t B, int j, float &m0, float &m1) {
+    m0 = 0.f;
+    m1 = 0.f;
+    const int e1 = f.child_off[j + 1];
+    for (int e = f.child_off[j]; e < e1; ++e) {
+        const int64_t c = f.child_idx[e];
+        m0 += t[2 * c * B];
+        m1 += t[(2 * c + 1) * B];
+    }
+}
+
+// the upward pass of dpc_clt_log_likelihood (R = lse) or of dpc_clt_mpe (MAX: R = max) over the leaf's columns, ending
+// at the root as the log likelihood does
+template <bool MAX>
+__device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+    for (int p = f.d - 1; p >= 1; --p) {
+        const int j = f.bfs[p];
+        const float *pj = f.params + j * 4;
+        const int cj = q[(int64_t)f.col[j] * B];
+        float m0, m1;
+        leaf_pull(f, t, B, j, m0, m1);
+        float t0, t1;
+        if (cj != DPC_MISSING) {
+            const float m = cj ? m1 : m0;
+            t0 = pj[cj] + m;
+            t1 = pj[2 + cj] + m;
+        } else if (MAX) {
+            t0 = fmaxf(pj[0] + m0, pj[1] + m1);
+            t1 = fmaxf(pj[2] + m0, pj[3] + m1);
+        } else {
+            t0 = lse2(pj[0] + m0, pj[1] + m1);
+            t1 = lse2(pj[2] + m0, pj[3] + m1);
+        }
+        t[2 * (int64_t)j * B] = t0;
+        t[(2 * (int64_t)j + 1) * B] = t1;
+    }
+    const int j = f.bfs[0];
+    const float *pj = f.params + j * 4;
+    const int cj = q[(int64_t)f.col[j] * B];
+    float m0, m1;
+    leaf_pull(f, t, B, j, m0, m1);
+    if (cj != DPC_MISSING) return pj[cj] + (cj ? m1 : m0);
+    return MAX ? fmaxf(pj[0] + m0, pj[1] + m1) : lse2(pj[0] + m0, pj[1] + m1);
 }
 
 }  // namespace dpc_detail

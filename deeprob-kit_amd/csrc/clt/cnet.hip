@@ -13,7 +13,11 @@
 
 namespace {
 
-using dpc_detail::lse2;
+using dpc_detail::Leaf;
+using dpc_detail::leaf_gather;
+using dpc_detail::leaf_of;
+using dpc_detail::leaf_upward;
+using dpc_detail::lse64;
 
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
@@ -247,75 +251,6 @@ struct CnetArgs {
     float *out;
 };
 
-struct Leaf {
-    int d;
-    const int32_t *col, *bfs, *parent, *child_off, *child_idx;
-    const float *params;
-};
-
-__device__ __forceinline__ Leaf leaf_of(const CnetArgs &a, int l) {
-    const int32_t *m = a.leaf_meta + 3 * (int64_t)l;
-    const int d = m[0];
-    const int32_t *ints = a.leaf_ints + m[1];
-    return {d, ints, ints + d, ints + 2 * d, ints + 3 * d, ints + 4 * d + 1, a.leaf_params + m[2]};
-}
-
-__device__ __forceinline__ double lse64(double x, double y) {
-    const double hi = fmax(x, y), lo = fmin(x, y);
-    if (hi == -INFINITY) return -INFINITY;
-    return hi + log1p(exp(lo - hi));
-}
-
-// s += params[i][x_parent(i)][x_i] over the leaf's positions in order; false (and s unspecified) if an entry is missing
-__device__ __forceinline__ bool leaf_gather(const Leaf &f, const uint8_t *q, int64_t B, double &s) {
-    for (int i = 0; i < f.d; ++i) {
-        const int pa = f.parent[i];
-        const int ci = q[(int64_t)f.col[i] * B], cp = pa < 0 ? 0 : q[(int64_t)f.col[pa] * B];
-        if (ci == DPC_MISSING) return false;
-        s += (double)f.params[i * 4 + cp * 2 + ci];
-    }
-    return true;
-}
-
-__device__ __forceinline__ void pull(const Leaf &f, const float *t, int64_t B, int j, float &m0, float &m1) {
-    m0 = 0.f;
-    m1 = 0.f;
-    const int e1 = f.child_off[j + 1];
-    for (int e = f.child_off[j]; e < e1; ++e) {
-        const int64_t c = f.child_idx[e];
-        m0 += t[2 * c * B];
-        m1 += t[(2 * c + 1) * B];
-    }
-}
-
-// the upward pass of dpc_clt_log_likelihood over the leaf's columns
-__device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
-    for (int p = f.d - 1; p >= 1; --p) {
-        const int j = f.bfs[p];
-        const float *pj = f.params + j * 4;
-        const int cj = q[(int64_t)f.col[j] * B];
-        float m0, m1;
-        pull(f, t, B, j, m0, m1);
-        float t0, t1;
-        if (cj != DPC_MISSING) {
-            const float m = cj ? m1 : m0;
-            t0 = pj[cj] + m;
-            t1 = pj[2 + cj] + m;
-        } else {
-            t0 = lse2(pj[0] + m0, pj[1] + m1);
-            t1 = lse2(pj[2] + m0, pj[3] + m1);
-        }
-        t[2 * (int64_t)j * B] = t0;
-        t[(2 * (int64_t)j + 1) * B] = t1;
-    }
-    const int j = f.bfs[0];
-    const float *pj = f.params + j * 4;
-    const int cj = q[(int64_t)f.col[j] * B];
-    float m0, m1;
-    pull(f, t, B, j, m0, m1);
-    return cj != DPC_MISSING ? pj[cj] + (cj ? m1 : m0) : lse2(pj[0] + m0, pj[1] + m1);
-}
-
 __global__ __launch_bounds__(kRowThreads) void cnet_query_kernel(const CnetArgs a) {
     const int64_t r = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
     if (r >= a.b) return;
@@ -335,7 +270,7 @@ __global__ __launch_bounds__(kRowThreads) void cnet_query_kernel(const CnetArgs 
             s += a.node_logw[2 * k + c];
             k = a.node_child[2 * k + c];
         }
-        if (complete && leaf_gather(leaf_of(a, a.node_child[2 * k]), q, B, s)) {
+        if (complete && leaf_gather(leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]), q, B, s)) {
             a.out[r] = (float)s;
             return;
         }
@@ -352,9 +287,9 @@ __global__ __launch_bounds__(kRowThreads) void cnet_query_kernel(const CnetArgs 
         const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
         const int col = a.node_col[k];
         if (col < 0) {
-            const Leaf f = leaf_of(a, a.node_child[2 * k]);
+            const Leaf f = leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]);
             double s = 0.0;
-            ret = leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward(f, q, B, a.t + r);
+            ret = leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward<false>(f, q, B, a.t + r);
             --depth;
             continue;
         }

@@ -20,6 +20,8 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_c
 
 #: floats of scratch per query launch (128 MiB): a long batch is evaluated in pieces of WORK_FLOATS / (2 D) rows
 WORK_FLOATS = 1 << 25
+#: the oldest ``dpc_abi_version()`` this binding loads: 2 added the ``dpc_cnq_*`` queries of cutset networks
+ABI_VERSION = 2
 
 
 def query_rows(d: int) -> int:
@@ -51,6 +53,11 @@ def load_library() -> ctypes.CDLL:
             "libdeeprob_clt.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
             "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
+    version = lib.dpc_abi_version() if hasattr(lib, 'dpc_abi_version') else 0
+    if version < ABI_VERSION:
+        raise HipError(
+            "libdeeprob_clt.so at {} has ABI version {}, this binding needs {} -- rebuild it with "
+            "`make -C deeprob-kit_amd/csrc` (or __graft_entry__.build())".format(LIB_PATH, version, ABI_VERSION))
     for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
         fn.restype = restype

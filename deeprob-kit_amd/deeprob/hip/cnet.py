@@ -3,7 +3,9 @@
 
 :class:`Generation` is one level of the level-synchronous learner -- the row segments of its tasks, their bit planes,
 counts, scores and the partition into the next level; :class:`DeviceCNet` holds a fitted model as one concatenated
-table, uploaded in one copy.  Everything takes and returns device tensors; there is no CPU fallback.
+table, uploaded in one copy; :func:`log_likelihood`, :func:`mpe` and :func:`sample` are the queries (``dpc_cnet_log_likelihood``
+and the ``dpc_cnq_*`` entries: exact MPE and exact conditional sampling, one launch per piece of the batch).  Everything
+takes and returns device tensors; there is no CPU fallback.
 """
 import numpy as np
 import torch
@@ -124,7 +126,8 @@ class Generation:
 
 
 class DeviceCNet:
-    """A cutset network over ``d`` columns as the tables of ``dpc_cnet_log_likelihood``, in one host-to-device copy.
+    """A cutset network over ``d`` columns as the tables of ``dpc_cnet_log_likelihood`` and of the ``dpc_cnq_*`` queries
+    (``node_parent`` ``[M]``: ``2 * parent + side``, -1 at the root, is derived here), in one host-to-device copy.
 
     ``node_col`` ``[M]``: the cut column of node k, -1 at a leaf; ``node_child`` ``[M, 2]``: its children (at a leaf,
     ``[leaf number, -1]``); ``node_logw`` ``[M, 2]`` float64; ``leaves``: per leaf number ``(cols, bfs, parent, params)``,
@@ -153,13 +156,15 @@ class DeviceCNet:
             meta.append((len(parent), n_ints, n_params))
             n_ints, n_params = n_ints + 5 * len(parent), n_params + 4 * len(parent)
         # one walk from the root: every node once, columns distinct along a path
-        seen, levels, stack = np.zeros(m, bool), 0, [(0, 1, frozenset())]
+        seen, levels, stack = np.zeros(m, bool), 0, [(0, 1, frozenset(), -1)]
+        node_parent = np.full(m, -1, np.int32)
         leaf_seen = np.zeros(len(meta), bool)
         while stack:
-            k, level, used = stack.pop()
+            k, level, used, up = stack.pop()
             ok = 0 <= k < m and not seen[k]
             if ok:
                 seen[k] = True
+                node_parent[k] = up
                 levels = max(levels, level)
                 col = int(node_col[k])
                 if col < 0:
@@ -172,12 +177,13 @@ class DeviceCNet:
                                                                                  for c in cols)
                 else:
                     ok = col < d and col not in used
-                    stack += [(int(node_child[k, 1]), level + 1, used | {col}), (int(node_child[k, 0]), level + 1, used | {col})]
+                    stack += [(int(node_child[k, 1]), level + 1, used | {col}, 2 * k + 1),
+                              (int(node_child[k, 0]), level + 1, used | {col}, 2 * k)]
             if not ok:
                 raise ValueError("the node tables do not describe one cutset network")
         if not seen.all() or not leaf_seen.all():
             raise ValueError("the node tables do not describe one cutset network")
-        ints_all = np.concatenate([node_col.astype(np.int32), node_child.astype(np.int32).reshape(-1),
+        ints_all = np.concatenate([node_col.astype(np.int32), node_child.astype(np.int32).reshape(-1), node_parent,
                                    np.asarray(meta, np.int32).reshape(-1)] + ints)
         buf = torch.from_numpy(np.concatenate([node_logw.reshape(-1).view(np.uint8), ints_all.view(np.uint8),
                                                np.concatenate(params).view(np.uint8)])).to(device)
@@ -185,20 +191,27 @@ class DeviceCNet:
         self.max_leaf_d = max(k for k, _, _ in meta)
         self.node_logw = buf[:16 * m].view(torch.float64)
         ints_d = buf[16 * m:16 * m + 4 * len(ints_all)].view(torch.int32)
-        self.node_col, self.node_child = ints_d[:m], ints_d[m:3 * m]
-        self.leaf_meta, self.leaf_ints = ints_d[3 * m:3 * m + 3 * len(meta)], ints_d[3 * m + 3 * len(meta):]
+        self.node_col, self.node_child, self.node_parent = ints_d[:m], ints_d[m:3 * m], ints_d[3 * m:4 * m]
+        self.leaf_meta, self.leaf_ints = ints_d[4 * m:4 * m + 3 * len(meta)], ints_d[4 * m + 3 * len(meta):]
         self.leaf_params = buf[16 * m + 4 * len(ints_all):].view(torch.float32)
         self.row_bytes = 12 * self.levels + 8 * self.max_leaf_d
+        #: scratch per row of ``dpc_cnq_mpe`` / ``dpc_cnq_sample``: one more int32 per level, the leaf carried upward
+        self.query_row_bytes = 16 * self.levels + 8 * self.max_leaf_d
 
 
-def log_likelihood(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
-    """``[B]`` float32 (``dpc_cnet_log_likelihood``); NaN entries are marginalised."""
-    lib = load_library()
+def _query_rows_of(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
     x = hip.require_device_f32(x, 'x')
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != model.d:
         raise ValueError("expected inputs [B, {}], got {}".format(model.d, tuple(x.shape)))
     if x.device != model.device:
         raise HipError("x lives on '{}', the model on '{}'".format(x.device, model.device))
+    return x
+
+
+def log_likelihood(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
+    """``[B]`` float32 (``dpc_cnet_log_likelihood``); NaN entries are marginalised."""
+    lib = load_library()
+    x = _query_rows_of(model, x)
     b, d = x.shape
     st = hip.stream_ptr(x.device)
     out = torch.empty(b, dtype=torch.float32, device=x.device)
@@ -213,3 +226,44 @@ def log_likelihood(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
              model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d, work.data_ptr(),
              os_.data_ptr(), st)
     return out
+
+
+def _fill(model: DeviceCNet, x: torch.Tensor, seed, want_choice: bool):
+    """``(out [B, D] float32, choice [B] int32 or None)`` of ``dpc_cnq_mpe`` (``seed`` None) or ``dpc_cnq_sample``, a long batch in
+    pieces of :func:`query_rows` rows; a piece of the sampler starts its counters at its first row (``row0``)."""
+    lib = load_library()
+    x = _query_rows_of(model, x)
+    b, d = x.shape
+    st = hip.stream_ptr(x.device)
+    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
+    choice = torch.empty(b, dtype=torch.int32, device=x.device) if want_choice else None
+    step = query_rows(model.query_row_bytes)
+    work = torch.empty(model.query_row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
+    for r0 in range(0, b, step):
+        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
+        n = xs.shape[0]
+        codes = clt.pack_query(xs)
+        head = (xs.data_ptr(), codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(), model.node_child.data_ptr(),
+                model.node_parent.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
+                model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d)
+        tail = (work.data_ptr(), os_.data_ptr(), choice[r0:r0 + step].data_ptr() if want_choice else None, st)
+        if seed is None:
+            call(lib.dpc_cnq_mpe, *head, *tail)
+        else:
+            call(lib.dpc_cnq_sample, *head, seed, r0, *tail)
+    return out, choice
+
+
+def mpe(model: DeviceCNet, x: torch.Tensor, return_choice: bool = False):
+    """``[B, D]`` float32: ``x`` with its NaN entries filled by a most probable completion (``dpc_cnq_mpe``, exact: the OR
+    nodes are deterministic).  With ``return_choice`` also ``[B]`` int32, the node number of the winning leaf."""
+    out, choice = _fill(model, x, None, return_choice)
+    return (out, choice) if return_choice else out
+
+
+def sample(model: DeviceCNet, x: torch.Tensor, seed: int, return_choice: bool = False):
+    """``[B, D]`` float32: ``x`` with its NaN entries drawn from the exact posterior given the observed ones
+    (``dpc_cnq_sample``); the same seed gives the same bytes.  With ``return_choice`` also ``[B]`` int32, the node number of
+    the drawn leaf."""
+    out, choice = _fill(model, x, int(seed) & 0xFFFFFFFFFFFFFFFF, return_choice)
+    return (out, choice) if return_choice else out

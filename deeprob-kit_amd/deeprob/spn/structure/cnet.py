@@ -9,7 +9,10 @@ segments of the splitting tasks are partitioned stably by their cut column.  The
 (:func:`stop_rule` decides on it, in the reference's order) and, for a leaf, the leaf's block of the counts, from which the
 leaf's tree and tables come by ``BinaryCLT.fit_counts`` -- the host half of ``BinaryCLT.fit``.  The training rows never
 come back.  ``log_likelihood`` is one thread per row: a complete row walks one path, a row with NaN walks the OR tree
-depth first.  Inputs follow ``BinaryCLT``: numpy in, numpy out; a device tensor stays on its device; a CPU tensor or a
+depth first.  ``sample`` is the same walk in one launch (``dpc_cnq_sample``): every node returns its value and a leaf drawn
+below it, a NaN OR node picks between its two sides with their posterior odds, and the NaN entries are filled along the one
+path of the drawn leaf and inside it -- an exact draw from ``p(x_missing | x_observed)``, an all-NaN batch being unconditional
+generation.  Inputs follow ``BinaryCLT``: numpy in, numpy out; a device tensor stays on its device; a CPU tensor or a
 missing library raises ``HipError``.
 
 Two deliberate differences from the reference, both in DESIGN.md §16.  ``fit`` takes ``random_state``: the reference lets
@@ -18,9 +21,11 @@ leaf in breadth-first order, left child before right.  And in ``log_likelihood``
 silently drops a row from the sum at the first OR node whose variable is NaN (cnet.py:226-229).  The scores are float64
 (the reference's are float32), which only matters where two gains tie to float32 precision.
 
-Not built: ``mpe`` and ``sample`` (the reference has none for cutset networks) and the xpc learners.  The scored learners
-``learn_cnet_bd`` / ``learn_cnet_bic`` are built in ``deeprob.spn.learning.cnet_bayesian`` and return a
-``BinaryCNet``.
+The reference has neither ``sample`` nor ``mpe`` for cutset networks, so there is nothing to reproduce: both are exact here
+(the OR nodes are deterministic).  Exact MPE is built at kernel, ABI and binding level --
+``deeprob.hip.cnet.mpe(model._on_device(device), x)``, ``dpc_cnq_mpe`` -- and the one-line ``mpe`` method on the class awaits
+a follow-up.  Not built: the xpc learners.  The scored learners ``learn_cnet_bd`` / ``learn_cnet_bic`` are built in
+``deeprob.spn.learning.cnet_bayesian`` and return a ``BinaryCNet``.
 """
 import time
 from typing import List, Optional, Union
@@ -226,10 +231,10 @@ class BinaryCNet(ORNode):
                     logw.append(np.log(np.asarray(node.weights, np.float64)))
         return cnet.DeviceCNet(len(self.scope), col, child, logw, leaves, device)
 
-    def log_likelihood(self, x):
-        """``[B]`` float32 log likelihoods; NaN entries are marginalised."""
+    def _run(self, op, x, *args):
+        """``op(tables on the device, x on the device, *args)`` under the input rules of the module docstring."""
         import torch
-        from deeprob.hip import HipError, clt, cnet
+        from deeprob.hip import HipError, clt
         clt.load_library()
         as_numpy = not isinstance(x, torch.Tensor)
         if as_numpy:
@@ -242,8 +247,28 @@ class BinaryCNet(ORNode):
                            "device tensor".format(x.device))
         if x.dim() != 2 or x.shape[1] != len(self.scope):
             raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
-        out = cnet.log_likelihood(self._on_device(x.device), x)
+        out = op(self._on_device(x.device), x, *args)
         return out.cpu().numpy() if as_numpy else out
+
+    def log_likelihood(self, x):
+        """``[B]`` float32 log likelihoods; NaN entries are marginalised."""
+        from deeprob.hip import cnet
+        return self._run(cnet.log_likelihood, x)
+
+    def sample(self, x, seed: Optional[int] = None):
+        """A copy of ``x`` ``[B, D]`` with every NaN entry drawn, the row as a whole an exact draw from the posterior given
+        its observed entries (which come back bit for bit); an all-NaN batch is unconditional generation.  ``seed``: the
+        seed of the counter-based generator (the same seed gives the same bytes, whatever the batch a row comes in at the
+        same position); None draws one from numpy's global generator."""
+        from deeprob.hip import cnet
+        # (what is wrong with the call itself is reported before what is wrong with where the rows live)
+        if any(node.clt is not None and (node.clt.tree is None or node.clt.params is None) for node in self._nodes()):
+            raise ValueError("The CNet's structure and parameters must be already initialized")
+        if len(x.shape) != 2 or x.shape[1] != len(self.scope):
+            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        return self._run(cnet.sample, x, int(seed))
 
     def likelihood(self, x):
         ll = self.log_likelihood(x)

@@ -185,6 +185,47 @@ int dpc_cnet_log_likelihood(const uint8_t *codes, int64_t b, int d, int n_nodes,
                             const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work,
                             float *out, void *stream);
 
+/* ---- Queries of a cutset network that fill a row in: exact MPE and exact conditional sampling, one launch each ----
+ *
+ * x: [b, d] float32 row major, NaN = unknown; codes: the output of dpc_pack_query for the same rows.  out: [b, d]
+ * float32: an observed entry comes back bit for bit, a NaN entry becomes 0.0 or 1.0 -- except a column that is neither
+ * cut on the chosen path nor in the chosen leaf's scope (hand-built tables only), which is returned as given.
+ * choice: [b] int32 or null, the NODE number of the chosen leaf.  The model is the tables of
+ * dpc_cnet_log_likelihood (M = n_nodes, nodes numbered breadth first, left child before right) and
+ *   node_parent[M]   2 * parent + side (side = which child of the parent the node is), -1 at the root.
+ * Both walk the OR tree depth first exactly as dpc_cnet_log_likelihood does for a row with NaN (a row without NaN
+ * takes the same walk: one path).  Every node returns a pair (value, leaf):
+ *   a leaf           (V(leaf), itself);
+ *   x_col observed   (node_logw[k][x] + V(child x), the leaf child x returned);
+ *   x_col NaN        both children return (value V_c, leaf_c), a_c = node_logw[k][c] + V_c in float64, and
+ *     sampling:  t = lse64(a_0, a_1), p1 = exp(a_1 - t) in float64 (0 when t = -inf); the node returns
+ *                (t, leaf_1 if (double)u(k) < p1 else leaf_0);
+ *     MPE:       (a_1, leaf_1) if a_1 > a_0, else (a_0, leaf_0): a tie goes to child 0.
+ * V(leaf) for sampling is the V(leaf) of dpc_cnet_log_likelihood; for MPE it is the same with R = max in the upward
+ * pass (the gather path if none of the leaf's columns is NaN).  The leaf drawn inside a subtree is an exact draw given
+ * that subtree and the draw at the parent picks between the two sides with their posterior odds, so the pair the root
+ * returns names a leaf with exactly its posterior probability (or the leaf of a most probable completion), in ONE
+ * bottom-up walk.  Then, from that leaf up to the root through node_parent, every NaN cut variable takes the side the
+ * path went; and the leaf's NaN columns are filled in `bfs` order after the leaf's upward pass (R = lse / max): for
+ * position j with parent value xp (row 0 at the leaf's root), a_k = params[j][xp][k] + m_j[k] in float32,
+ *     sampling:  the entry is 1 iff u(M + col_j) < expf(a_1 - lse(a_0, a_1)) in float32: the normalised conditional
+ *                (NOT the expression of dpc_clt_sample, which is exact only without evidence below j);
+ *     MPE:       the entry is 1 iff a_1 > a_0 (the rule of dpc_clt_mpe).
+ * u(i) = the generator of dpc_clt_sample with ctr = (row0 + r) * (M + d) + i: OR node k draws with i = k, column c with
+ * i = M + c, so a row's output depends only on (seed, row0 + r, the row); `row0` lets a caller sample a long batch in
+ * pieces.  levels, max_leaf_d: as for dpc_cnet_log_likelihood; a row whose stack would grow past `levels` gets NaN in
+ * all of out[r] and choice[r] = -1, with no write past the stack.  work: b * (16 * levels + 8 * max_leaf_d) bytes of
+ * scratch, 8-byte aligned: per row the stack of `levels` (float64, int32) entries, one more int32 per level for the
+ * leaf carried upward, and the 2 * max_leaf_d floats of the leaf pass.  b = 0 writes nothing. */
+int dpc_cnq_mpe(const float *x, const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
+                const int32_t *node_child, const int32_t *node_parent, const double *node_logw, const int32_t *leaf_meta,
+                const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work, float *out,
+                int32_t *choice, void *stream);
+int dpc_cnq_sample(const float *x, const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
+                   const int32_t *node_child, const int32_t *node_parent, const double *node_logw, const int32_t *leaf_meta,
+                   const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, uint64_t seed, int64_t row0,
+                   void *work, float *out, int32_t *choice, void *stream);
+
 /* ---- Scored cutset learners (deeprob.spn.learning.cnet_bayesian; reference spn/learning/cnet_bayesian.py) ----
  *
  * learn_cnet_bd / learn_cnet_bic try several candidate cut columns per task and fit a Chow-Liu tree to each

@@ -8,11 +8,17 @@ clock around work that ends in a device synchronise:
                    records read back) and the leaves' host learning (mutual information, Prim, CPTs); the split comes
                    from ``BinaryCNet.fit_profile_`` of the same runs;
     ll_complete    log_likelihood of the training rows, resident on the device;
-    ll_nan         log_likelihood of the same rows with 30 % of the entries NaN.
+    ll_nan         log_likelihood of the same rows with 30 % of the entries NaN;
+    sample_nan     BinaryCNet.sample of those rows with NaN: one exact posterior draw per row, one launch;
+    mpe_nan        deeprob.hip.cnet.mpe of those rows (the tables uploaded per call, as the class's queries do).
 
 The restatement runs once: ``fit`` on all rows, the queries on the first ``--ref-rows`` rows; ``speedup`` compares seconds
 per row.  The device results are checked against it: the OR tree, and the likelihoods of the device model evaluated by
 the restatement's query code.  Writes one JSON line to ``--out`` (default profiles/cnet_bench_line.json) and prints it.
+The two filling queries go beside ``ll_nan`` -- the same rows, the same NaN share, the same walk plus one leaf pass -- into
+a line of their own, ``--queries-out`` (default profiles/cnet_queries_bench_line.json), with their time as a multiple of
+``ll_nan``'s and what was checked of their outputs (observed entries kept, every NaN filled with 0 / 1, the MPE no less
+likely than the sample row by row).
 
     python tools/bench_cnet.py [--rows 20000] [--cols 200] [--ref-rows 4096] [--no-restatement]
 """
@@ -80,6 +86,7 @@ def main():
     ap.add_argument('--ref-rows', type=int, default=4096)
     ap.add_argument('--runs', type=int, default=5)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'cnet_bench_line.json'))
+    ap.add_argument('--queries-out', default=os.path.join(ROOT, 'profiles', 'cnet_queries_bench_line.json'))
     ap.add_argument('--no-restatement', action='store_true')
     args = ap.parse_args()
     import torch
@@ -99,13 +106,30 @@ def main():
     line['fit_split_seconds'] = {k: round(statistics.median(m.fit_profile_[k] for m in models), 5)
                                  for k in ('generations_seconds', 'host_leaf_seconds')}
     todo, results = [('fit', times)], {}
-    for name, fn in (('ll_complete', lambda: model.log_likelihood(xd)), ('ll_nan', lambda: model.log_likelihood(xd_nan))):
+    from deeprob.hip import cnet
+
+    def mpe_nan():
+        return cnet.mpe(model._on_device(xd_nan.device), xd_nan)
+    for name, fn in (('ll_complete', lambda: model.log_likelihood(xd)), ('ll_nan', lambda: model.log_likelihood(xd_nan)),
+                     ('sample_nan', lambda: model.sample(xd_nan, seed=DATA_SEED)), ('mpe_nan', mpe_nan)):
         outs, t = timed(fn, args.runs)
         results[name] = outs[-1]
         todo.append((name, t))
+    queries = {'bench': 'cnet_queries', 'rows': args.rows, 'cols': args.cols, 'nan_share': 0.3, 'runs': args.runs,
+               'hyper': HYPER, 'model': line['model'], 'method': line['method'], 'hip_seconds': {}, 'hip_seconds_all': {}}
     for name, t in todo:
-        line['hip_seconds'][name] = round(statistics.median(t), 5)
-        line['hip_seconds_all'][name] = [round(v, 5) for v in t]
+        into = queries if name in ('sample_nan', 'mpe_nan') else line
+        into['hip_seconds'][name] = round(statistics.median(t), 5)
+        into['hip_seconds_all'][name] = [round(v, 5) for v in t]
+    queries['hip_seconds']['ll_nan'] = line['hip_seconds']['ll_nan']
+    queries['multiple_of_ll_nan'] = {k: round(queries['hip_seconds'][k] / queries['hip_seconds']['ll_nan'], 2)
+                                     for k in ('sample_nan', 'mpe_nan')}
+    observed = ~torch.isnan(xd_nan)
+    drawn, best = results.pop('sample_nan'), results.pop('mpe_nan')
+    queries['checks'] = {
+        'observed_entries_kept': bool(torch.equal(drawn[observed], xd_nan[observed]) and torch.equal(best[observed], xd_nan[observed])),
+        'every_nan_filled_with_0_or_1': bool(((drawn == 0) | (drawn == 1)).all() and ((best == 0) | (best == 1)).all()),
+        'mpe_no_less_likely_than_the_sample': bool((model.log_likelihood(best) >= model.log_likelihood(drawn) - 1e-4).all())}
     if not args.no_restatement:
         from tests import cnet_ref as ref
         n = min(args.ref_rows, args.rows)
@@ -136,6 +160,11 @@ def main():
     text = json.dumps(line)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, 'w') as f:
+        f.write(text + '\n')
+    print(text)
+    text = json.dumps(queries)
+    os.makedirs(os.path.dirname(os.path.abspath(args.queries_out)), exist_ok=True)
+    with open(args.queries_out, 'w') as f:
         f.write(text + '\n')
     print(text)
 
