@@ -92,13 +92,13 @@ __device__ __forceinline__ void leaf_pull(const Leaf &f, const float *t, int64_t
 }
 
 // the upward pass of dpc_clt_log_likelihood (R = lse) or of dpc_clt_mpe (MAX: R = max) over the leaf's columns, ending
-// at the root as the log likelihood does
-template <bool MAX>
+// at the root as the log likelihood does.  COLS = false: a stand-alone tree, position j is column j and f.col is unused.
+template <bool MAX, bool COLS = true>
 __device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
     for (int p = f.d - 1; p >= 1; --p) {
         const int j = f.bfs[p];
         const float *pj = f.params + j * 4;
-        const int cj = q[(int64_t)f.col[j] * B];
+        const int cj = q[(int64_t)(COLS ? f.col[j] : j) * B];
         float m0, m1;
         leaf_pull(f, t, B, j, m0, m1);
         float t0, t1;
@@ -118,11 +118,44 @@ __device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *
     }
     const int j = f.bfs[0];
     const float *pj = f.params + j * 4;
-    const int cj = q[(int64_t)f.col[j] * B];
+    const int cj = q[(int64_t)(COLS ? f.col[j] : j) * B];
     float m0, m1;
     leaf_pull(f, t, B, j, m0, m1);
     if (cj != DPC_MISSING) return pj[cj] + (cj ? m1 : m0);
     return MAX ? fmaxf(pj[0] + m0, pj[1] + m1) : lse2(pj[0] + m0, pj[1] + m1);
+}
+
+// the downward pass of the posterior marginals (dpc_mar_*), after leaf_upward<false>: in `bfs` order the normalised log
+// belief b_j takes the slot of t_j (t_j is read here for the last time; the children's t are still whole when j pulls
+// them), and sink(column, expf(b_j[1])) is called for every NaN position
+template <bool COLS, typename Sink>
+__device__ __forceinline__ void leaf_beliefs(const Leaf &f, const uint8_t *q, int64_t B, float *t, Sink sink) {
+    for (int p = 0; p < f.d; ++p) {
+        const int64_t j = f.bfs[p];
+        const int64_t pa = f.parent[j];
+        const int col = COLS ? f.col[j] : (int)j;
+        const int cj = q[(int64_t)col * B];
+        const float *pj = f.params + j * 4;
+        float m0, m1;
+        leaf_pull(f, t, B, (int)j, m0, m1);
+        const float e0 = cj == 1 ? -INFINITY : 0.f, e1 = cj == 0 ? -INFINITY : 0.f;
+        float a0, a1;
+        if (pa < 0) {
+            a0 = pj[0] + m0 + e0;
+            a1 = pj[1] + m1 + e1;
+        } else {
+            const float bp0 = t[2 * pa * B], bp1 = t[(2 * pa + 1) * B];
+            const float c0 = bp0 == -INFINITY ? -INFINITY : bp0 - t[2 * j * B];
+            const float c1 = bp1 == -INFINITY ? -INFINITY : bp1 - t[(2 * j + 1) * B];
+            a0 = lse2(c0 + pj[0], c1 + pj[2]) + m0 + e0;
+            a1 = lse2(c0 + pj[1], c1 + pj[3]) + m1 + e1;
+        }
+        const float z = lse2(a0, a1);
+        const float b1 = a1 - z;
+        t[2 * j * B] = a0 - z;
+        t[(2 * j + 1) * B] = b1;
+        if (cj == DPC_MISSING) sink(col, expf(b1));
+    }
 }
 
 }  // namespace dpc_detail

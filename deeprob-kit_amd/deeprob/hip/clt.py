@@ -20,7 +20,8 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_c
 
 #: floats of scratch per query launch (128 MiB): a long batch is evaluated in pieces of WORK_FLOATS / (2 D) rows
 WORK_FLOATS = 1 << 25
-#: the oldest ``dpc_abi_version()`` this binding loads: 2 added the ``dpc_cnq_*`` queries of cutset networks
+#: the oldest ``dpc_abi_version()`` this binding loads: 2 added the ``dpc_cnq_*`` queries of cutset networks (3 added the
+#: ``dpc_mar_*`` posterior marginals: a library without them fails in the binding loop of :func:`load_library`)
 ABI_VERSION = 2
 
 
@@ -180,6 +181,8 @@ def _query(tree: DeviceTree, x: torch.Tensor, what: str, seed: int = 0) -> torch
         codes = pack_query(xs)
         if what == 'll':
             call(lib.dpc_clt_log_likelihood, codes.data_ptr(), n, d, *tree.pointers(), work.data_ptr(), os_.data_ptr(), st)
+        elif what == 'marginals':
+            call(lib.dpc_mar_clt, xs.data_ptr(), codes.data_ptr(), n, d, *tree.pointers(), work.data_ptr(), os_.data_ptr(), st)
         elif what == 'mpe':
             call(lib.dpc_clt_mpe, xs.data_ptr(), codes.data_ptr(), n, d, *tree.pointers(), work.data_ptr(), os_.data_ptr(), st)
         else:
@@ -201,3 +204,9 @@ def mpe(tree: DeviceTree, x: torch.Tensor) -> torch.Tensor:
 def sample(tree: DeviceTree, x: torch.Tensor, seed: int) -> torch.Tensor:
     """``[B, D]`` float32: ``x`` with its NaN entries drawn given the observed ones (``dpc_clt_sample``)."""
     return _query(tree, x, 'sample', int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def marginals(tree: DeviceTree, x: torch.Tensor) -> torch.Tensor:
+    """``[B, D]`` float32: ``x`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)``, exact
+    (``dpc_mar_clt``); NaN where the row's evidence has probability zero."""
+    return _query(tree, x, 'marginals')

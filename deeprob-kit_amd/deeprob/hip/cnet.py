@@ -3,9 +3,10 @@
 
 :class:`Generation` is one level of the level-synchronous learner -- the row segments of its tasks, their bit planes,
 counts, scores and the partition into the next level; :class:`DeviceCNet` holds a fitted model as one concatenated
-table, uploaded in one copy; :func:`log_likelihood`, :func:`mpe` and :func:`sample` are the queries (``dpc_cnet_log_likelihood``
-and the ``dpc_cnq_*`` entries: exact MPE and exact conditional sampling, one launch per piece of the batch).  Everything
-takes and returns device tensors; there is no CPU fallback.
+table, uploaded in one copy; :func:`log_likelihood`, :func:`mpe`, :func:`sample` and :func:`marginals` are the queries
+(``dpc_cnet_log_likelihood``, the ``dpc_cnq_*`` entries -- exact MPE and exact conditional sampling -- and ``dpc_mar_cnet``,
+the exact posterior marginals: one launch per piece of the batch).  Everything takes and returns device tensors; there is
+no CPU fallback.
 """
 import numpy as np
 import torch
@@ -133,7 +134,8 @@ class DeviceCNet:
     ``[leaf number, -1]``); ``node_logw`` ``[M, 2]`` float64; ``leaves``: per leaf number ``(cols, bfs, parent, params)``,
     ``cols`` the column of every position of the leaf's scope.  Checked on the host -- the kernel indexes device memory
     with these tables: node 0 roots one binary tree that reaches every node once, and along every path the cut columns and
-    the leaf's columns are distinct columns of ``0 .. d - 1``."""
+    the leaf's columns are distinct columns of ``0 .. d - 1``.  ``covered`` records whether every path also accounts for
+    EVERY column, as a cut or in its leaf's scope -- learned networks always do; :func:`marginals` needs it."""
 
     def __init__(self, d, node_col, node_child, node_logw, leaves, device):
         node_col, node_child = np.asarray(node_col, np.int64), np.asarray(node_child, np.int64)
@@ -159,6 +161,7 @@ class DeviceCNet:
         seen, levels, stack = np.zeros(m, bool), 0, [(0, 1, frozenset(), -1)]
         node_parent = np.full(m, -1, np.int32)
         leaf_seen = np.zeros(len(meta), bool)
+        covered = True
         while stack:
             k, level, used, up = stack.pop()
             ok = 0 <= k < m and not seen[k]
@@ -175,6 +178,7 @@ class DeviceCNet:
                         cols = leaves[l][0]
                         ok = len(set(int(c) for c in cols)) == len(cols) and all(0 <= int(c) < d and int(c) not in used
                                                                                  for c in cols)
+                        covered = covered and len(used) + len(cols) == d
                 else:
                     ok = col < d and col not in used
                     stack += [(int(node_child[k, 1]), level + 1, used | {col}, 2 * k + 1),
@@ -197,6 +201,10 @@ class DeviceCNet:
         self.row_bytes = 12 * self.levels + 8 * self.max_leaf_d
         #: scratch per row of ``dpc_cnq_mpe`` / ``dpc_cnq_sample``: one more int32 per level, the leaf carried upward
         self.query_row_bytes = 16 * self.levels + 8 * self.max_leaf_d
+        #: scratch per row of ``dpc_mar_cnet``: a second float64 per level (the prefix weight) and the D float64 accumulators
+        self.marginals_row_bytes = 20 * self.levels + 8 * self.max_leaf_d + 8 * self.d
+        #: whether every root-to-leaf path accounts for every column, as a cut or in the leaf's scope
+        self.covered = bool(covered)
 
 
 def _query_rows_of(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
@@ -267,3 +275,31 @@ def sample(model: DeviceCNet, x: torch.Tensor, seed: int, return_choice: bool = 
     the drawn leaf."""
     out, choice = _fill(model, x, int(seed) & 0xFFFFFFFFFFFFFFFF, return_choice)
     return (out, choice) if return_choice else out
+
+
+def marginals(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
+    """``[B, D]`` float32: ``x`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)``, exact
+    (``dpc_mar_cnet``); NaN where the row's evidence has probability zero.  A long batch goes in pieces of
+    ``query_rows(model.marginals_row_bytes)`` rows.
+
+    :raises ValueError: If a path of the model leaves a column out (``model.covered`` is false): the sum over the leaves
+                        would not be a marginal."""
+    if not model.covered:
+        raise ValueError("marginals need every root-to-leaf path to account for every column, as a cut or in the leaf's "
+                         "scope: these tables leave a column out on some path")
+    lib = load_library()
+    x = _query_rows_of(model, x)
+    b, d = x.shape
+    st = hip.stream_ptr(x.device)
+    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
+    step = query_rows(model.marginals_row_bytes)
+    work = torch.empty(model.marginals_row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
+    for r0 in range(0, b, step):
+        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
+        n = xs.shape[0]
+        codes = clt.pack_query(xs)
+        call(lib.dpc_mar_cnet, xs.data_ptr(), codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(),
+             model.node_child.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
+             model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d, work.data_ptr(),
+             os_.data_ptr(), st)
+    return out

@@ -3,7 +3,8 @@ estimator, learned and queried on the HIP device through ``libdeeprob_clt.so`` (
 
 ``fit`` counts on the device (``dpc_pack_bits``, ``dpc_pair_counts``) and finishes on the host: float32 priors, joints
 and mutual information in the reference's expressions from exact integer counts, Prim's maximum spanning tree, the
-conditional tables.  ``log_likelihood``, ``mpe`` and ``sample`` run one thread per row on the device.  Inputs follow
+conditional tables.  ``log_likelihood``, ``mpe``, ``sample`` and ``marginals`` (the exact posterior marginal of every NaN
+entry, which the reference does not have) run one thread per row on the device.  Inputs follow
 ``deeprob.spn.algorithms.inference.log_likelihood``: a numpy array is evaluated on the current HIP device and numpy comes
 back, a device tensor stays on its device, a CPU tensor or a missing library raises ``HipError``.
 
@@ -196,6 +197,18 @@ class BinaryCLT(Leaf):
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         return self._run(clt.sample, x, int(seed))
+
+    def marginals(self, x):
+        """A copy of ``x`` ``[B, D]`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)``, exact: one
+        upward and one downward pass per row.  Observed entries come back bit for bit; an all-NaN row gives the prior
+        marginals; a row whose evidence has probability zero gets NaN in its unobserved entries."""
+        from deeprob.hip import clt
+        # (what is wrong with the call itself is reported before what is wrong with where the rows live)
+        if self.tree is None or self.params is None:
+            raise ValueError("The CLT's structure and parameters must be already initialized")
+        if len(x.shape) != 2 or x.shape[1] != len(self.scope):
+            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
+        return self._run(clt.marginals, x)
 
     def moment(self, k: int = 1) -> float:
         raise NotImplementedError("Computation of moments on Binary CLTs not yet implemented")

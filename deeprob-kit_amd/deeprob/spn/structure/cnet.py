@@ -12,7 +12,9 @@ come back.  ``log_likelihood`` is one thread per row: a complete row walks one p
 depth first.  ``sample`` is the same walk in one launch (``dpc_cnq_sample``): every node returns its value and a leaf drawn
 below it, a NaN OR node picks between its two sides with their posterior odds, and the NaN entries are filled along the one
 path of the drawn leaf and inside it -- an exact draw from ``p(x_missing | x_observed)``, an all-NaN batch being unconditional
-generation.  Inputs follow ``BinaryCLT``: numpy in, numpy out; a device tensor stays on its device; a CPU tensor or a
+generation.  ``marginals`` is the walk taken twice in one launch (``dpc_mar_cnet``): the first gives ``log P(e)``, the second
+weighs every consistent leaf with its posterior probability and adds the leaf's own posterior marginals, so that every
+NaN entry comes back as ``p(x_j = 1 | x_observed)``, exact.  Inputs follow ``BinaryCLT``: numpy in, numpy out; a device tensor stays on its device; a CPU tensor or a
 missing library raises ``HipError``.
 
 Two deliberate differences from the reference, both in DESIGN.md §16.  ``fit`` takes ``random_state``: the reference lets
@@ -21,8 +23,8 @@ leaf in breadth-first order, left child before right.  And in ``log_likelihood``
 silently drops a row from the sum at the first OR node whose variable is NaN (cnet.py:226-229).  The scores are float64
 (the reference's are float32), which only matters where two gains tie to float32 precision.
 
-The reference has neither ``sample`` nor ``mpe`` for cutset networks, so there is nothing to reproduce: both are exact here
-(the OR nodes are deterministic).  Exact MPE is built at kernel, ABI and binding level --
+The reference has neither ``sample`` nor ``mpe`` nor ``marginals`` for cutset networks, so there is nothing to reproduce: all
+are exact here (the OR nodes are deterministic).  Exact MPE is built at kernel, ABI and binding level --
 ``deeprob.hip.cnet.mpe(model._on_device(device), x)``, ``dpc_cnq_mpe`` -- and the one-line ``mpe`` method on the class awaits
 a follow-up.  Not built: the xpc learners.  The scored learners ``learn_cnet_bd`` / ``learn_cnet_bic`` are built in
 ``deeprob.spn.learning.cnet_bayesian`` and return a ``BinaryCNet``.
@@ -269,6 +271,18 @@ class BinaryCNet(ORNode):
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         return self._run(cnet.sample, x, int(seed))
+
+    def marginals(self, x):
+        """A copy of ``x`` ``[B, D]`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)``, exact.
+        Observed entries come back bit for bit; an all-NaN row gives the prior marginals; a row whose evidence has
+        probability zero gets NaN in its unobserved entries."""
+        from deeprob.hip import cnet
+        # (what is wrong with the call itself is reported before what is wrong with where the rows live)
+        if any(node.clt is not None and (node.clt.tree is None or node.clt.params is None) for node in self._nodes()):
+            raise ValueError("The CNet's structure and parameters must be already initialized")
+        if len(x.shape) != 2 or x.shape[1] != len(self.scope):
+            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
+        return self._run(cnet.marginals, x)
 
     def likelihood(self, x):
         ll = self.log_likelihood(x)

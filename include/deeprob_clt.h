@@ -226,6 +226,52 @@ int dpc_cnq_sample(const float *x, const uint8_t *codes, int64_t b, int d, int n
                    const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, uint64_t seed, int64_t row0,
                    void *work, float *out, int32_t *choice, void *stream);
 
+/* ---- Posterior marginals: p(x_j = 1 | the row's observed entries) for every NaN entry, exact, one launch each ----
+ *
+ * x: [b, d] float32 row major, NaN = unknown; codes: the output of dpc_pack_query for the same rows.  out: [b, d]
+ * float32: an observed entry comes back bit for bit (its 0.0 or 1.0 is its own marginal), a NaN entry becomes the
+ * posterior probability that it is 1.  A row whose evidence has probability zero (tables that hold -inf) gets NaN in
+ * its unobserved entries.  b = 0 writes nothing.
+ *
+ * The tree (dpc_mar_clt; float32 throughout).  A row with NaN runs the upward pass above with R = lse: t_j[l] for every
+ * j but the root, the same expressions in the same order as dpc_clt_log_likelihood.  Then, in `bfs` order, every j gets
+ * its normalised log belief b_j[k] = log p(x_j = k | e):
+ *   ev_j[k]  = 0, or -inf where x_j is observed and is not k;
+ *   the root:            a_k = (params[root][0][k] + m_root[k]) + ev_root[k];
+ *   a child j of pa:     cav[l] = b_pa[l] - t_j[l], taken as -inf where b_pa[l] is -inf (the belief of pa without
+ *                        what j sent it; the plain difference would be -inf - (-inf)),
+ *                        a_k = (lse(cav[0] + params[j][0][k], cav[1] + params[j][1][k]) + m_j[k]) + ev_j[k];
+ *   b_j[k]   = a_k - lse(a_0, a_1), and a NaN entry j becomes expf(b_j[1]).
+ * m_j is pulled from the children's t as above; b_j takes the slot of t_j, which nothing reads after j (the children's
+ * slots still hold their t when j pulls them), so work is the [2 * d * b] float32 scratch of dpc_clt_log_likelihood. */
+int dpc_mar_clt(const float *x, const uint8_t *codes, int64_t b, int d, const int32_t *bfs, const int32_t *parent,
+                const float *params, const int32_t *child_off, const int32_t *child_idx, float *work, float *out,
+                void *stream);
+
+/* The network (dpc_mar_cnet): the tables of dpc_cnet_log_likelihood, trusted; the result is a marginal only if every
+ * path from the root to a leaf accounts for every column, as a cut or in the leaf's scope (the binding checks it).  A row
+ * with NaN walks the OR tree depth first twice, each walk exactly the walk of dpc_cnet_log_likelihood for a row with NaN.
+ *   First walk:   log P(e) = V(root), KEPT IN float64 (V(leaf) float32 as there: the gather path if none of the leaf's
+ *                 columns is NaN, else the upward pass with R = lse).  log P(e) = -inf: NaN in every unobserved entry.
+ *   Second walk:  node k is entered with the prefix weight p_k in float64, p_root = 0; the child for side c is entered
+ *                 with p_k + node_logw[k][c].  Every node returns S = the sum of pi_l over the leaves below it that
+ *                 are consistent with the row:
+ *     a leaf l        pi_l = exp((p_l + V(l)) - log P(e)) in float64; S = pi_l.  If pi_l > 0 and the leaf holds NaN
+ *                     columns, the downward pass of dpc_mar_clt follows the leaf's upward pass (float32, over the
+ *                     leaf's columns) and every NaN position j of the leaf adds pi_l * (double)expf(b_j[1]) to the
+ *                     accumulator of its column;
+ *     x_col observed  S = S(child x);
+ *     x_col NaN       child 0, then child 1; the accumulator of `col` gets += S(child 1); S = S(child 0) + S(child 1).
+ *   The accumulators are float64, zero before the second walk, added to in the order of the walk; a NaN entry of the row
+ *   becomes its accumulator rounded to float32.
+ * levels, max_leaf_d: as for dpc_cnet_log_likelihood; a row whose stack would grow past `levels` gets NaN in its
+ * unobserved entries, with no write past the stack.  work: b * (20 * levels + 8 * max_leaf_d + 8 * d) bytes of scratch,
+ * 8-byte aligned: per row the stack of `levels` (float64, float64, int32) entries -- the left side's value or sum, the
+ * prefix weight, the node -- the d float64 accumulators and the 2 * max_leaf_d floats of the leaf passes. */
+int dpc_mar_cnet(const float *x, const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
+                 const int32_t *node_child, const double *node_logw, const int32_t *leaf_meta, const int32_t *leaf_ints,
+                 const float *leaf_params, int levels, int max_leaf_d, void *work, float *out, void *stream);
+
 /* ---- Scored cutset learners (deeprob.spn.learning.cnet_bayesian; reference spn/learning/cnet_bayesian.py) ----
  *
  * learn_cnet_bd / learn_cnet_bic try several candidate cut columns per task and fit a Chow-Liu tree to each

@@ -7,7 +7,9 @@ the median of ``--runs`` calls after one warm-up, with a host clock around work 
                    Prim, the CPTs);
     ll_complete    log_likelihood of the 60 000 training rows, resident on the device;
     ll_nan         log_likelihood of the same rows with 30 % of the entries NaN;
-    mpe, sample    on the 30 % NaN rows.
+    mpe, sample    on the 30 % NaN rows;
+    marginals      the posterior marginal of every NaN entry of those rows (checked against the float64 restatement,
+                   tests/marginals_ref.py).
 
 The restatement runs once: ``fit`` on all rows, the queries on the first ``--ref-rows`` rows (it holds a
 [D, 2, rows] float32 message array); ``speedup`` compares seconds per row.  The device results are checked against it on
@@ -37,7 +39,8 @@ for p in (os.path.join(ROOT, 'deeprob-kit_amd'), ROOT):
 import numpy as np  # noqa: E402
 
 DATA_SEED, ROOT_VAR, ALPHA, SAMPLE_SEED = 1, 0, 0.1, 7
-KERNELS = ('pack_bits', 'pack_query', 'pair_counts', 'query_kernel<0>', 'query_kernel<1>', 'query_kernel<2>')
+KERNELS = ('pack_bits', 'pack_query', 'pair_counts', 'query_kernel<0>', 'query_kernel<1>', 'query_kernel<2>',
+           'clt_marginals_kernel')
 
 
 def workload(rows, cols, n_clusters=4, noise=0.2):
@@ -74,7 +77,8 @@ def fit_model(x):
 
 def steps(clt, xd, xd_nan):
     return {'ll_complete': lambda: clt.log_likelihood(xd), 'll_nan': lambda: clt.log_likelihood(xd_nan),
-            'mpe': lambda: clt.mpe(xd_nan), 'sample': lambda: clt.sample(xd_nan, seed=SAMPLE_SEED)}
+            'mpe': lambda: clt.mpe(xd_nan), 'sample': lambda: clt.sample(xd_nan, seed=SAMPLE_SEED),
+            'marginals': lambda: clt.marginals(xd_nan)}
 
 
 def kernel_split(rows, cols):
@@ -137,6 +141,7 @@ def main():
         line['hip_seconds_all'][name] = [round(v, 5) for v in t]
     if not args.no_restatement:
         from tests import clt_ref as ref
+        from tests import marginals_ref as mref
         n = min(args.ref_rows, args.rows)
         t0 = time.perf_counter()
         bfs, tree, params = ref.fit(x, ROOT_VAR, ALPHA)
@@ -145,7 +150,8 @@ def main():
         for name, fn in (('ll_complete', lambda: ref.log_likelihood(bfs, tree, params, x[:n])),
                          ('ll_nan', lambda: ref.log_likelihood(bfs, tree, params, x_nan[:n])),
                          ('mpe', lambda: ref.mpe(bfs, tree, params, x_nan[:n])),
-                         ('sample', lambda: ref.sample_replay(bfs, tree, params, x_nan[:n], SAMPLE_SEED))):
+                         ('sample', lambda: ref.sample_replay(bfs, tree, params, x_nan[:n], SAMPLE_SEED)),
+                         ('marginals', lambda: mref.tree_marginals(bfs, tree, params, x_nan[:n], np.float64))):
             t0 = time.perf_counter()
             want[name] = fn()
             seconds[name] = time.perf_counter() - t0
@@ -166,7 +172,9 @@ def main():
             'mpe_rows_equal_share': float(np.mean((results['mpe'][:n].cpu().numpy() == want['mpe']).all(axis=1))),
             'sample_rows_equal_share_outside_window': float(np.mean(
                 (results['sample'][:n].cpu().numpy() == replay).all(axis=1)[~near])),
-            'sample_rows_inside_window_share': float(np.mean(near))}
+            'sample_rows_inside_window_share': float(np.mean(near)),
+            'marginals_max_abs_err': float(np.max(np.abs(results['marginals'][:n].cpu().numpy() - want['marginals'])))}
+        line['multiple_of_ll_nan'] = {'marginals': round(line['hip_seconds']['marginals'] / line['hip_seconds']['ll_nan'], 2)}
     if not args.no_profile:
         line['kernel_split'] = kernel_split(args.rows, args.cols)
     text = json.dumps(line)

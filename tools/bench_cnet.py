@@ -10,15 +10,17 @@ clock around work that ends in a device synchronise:
     ll_complete    log_likelihood of the training rows, resident on the device;
     ll_nan         log_likelihood of the same rows with 30 % of the entries NaN;
     sample_nan     BinaryCNet.sample of those rows with NaN: one exact posterior draw per row, one launch;
-    mpe_nan        deeprob.hip.cnet.mpe of those rows (the tables uploaded per call, as the class's queries do).
+    mpe_nan        deeprob.hip.cnet.mpe of those rows (the tables uploaded per call, as the class's queries do);
+    marginals_nan  BinaryCNet.marginals of those rows: the posterior marginal of every NaN entry, one launch.
 
 The restatement runs once: ``fit`` on all rows, the queries on the first ``--ref-rows`` rows; ``speedup`` compares seconds
 per row.  The device results are checked against it: the OR tree, and the likelihoods of the device model evaluated by
 the restatement's query code.  Writes one JSON line to ``--out`` (default profiles/cnet_bench_line.json) and prints it.
-The two filling queries go beside ``ll_nan`` -- the same rows, the same NaN share, the same walk plus one leaf pass -- into
+The three filling queries go beside ``ll_nan`` -- the same rows, the same NaN share, the same walk plus one leaf pass -- into
 a line of their own, ``--queries-out`` (default profiles/cnet_queries_bench_line.json), with their time as a multiple of
 ``ll_nan``'s and what was checked of their outputs (observed entries kept, every NaN filled with 0 / 1, the MPE no less
-likely than the sample row by row).
+likely than the sample row by row, the marginals within [0, 1] and their distance from the float64 restatement,
+tests/marginals_ref.py, on the first ``--marginals-ref-rows`` rows).
 
     python tools/bench_cnet.py [--rows 20000] [--cols 200] [--ref-rows 4096] [--no-restatement]
 """
@@ -87,6 +89,7 @@ def main():
     ap.add_argument('--runs', type=int, default=5)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'cnet_bench_line.json'))
     ap.add_argument('--queries-out', default=os.path.join(ROOT, 'profiles', 'cnet_queries_bench_line.json'))
+    ap.add_argument('--marginals-ref-rows', type=int, default=1024)
     ap.add_argument('--no-restatement', action='store_true')
     args = ap.parse_args()
     import torch
@@ -111,25 +114,28 @@ def main():
     def mpe_nan():
         return cnet.mpe(model._on_device(xd_nan.device), xd_nan)
     for name, fn in (('ll_complete', lambda: model.log_likelihood(xd)), ('ll_nan', lambda: model.log_likelihood(xd_nan)),
-                     ('sample_nan', lambda: model.sample(xd_nan, seed=DATA_SEED)), ('mpe_nan', mpe_nan)):
+                     ('sample_nan', lambda: model.sample(xd_nan, seed=DATA_SEED)), ('mpe_nan', mpe_nan),
+                     ('marginals_nan', lambda: model.marginals(xd_nan))):
         outs, t = timed(fn, args.runs)
         results[name] = outs[-1]
         todo.append((name, t))
     queries = {'bench': 'cnet_queries', 'rows': args.rows, 'cols': args.cols, 'nan_share': 0.3, 'runs': args.runs,
                'hyper': HYPER, 'model': line['model'], 'method': line['method'], 'hip_seconds': {}, 'hip_seconds_all': {}}
     for name, t in todo:
-        into = queries if name in ('sample_nan', 'mpe_nan') else line
+        into = queries if name in ('sample_nan', 'mpe_nan', 'marginals_nan') else line
         into['hip_seconds'][name] = round(statistics.median(t), 5)
         into['hip_seconds_all'][name] = [round(v, 5) for v in t]
     queries['hip_seconds']['ll_nan'] = line['hip_seconds']['ll_nan']
     queries['multiple_of_ll_nan'] = {k: round(queries['hip_seconds'][k] / queries['hip_seconds']['ll_nan'], 2)
-                                     for k in ('sample_nan', 'mpe_nan')}
+                                     for k in ('sample_nan', 'mpe_nan', 'marginals_nan')}
     observed = ~torch.isnan(xd_nan)
-    drawn, best = results.pop('sample_nan'), results.pop('mpe_nan')
+    drawn, best, soft = results.pop('sample_nan'), results.pop('mpe_nan'), results.pop('marginals_nan')
     queries['checks'] = {
         'observed_entries_kept': bool(torch.equal(drawn[observed], xd_nan[observed]) and torch.equal(best[observed], xd_nan[observed])),
         'every_nan_filled_with_0_or_1': bool(((drawn == 0) | (drawn == 1)).all() and ((best == 0) | (best == 1)).all()),
-        'mpe_no_less_likely_than_the_sample': bool((model.log_likelihood(best) >= model.log_likelihood(drawn) - 1e-4).all())}
+        'mpe_no_less_likely_than_the_sample': bool((model.log_likelihood(best) >= model.log_likelihood(drawn) - 1e-4).all()),
+        'marginals_keep_observed_entries_and_lie_in_0_1': bool(torch.equal(soft[observed], xd_nan[observed])
+                                                               and ((soft >= 0) & (soft <= 1)).all())}
     if not args.no_restatement:
         from tests import cnet_ref as ref
         n = min(args.ref_rows, args.rows)
@@ -150,6 +156,11 @@ def main():
         def rel(got, ref_values):
             got = got.cpu().numpy().reshape(-1)[:n].astype(np.float64)
             return float(np.max(np.abs(got - ref_values) / np.maximum(1.0, np.abs(ref_values))))
+        from tests import marginals_ref as mref
+        k = min(args.marginals_ref_rows, args.rows)
+        queries['checks']['marginals_max_abs_err'] = float(np.max(np.abs(
+            soft[:k].cpu().numpy() - mref.cnet_marginals(device_model, x_nan[:k], np.float64))))
+        queries['checks']['marginals_rows_checked'] = k
         a, b = ref.structure(restated), ref.structure(device_model)
         line['checks'] = {
             'same_or_tree': bool(np.array_equal(a[0], b[0]) and a[2] == b[2]),
