@@ -1,0 +1,110 @@
+"""ctypes binding of ``libdeeprob_spnq.so`` (the C ABI declared in ``include/deeprob_spnq.h``, prefix ``dpq_``): posterior
+queries on a node-graph SPN -- conditional moments and the posterior of one discrete variable.  The prototypes, the
+``DPQ_*`` constants and the circuit record are read from the header with the parser of ``deeprob.hip``; nothing of them is
+written down a second time.  There is no CPU fallback: a missing library or a CPU tensor raises.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from deeprob import hip
+from deeprob.hip import HipError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_spnq.h'))
+LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_spnq.so'))
+
+
+def _read_header():
+    if not os.path.isfile(HEADER_PATH):
+        raise HipError("deeprob_spnq.h not found at {} -- it is the declaration of the C ABI this binding is built "
+                       "from".format(HEADER_PATH))
+    with open(HEADER_PATH) as f:
+        return hip.parse_header(f.read(), prefix='dpq', header='deeprob_spnq.h')
+
+
+SIGNATURES, CONSTANTS, _STRUCT_FIELDS = _read_header()
+globals().update(CONSTANTS)
+
+#: the header's mirror of ``dpk_flat_spn_circuit``; the record ``FlatSpn.circuit(device)`` builds is passed as it is
+FlatSpnCircuit = type('dpq_flat_spn_circuit', (ctypes.Structure,), {'_fields_': _STRUCT_FIELDS['dpq_flat_spn_circuit']})
+
+_lib = None
+
+
+def load_library() -> ctypes.CDLL:
+    """Load ``libdeeprob_spnq.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.isfile(LIB_PATH):
+        raise HipError(
+            "libdeeprob_spnq.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
+            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
+    lib = ctypes.CDLL(LIB_PATH)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _lib = lib
+    return lib
+
+
+def call(fn, *args) -> int:
+    rc = fn(*args)
+    if rc < 0:
+        msg = load_library().dpq_last_error()
+        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
+    return rc
+
+
+def leaf_table(spn):
+    """``(var_leaf_off [n_features + 1], var_leaf [n_leaves])`` int32: the node ids of the leaves over each variable, in
+    increasing node id (the header's table)."""
+    leaves = np.flatnonzero(spn.kind >= 2)
+    var = spn.arg0[leaves]
+    keep = np.argsort(var, kind='stable')            # (leaves is increasing, so ids stay increasing per variable)
+    off = np.zeros(spn.n_features + 1, np.int32)
+    off[1:] = np.cumsum(np.bincount(var, minlength=spn.n_features))
+    return off, leaves[keep].astype(np.int32)
+
+
+def _device_leaf_table(spn, device):
+    cache = spn.__dict__.setdefault('_leaf_tables', {})      # (structure, not parameters: uploaded once per device)
+    key = str(device)
+    if key not in cache:
+        off, leaf = leaf_table(spn)
+        cache[key] = (torch.from_numpy(off).to(device), torch.from_numpy(leaf).to(device))
+    return cache[key]
+
+
+def flat_spn_posterior(spn, xd: torch.Tensor, mode: int, n_orders: int = 0, var: int = 0, values=None,
+                       force_workspace: bool = False) -> torch.Tensor:
+    """``dpq_flat_spn_posterior`` on the device tensor ``xd [B, D]`` (contiguous float32): ``[n_orders, B, D]`` moments
+    (mode ``DPQ_MODE_MOMENTS``) or ``[B, V]`` probabilities of ``values`` for variable ``var`` (``DPQ_MODE_VALUES``).
+    ``force_workspace``: take the workspace route whatever the circuit's size (the two routes give the same bits)."""
+    if not xd.is_cuda:
+        raise HipError("x lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
+                       "fallback)".format(xd.device))
+    lib = load_library()
+    B, D = xd.shape
+    dev = xd.device
+    flags = DPQ_FLAG_FORCE_WORKSPACE if force_workspace else 0
+    vd = None
+    if mode == DPQ_MODE_VALUES:
+        vd = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float32)).to(dev)
+        out = torch.empty((B, vd.numel()), dtype=torch.float32, device=dev)
+    else:
+        out = torch.empty((n_orders, B, D), dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    rec = spn.circuit(dev)
+    off, leaf = _device_leaf_table(spn, dev)
+    n = call(lib.dpq_flat_spn_posterior_workspace_bytes, B, ctypes.addressof(rec), flags)
+    ws = torch.empty(int(n), dtype=torch.uint8, device=dev) if n > 0 else None
+    call(lib.dpq_flat_spn_posterior, hip.ptr(xd), B, D, ctypes.addressof(rec), hip.ptr(off), hip.ptr(leaf), leaf.numel(),
+         mode, n_orders, var, hip.ptr(vd), 0 if vd is None else vd.numel(), hip.ptr(out), flags, hip.ptr(ws),
+         0 if ws is None else ws.numel(), hip.stream_ptr(dev))
+    return out
