@@ -379,6 +379,45 @@ class RatSpn(ProbabilisticModel):
                                   self._topdown_src(), p0, p1, seed=ops.draw_seed() if seed is None else int(seed))
 
     @torch.no_grad()
+    def posterior_moments(self, x: torch.Tensor, y: Optional[torch.Tensor] = None,
+                          want_var: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Exact ``(E[x_f | e], Var[x_f | e])`` of every NaN entry of ``x`` given the row's observed entries ``e`` (and the
+        class ``y``, when given): the bottom-up pass of ``mpe``, then one top-down launch that sends the posterior flow of
+        every sum node to all of its inputs (csrc/rat/ratspn_moments.hip) and mixes the leaf channels' moments by the flow
+        they receive.  An observed entry comes back as it is, with variance 0.  Without labels a model with several classes
+        answers for the mixture of its classes under the uniform class prior (the one ``sample`` and ``sample_conditional``
+        assume).  A row whose evidence is impossible under the model has NaN in its NaN entries.  For Bernoulli leaves the
+        mean is ``p(x_f = 1 | e)``.  The reference has no counterpart for its tensorized models
+        (``deeprob.spn.algorithms.moments`` is the node-graph path's)."""
+        leaf = self._leaf_params()
+        if leaf is None:
+            raise NotImplementedError('posterior_moments: a user-defined leaf layer ({}) has no one-launch top-down pass'
+                                      .format(type(self.base_layer).__name__))
+        if self.training and (self.in_dropout is not None or self.sum_dropout is not None):
+            raise NotImplementedError('posterior_moments: training mode with in_dropout / sum_dropout set '
+                                      '(call eval() first: the posterior is that of the model without dropout)')
+        from deeprob.hip import rat
+        x = ops.require_device_f32(x, 'x')
+        acts = self._upward_for_mpe(x)
+        if self.out_classes == 1:
+            y = None
+        dist, p0, p1 = leaf
+        mean, var, _ = rat.ratspn_moments(dist, self._fused_ctx, x, y, acts, self._topdown_logw(), self._topdown_src(), p0, p1,
+                                          all_classes=y is None, want_var=want_var)
+        return mean, var
+
+    def expectation(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``E[x_missing | x_observed, y]`` in the NaN entries of ``x``, the observed entries as they are: mean imputation,
+        the completion of least expected squared error.  For a ``BernoulliRatSpn`` this is ``p(x_j = 1 | e)``.  See
+        :meth:`posterior_moments`."""
+        return self.posterior_moments(x, y, want_var=False)[0]
+
+    def variance(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``Var[x_missing | x_observed, y]`` in the NaN entries of ``x``, 0 in the observed ones.  See
+        :meth:`posterior_moments`."""
+        return self.posterior_moments(x, y)[1]
+
+    @torch.no_grad()
     def _mpe_layerwise(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The layer-by-layer form (user-defined leaf layers, training-mode dropout): the layers' own ``mpe`` methods."""
         evidence = x
