@@ -12,7 +12,7 @@
 namespace {
 
 using dpc_detail::lse2;
-using dpc_detail::uniform01;
+using dp_device::counter_uniform;
 
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
                 v = (pj[1] + m1) > (pj[0] + m0);
             } else {
                 const float prob = expf(pj[1] + (pa < 0 ? m1 : (xp ? m1 : m0)));
-                v = uniform01(a.seed, (u64)(a.row0 + r) * (u64)D + (u64)j) < prob;
+                v = counter_uniform(a.seed, (u64)(a.row0 + r) * (u64)D + (u64)j) < prob;
             }
             value = (float)v;
         }

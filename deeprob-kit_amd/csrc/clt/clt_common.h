@@ -1,18 +1,16 @@
-// What the translation units of libdeeprob_clt.so share: the thread-local error text behind dpc_last_error(), the
-// argument and launch checks, lse2 / lse64 of the header's order of operations, the counter-based uniform of the samplers,
-// the shape of the segmented pair-count tile, and a cutset network's leaf: its tables, the gather path and the upward pass
-// (cnet.hip evaluates with them, cnet_queries.hip evaluates and then walks back down).
+// What the translation units of libdeeprob_clt.so share: the library's instance of the shared entry-point scaffolding
+// (error text, checks), lse2 / lse64 of the header's order of operations, the shape of the segmented pair-count tile, and a
+// cutset network's leaf: its tables, the gather path and the upward pass (cnet.hip evaluates with them, cnet_queries.hip
+// evaluates and then walks back down).  The samplers draw with dp_device::counter_uniform (shared/device.h).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 #include "../../../include/deeprob_clt.h"
+#define DP_ENTRY_NS dpc_detail
+#define DP_ENTRY_ELAUNCH DPC_ELAUNCH
+#include "../shared/entry.h"
+#include "../shared/device.h"
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "libdeeprob_clt is written for gfx950 (MI355X)"
-#endif
+#define DPC_REQUIRE(cond, ...) DP_REQUIRE(cond, DPC_EINVAL, __VA_ARGS__)
+#define DPC_LAUNCH DP_LAUNCH
 
 namespace dpc_detail {
 
@@ -24,16 +22,6 @@ constexpr int kPairWords = 32;
 constexpr int kMaxGridZ = 65535;
 constexpr int64_t kMaxGridX = 2147483647;
 
-// (an inline variable: one copy for the whole library)
-inline thread_local char g_error[512] = "";
-
-inline void set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-
 __device__ __forceinline__ float lse2(float a, float b) {
     const float hi = fmaxf(a, b), lo = fminf(a, b);
     if (hi == -INFINITY) return -INFINITY;
@@ -44,15 +32,6 @@ __device__ __forceinline__ double lse64(double x, double y) {
     const double hi = fmax(x, y), lo = fmin(x, y);
     if (hi == -INFINITY) return -INFINITY;
     return hi + log1p(exp(lo - hi));
-}
-
-// the generator of dpk_flat_spn_topdown (csrc/flat_spn_queries.hip)
-__device__ __forceinline__ float uniform01(unsigned long long seed, unsigned long long ctr) {
-    unsigned long long z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
 }
 
 // ---- a leaf of a cutset network: one thread per row, codes as q[col * B], the pass's state as t[(2 j + l) * B] ----------
@@ -159,22 +138,3 @@ __device__ __forceinline__ void leaf_beliefs(const Leaf &f, const uint8_t *q, in
 }
 
 }  // namespace dpc_detail
-
-#define DPC_REQUIRE(cond, ...)                  \
-    do {                                        \
-        if (!(cond)) {                          \
-            dpc_detail::set_error(__VA_ARGS__); \
-            return DPC_EINVAL;                  \
-        }                                       \
-    } while (0)
-
-#define DPC_LAUNCH(what, ...)                                                  \
-    do {                                                                       \
-        (void)hipGetLastError();                                               \
-        hipLaunchKernelGGL(__VA_ARGS__);                                       \
-        hipError_t e__ = hipGetLastError();                                    \
-        if (e__ != hipSuccess) {                                               \
-            dpc_detail::set_error("%s: %s", (what), hipGetErrorString(e__));   \
-            return DPC_ELAUNCH;                                                \
-        }                                                                      \
-    } while (0)

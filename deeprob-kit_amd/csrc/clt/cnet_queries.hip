@@ -22,7 +22,7 @@ using dpc_detail::leaf_pull;
 using dpc_detail::leaf_upward;
 using dpc_detail::lse2;
 using dpc_detail::lse64;
-using dpc_detail::uniform01;
+using dp_device::counter_uniform;
 using dpc_detail::kMaxGridX;
 
 typedef unsigned long long u64;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kRowThreads) void cnet_fill_kernel(const QueryArgs 
             } else {
                 const double t = lse64(a0, a1);
                 const double p1 = t == -INFINITY ? 0.0 : exp(a1 - t);
-                right = (double)uniform01(a.seed, ctr0 + (u64)k) < p1;
+                right = (double)counter_uniform(a.seed, ctr0 + (u64)k) < p1;
                 ret = t;
             }
             if (!right) ret_leaf = lf[depth * B];
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kRowThreads) void cnet_fill_kernel(const QueryArgs 
                 v = a1 > a0;
             } else {
                 const float p1 = expf(a1 - lse2(a0, a1));
-                v = uniform01(a.seed, ctr0 + (u64)a.n_nodes + (u64)col) < p1;
+                v = counter_uniform(a.seed, ctr0 + (u64)a.n_nodes + (u64)col) < p1;
             }
             o[col] = __float_as_uint((float)v);
         }

@@ -33,10 +33,10 @@
 //   Pixels out of scope.  A pixel that no path reaches (a 'valid' stride-2 level of an odd map drops its last row and column)
 //     is returned as given: its evidence value, or NaN when everything is drawn; its entry of `choice` is -1.
 //   Inverse CDF.  target = u * total, the first n with target < c(n) in index order, the last input when rounding leaves
-//     none; total and c(n) are fp32 sums in index order (a node of more than 64 inputs: the wave scan of
-//     csrc/ratspn_topdown.hip, in-order sums in contiguous lane chunks, then a scan over the lanes).
-//   Draws.  u(ctr) = the library's counter-based uniform td_uniform(seed, ctr), ctr = row * slots_per_row + slot; slot 0 is
-//     the root's, slot base_t + h * Wout_{t-1} + w that of sum layer t at (h, w) (base_1 = 1, base_{t+1} = base_t +
+//     none; total and c(n) are fp32 sums in index order (a node of more than 64 inputs:
+//     dp_device::wave_inverse_cdf, in-order sums in contiguous lane chunks, then a scan over the lanes).
+//   Draws.  u(ctr) = dp_device::counter_uniform(seed, ctr) (shared/device.h), ctr = row * slots_per_row + slot; slot 0 is the
+//     root's, slot base_t + h * Wout_{t-1} + w that of sum layer t at (h, w) (base_1 = 1, base_{t+1} = base_t +
 //     Hout_{t-1} Wout_{t-1}), slots base_L + 2 ((c H + h) W + w), + 1 the two uniforms of leaf entry (c, h, w).  A row's
 //     output depends on (seed, row index, y) and its evidence only.
 //   Mode 1 (no evidence) takes every activation as log 1: act == null, every draw is by the bare weights, no bottom-up pass.
@@ -50,9 +50,13 @@
 // inputs, the root Cr Hr Wr) is scanned by a wave.  The scores are recomputed for every pass over them rather than kept:
 // one sample's maps are a few KiB, hot in L1 / L2 after the first pass, and nothing is indexed dynamically in registers.
 #include "dgc_common.h"
+#include "../shared/device.h"
 #include <algorithm>
 
 namespace dpg_detail {
+
+using dp_device::wave_inverse_cdf;
+using dp_device::wave_max_nan;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -111,52 +115,7 @@ __device__ __forceinline__ void activate(const Level &g, int oc, int oh, int ow,
     }
 }
 
-// NaN-propagating maximum over the wave (an impossible or undefined node must be seen, not skipped)
-__device__ __forceinline__ float wave_max_nan(float m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float t = __shfl_xor(m, o, 64);
-        m = (t > m || t != t) ? t : m;
-    }
-    return m;
-}
-
-// inverse CDF in index order over the non-negative weight(n), by a wave: lane l owns the contiguous chunk [l ch, (l + 1) ch)
-template <typename WeightFn>
-__device__ __forceinline__ int wave_inverse_cdf(int count, int lane, float u, WeightFn weight) {
-    const int ch = (count + 63) / 64;
-    const int n0 = min(lane * ch, count), n1 = min(n0 + ch, count);
-    float s = 0.f;
-    for (int n = n0; n < n1; ++n) s += weight(n);
-    float inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const float total = __shfl(inc, 63, 64);
-    const float target = u * total;
-    const unsigned long long hit = __ballot(target < inc && n1 > n0);
-    int pick = count - 1;                          // (target >= total by rounding: the last input)
-    if (hit != 0ull) {
-        const int owner = __ffsll((long long)hit) - 1;
-        int mine = n1 - 1;
-        if (lane == owner) {
-            float c = inc - s;
-            for (int n = n0; n < n1; ++n) {
-                c += weight(n);
-                if (target < c) {
-                    mine = n;
-                    break;
-                }
-            }
-        }
-        pick = __shfl(mine, owner, 64);
-    }
-    return pick;
-}
-
-// the same by one lane
+// inverse CDF in index order over the non-negative weight(n) by one lane: dp_device::wave_inverse_cdf without the wave
 template <typename WeightFn>
 __device__ __forceinline__ int lane_inverse_cdf(int count, float u, WeightFn weight) {
     float total = 0.f;
@@ -227,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
             const float *A = POSTERIOR ? a.act[L - 1] + b * ((int64_t)g.cin * g.hin * g.win) : nullptr;
             const float *lw = a.logw[L] + (int64_t)cls * count;
             const int n = wave_choose<POSTERIOR>(
-                count, lane, td_uniform(a.seed, ctr0),
+                count, lane, dp_device::counter_uniform(a.seed, ctr0),
                 [&](int q) {
                     const int oc = q / hw, p = q - oc * hw, oh = p / g.wout;
                     return prod_value(g, A, oc, oh, p - oh * g.wout) + lw[q];
@@ -252,7 +211,7 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                     const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
                     const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
                     const int c = wave_choose<POSTERIOR>(
-                        count, lane, td_uniform(a.seed, ctr + (unsigned)p),
+                        count, lane, dp_device::counter_uniform(a.seed, ctr + (unsigned)p),
                         [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
                         [&](int n) { return lw[(int64_t)n * hw]; });
                     if (lane == 0) activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
@@ -262,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                     const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
                     const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
                     const int c = lane_choose<POSTERIOR>(
-                        count, td_uniform(a.seed, ctr + (unsigned)p),
+                        count, dp_device::counter_uniform(a.seed, ctr + (unsigned)p),
                         [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
                         [&](int n) { return lw[(int64_t)n * hw]; });
                     activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
@@ -284,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                 if (xv != xv) {
                     const int64_t po = (int64_t)k * CHW + f;
                     const unsigned long long slot = ctr0 + a.base[L] + 2ull * (unsigned long long)f;
-                    const float u1 = td_uniform(a.seed, slot), u2 = td_uniform(a.seed, slot + 1ull);
+                    const float u1 = dp_device::counter_uniform(a.seed, slot), u2 = dp_device::counter_uniform(a.seed, slot + 1ull);
                     const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.28318530717958647692f * u2);
                     out[f] = fmaf(a.scale[po], z, a.loc[po]);
                 }
@@ -293,12 +252,6 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
         // (the lists and their counters are rewritten only after every thread has passed the reads above)
         __syncthreads();
     }
-}
-
-int cus() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
 }
 
 }  // namespace dpg_detail
@@ -383,7 +336,7 @@ extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H,
         DPG_REQUIRE(a.logw[t], "dpg_dgcspn_topdown: log-weights of level %d missing", t);
     }
     const size_t lds = (size_t)2 * a.cap * sizeof(int);
-    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)cus() * 8);
+    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)device_cus() * 8);
     if (mode == DPG_MODE_POSTERIOR)
         DPG_LAUNCH("dgcspn_topdown_kernel<true>", dgcspn_topdown_kernel<true>, dim3(grid), dim3(kThreads), lds,
                    (hipStream_t)stream, a);

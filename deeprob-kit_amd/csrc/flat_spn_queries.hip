@@ -20,7 +20,7 @@
 // of the first largest probability, Uniform start, Gaussian mean; sample -- Bernoulli u1 < p, Categorical inverse CDF over
 // the float32 probabilities in category order (same rule as the branch), Uniform start + width u1, Gaussian
 // mean + stddev sqrt(-2 log(1 - u1)) cos(2 pi u2).
-// Counter layout of the draws (a test replays it): u(ctr) = (splitmix64(seed + ctr * 0x9E3779B97F4A7C15) >> 40) / 2^24 with
+// Counter layout of the draws (a test replays it): u(ctr) = dp_device::counter_uniform(seed, ctr) (shared/device.h) with
 // ctr = b * K + slot, K = n_sum + 2 n_vars; slot s = the branch of the sum node with sum_index s, slots n_sum + 2 v and
 // n_sum + 2 v + 1 = u1, u2 of variable v's leaf.
 //
@@ -34,6 +34,7 @@
 // thread its strided share, a butterfly over the wave, the waves in order: no atomics, bitwise reproducible -- and applies
 // the update to its own parameters (raw and derived).  No work-group reads a parameter another one writes.
 #include "common.h"
+#include "shared/device.h"
 #include <math.h>
 
 namespace dpk {
@@ -45,6 +46,7 @@ constexpr int kLdsBytes = 65536;
 constexpr int kUpdThreads = 256;
 using Circuit = dpk_flat_spn_circuit;
 typedef unsigned long long u64;
+using dp_device::counter_uniform;
 
 // value of node i from its children's rows / its input (flat_spn.hip's node functions)
 template <class Load>
@@ -87,14 +89,6 @@ __device__ __forceinline__ float node_value(const Circuit &c, int i, int kind, c
         }
     }
     return fmaxf(v, kFloor);
-}
-
-__device__ __forceinline__ float uniform01(u64 seed, u64 ctr) {
-    u64 z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
 }
 
 __device__ __forceinline__ u64 wave_uniform(u64 v) {
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(64) void flat_topdown_kernel(const TopdownArgs a) {
                 // ll + log w has absorbed log w) still follow the weights
                 float total = 0.f;
                 for (int j = 0; j < nc; ++j) total += expf((load(cidx[c0 + j]) - bl) + (c.child_logw[c0 + j] - bw));
-                const float target = uniform01(a.seed, ctr0 + (u64)s) * total;
+                const float target = counter_uniform(a.seed, ctr0 + (u64)s) * total;
                 float cum = 0.f;
                 int last = br;
                 bool found = false;
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(64) void flat_topdown_kernel(const TopdownArgs a) {
                     }
                 } else {
                     const u64 slot = ctr0 + (u64)c.n_sum + 2ull * (u64)var;
-                    const float u1 = uniform01(a.seed, slot);
+                    const float u1 = counter_uniform(a.seed, slot);
                     if (kind == kBernoulli) {
                         fill = u1 < (float)c.raw0[i] ? 1.f : 0.f;
                     } else if (kind == kCategorical) {
@@ -245,7 +239,7 @@ __global__ __launch_bounds__(64) void flat_topdown_kernel(const TopdownArgs a) {
                     } else if (kind == kUniform) {
                         fill = fmaf((float)c.raw1[i], u1, (float)c.raw0[i]);
                     } else {
-                        const float u2 = uniform01(a.seed, slot + 1ull);
+                        const float u2 = counter_uniform(a.seed, slot + 1ull);
                         const float z = sqrtf(-2.f * logf(1.f - u1)) * cospif(2.f * u2);
                         fill = fmaf((float)c.raw1[i], z, (float)c.raw0[i]);
                     }

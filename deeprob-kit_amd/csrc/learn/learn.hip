@@ -1,27 +1,7 @@
 // libdeeprob_learn.so: the statistics of LearnSPN for discrete data, segmented over the tasks of one generation
 // (include/deeprob_learn.h).  Built with -ffp-contract=off: the float64 expressions below are evaluated operation by
 // operation, in the order the header states, so that a host restatement in the same order reproduces them.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include "../../../include/deeprob_learn.h"
 #include "learn_common.h"
-
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "libdeeprob_learn is written for gfx950 (MI355X)"
-#endif
-
-namespace {
-thread_local char g_error[512] = "";
-}
-
-void dpl_detail::set_error(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
 
 namespace {
 
@@ -377,7 +357,7 @@ bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
 
 extern "C" {
 
-const char *dpl_last_error(void) { return g_error; }
+const char *dpl_last_error(void) { return dpl_detail::g_error; }
 int dpl_abi_version(void) { return 3; }
 
 int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,

@@ -1,33 +1,13 @@
-// What the sources of libdeeprob_learn.so share: the thread-local error text behind dpl_last_error() (defined in
-// learn.hip), the argument / launch checks of the entry points, the in-order block sum and the two k-means kernels that
-// are the same for one-hot and for float columns.
+// What the sources of libdeeprob_learn.so share: the library's instance of the shared entry-point scaffolding (error
+// text, checks), the in-order block sum and the two k-means kernels that are the same for one-hot and for float columns.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include "../../../include/deeprob_learn.h"
+#define DP_ENTRY_NS dpl_detail
+#define DP_ENTRY_ELAUNCH DPL_ELAUNCH
+#include "../shared/entry.h"
 
-namespace dpl_detail {
-void set_error(const char *fmt, ...);
-}
-
-#define DPL_REQUIRE(cond, ...)                \
-    do {                                      \
-        if (!(cond)) {                        \
-            dpl_detail::set_error(__VA_ARGS__); \
-            return DPL_EINVAL;                \
-        }                                     \
-    } while (0)
-
-#define DPL_LAUNCH(what, ...)                                                  \
-    do {                                                                       \
-        (void)hipGetLastError();                                               \
-        hipLaunchKernelGGL(__VA_ARGS__);                                       \
-        hipError_t e__ = hipGetLastError();                                    \
-        if (e__ != hipSuccess) {                                               \
-            dpl_detail::set_error("%s: %s", (what), hipGetErrorString(e__));   \
-            return DPL_ELAUNCH;                                                \
-        }                                                                      \
-    } while (0)
+#define DPL_REQUIRE(cond, ...) DP_REQUIRE(cond, DPL_EINVAL, __VA_ARGS__)
+#define DPL_LAUNCH DP_LAUNCH
 
 namespace dpl_detail {
 constexpr int kThreads = 256;

@@ -1,9 +1,6 @@
 // libdeeprob_learn.so, continuous data: the statistics of LearnSPN on all-Gaussian data, segmented over the tasks of one
 // generation (include/deeprob_learn.h, last section).  Built with -ffp-contract=off like learn.hip: every float64
 // expression is evaluated operation by operation in the order the header states.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../../include/deeprob_learn.h"
 #include "learn_common.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)

@@ -38,9 +38,13 @@
 //     not with |loc|; ref is added once, at the end.  The table of the repetition is also what leaf_flow receives.
 // Every sum has a fixed order that depends on the shape only: the same row gives the same bits in any batch and grid.
 #include "rat_common.h"
+#include "../shared/device.h"
 #include <algorithm>
 
 namespace dpr_detail {
+
+using dp_device::wave_max_nan;
+using dp_device::wave_sum;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -62,23 +66,6 @@ struct MomentsArgs {
     float *mean, *var, *leaf_flow;          // [B, D], [B, D] or null, [B, reps 2^depth, I] or null
     int even_floats, odd_floats;            // sizes of the two flow tables
 };
-
-// NaN-propagating maximum over the wave (an impossible or undefined row must be seen, not skipped)
-__device__ __forceinline__ float wave_max_nan(float m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float t = __shfl_xor(m, o, 64);
-        m = (t > m || t != t) ? t : m;
-    }
-    return m;
-}
-
-// (a butterfly: every lane ends with the same bits)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ float block_max_nan(float m, float *red) {
     m = wave_max_nan(m);
@@ -314,12 +301,6 @@ __global__ __launch_bounds__(kThreads) void ratspn_moments_kernel(const MomentsA
     }
 }
 
-static int cus() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    return (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-}
-
 }  // namespace dpr_detail
 
 using namespace dpr_detail;
@@ -376,7 +357,7 @@ extern "C" int dpr_ratspn_moments(int32_t dist, int64_t B, int32_t D, int32_t de
         DPR_REQUIRE(e == hipSuccess, DPR_ELAUNCH, "hipFuncSetAttribute(max dynamic LDS = %lld): %s", (long long)lds,
                     hipGetErrorString(e));
     }
-    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)cus() * 8);
+    const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)device_cus() * 8);
     DPR_LAUNCH("ratspn_moments_kernel", ratspn_moments_kernel, dim3(grid), dim3(kThreads), (size_t)lds, (hipStream_t)stream, a);
     return DPR_OK;
 }

@@ -13,8 +13,8 @@
 // arithmetic (offset -> offset / N, offset % N), and the leaf step writes x[b, f] for every variable straight in variable
 // order through `src` (= the reference's inv_mask with the dummy variables dropped, unpad_samples).
 //
-// Sampling draws are counter based (the library's splitmix64 hash, common.h: dropout_hit uses the same), so that a test can
-// replay them: u(ctr) = (splitmix64(seed + ctr * golden) >> 40) / 2^24 with ctr = b * K + slot, K = 2^depth + 2 D;
+// Sampling draws are counter based, so that a test can replay them: u(ctr) = dp_device::counter_uniform(seed, ctr)
+// (shared/device.h; dropout_hit of common.h hashes the same way) with ctr = b * K + slot, K = 2^depth + 2 D;
 // slot 1 = the root's choice, slot G + g = the choice of region g (of G) of a sum level, slots 2^depth + 2 f, + 1 = the two
 // uniforms of variable f's leaf (Box-Muller: z = sqrt(-2 log(1 - u1)) cos(2 pi u2); Bernoulli: u1 < p).  A categorical
 // choice is the inverse CDF over exp(log-softmax weights) in index order.
@@ -36,10 +36,15 @@
 // activations of one sample are a few KiB, hot in L1 / L2 after the first pass, and a count of 2048 would need 32 registers a
 // lane.  The leaves are those of mode 1 with the observed x[b, f] kept.
 #include "common.h"
+#include "shared/device.h"
 #include <math.h>
 #include <algorithm>
 
 namespace dpk {
+
+using dp_device::counter_uniform;
+using dp_device::wave_inverse_cdf;
+using dp_device::wave_max_nan;
 
 constexpr int kTdMaxDepth = 10;      // 2^depth <= in_features (RegionGraph): 784 variables allow depth 9
 
@@ -58,14 +63,6 @@ struct TopDownArgs {
     int *choice;                     // optional [B, 1 + 2^depth]: repetition, then the leaf channel chosen per region
 };
 
-__device__ __forceinline__ float td_uniform(unsigned long long seed, unsigned long long ctr) {
-    unsigned long long z = seed + ctr * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(unsigned)(z >> 40) * (1.0f / 16777216.0f);
-}
-
 // first maximum over the wave: (v, n) pairs, larger v wins, equal v -> smaller n
 __device__ __forceinline__ void wave_argmax(float &v, int &n) {
 #pragma unroll
@@ -76,51 +73,6 @@ __device__ __forceinline__ void wave_argmax(float &v, int &n) {
         v = take ? ov : v;
         n = take ? on : n;
     }
-}
-
-// NaN-propagating maximum over the wave (mode 2: an impossible or undefined node must be seen, not skipped)
-__device__ __forceinline__ float wave_max_nan(float m) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float t = __shfl_xor(m, o, 64);
-        m = (t > m || t != t) ? t : m;
-    }
-    return m;
-}
-
-// inverse CDF in index order over the non-negative weight(n): lane l owns the contiguous chunk [l ch, (l + 1) ch)
-template <typename WeightFn>
-__device__ __forceinline__ int td_inverse_cdf(int count, int lane, float u, WeightFn weight) {
-    const int ch = (count + 63) / 64;
-    const int n0 = min(lane * ch, count), n1 = min(n0 + ch, count);
-    float s = 0.f;
-    for (int n = n0; n < n1; ++n) s += weight(n);
-    float inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    const float total = __shfl(inc, 63, 64);
-    const float target = u * total;
-    const unsigned long long hit = __ballot(target < inc && n1 > n0);
-    int pick = count - 1;                          // (target >= total by rounding: the last input)
-    if (hit != 0ull) {
-        const int owner = __ffsll((long long)hit) - 1;
-        int mine = n1 - 1;
-        if (lane == owner) {
-            float c = inc - s;
-            for (int n = n0; n < n1; ++n) {
-                c += weight(n);
-                if (target < c) {
-                    mine = n;
-                    break;
-                }
-            }
-        }
-        pick = __shfl(mine, owner, 64);
-    }
-    return pick;
 }
 
 // One node's choice among `count` inputs: value(n) = its score (mpe) / its log-weight (sample) / its score relative to the
@@ -148,9 +100,9 @@ __device__ __forceinline__ int td_choose(int mode, int count, int lane, float u,
         }
         m = wave_max_nan(m);
         // (wave-uniform; false for -inf and for NaN: then the bare weights below)
-        if (m > -INFINITY) return td_inverse_cdf(count, lane, u, [&](int n) { return expf(score(n) - m); });
+        if (m > -INFINITY) return wave_inverse_cdf(count, lane, u, [&](int n) { return expf(score(n) - m); });
     }
-    return td_inverse_cdf(count, lane, u, [&](int n) { return expf(logw(n)); });
+    return wave_inverse_cdf(count, lane, u, [&](int n) { return expf(logw(n)); });
 }
 
 // POSTERIOR = false: modes 0 and 1; true: mode 2
@@ -174,7 +126,7 @@ __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a
             const float *A = a.act[t] ? a.act[t] + b * (int64_t)R * N : nullptr;
             const float *lw = a.logw[a.depth] + (int64_t)cls * a.reps * NN;
             const int n = td_choose<POSTERIOR>(
-                a.mode, a.reps * NN, lane, a.mode ? td_uniform(a.seed, ctr0 + 1) : 0.f,
+                a.mode, a.reps * NN, lane, a.mode ? counter_uniform(a.seed, ctr0 + 1) : 0.f,
                 [&](int q) {
                     const int p = q / NN, e = q - p * NN, i = e / N, j = e - i * N;
                     return (A[(2 * p) * N + i] + A[(2 * p + 1) * N + j]) + lw[q];
@@ -199,7 +151,7 @@ __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a
                 const int g = rep * G + gl, o = cur[gl];
                 const float *lw = a.logw[t] + ((int64_t)g * a.S + o) * NN;
                 const int n = td_choose<POSTERIOR>(
-                    a.mode, NN, lane, a.mode ? td_uniform(a.seed, ctr0 + (unsigned long long)(G + gl)) : 0.f,
+                    a.mode, NN, lane, a.mode ? counter_uniform(a.seed, ctr0 + (unsigned long long)(G + gl)) : 0.f,
                     [&](int q) {
                         const int i = q / N, j = q - i * N;
                         return (A[(2 * g) * N + i] + A[(2 * g + 1) * N + j]) + lw[q];
@@ -234,9 +186,9 @@ __global__ __launch_bounds__(256) void ratspn_topdown_kernel(const TopDownArgs a
                     // the mode: Normal -> loc; Bernoulli -> [sigmoid(logit) >= 0.5] (ratspn.py:130, distribution means)
                     v = a.dist == 0 ? q0 : ((1.f / (1.f + expf(-q0))) >= 0.5f ? 1.f : 0.f);
                 } else {
-                    const float u1 = td_uniform(a.seed, ctr0 + (unsigned long long)G0 + 2ull * (unsigned long long)f);
+                    const float u1 = counter_uniform(a.seed, ctr0 + (unsigned long long)G0 + 2ull * (unsigned long long)f);
                     if (a.dist == 0) {
-                        const float u2 = td_uniform(a.seed, ctr0 + (unsigned long long)G0 + 2ull * (unsigned long long)f + 1ull);
+                        const float u2 = counter_uniform(a.seed, ctr0 + (unsigned long long)G0 + 2ull * (unsigned long long)f + 1ull);
                         const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.28318530717958647692f * u2);
                         v = fmaf(a.p1[po], z, q0);
                     } else {

@@ -5,105 +5,35 @@ code.  There is no CPU / PyTorch fallback: if the shared library is missing, or 
 a contiguous fp32 tensor on a HIP device, the call raises.  PyTorch is used for device memory,
 streams and ``torch.distributed`` only.
 """
-import ctypes
-import os
-import re
 from typing import Optional
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get(  # DEEPROB_HIP_LIB: measurement builds of the same ABI (profiles/README)
-    'DEEPROB_HIP_LIB', os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_hip.so')))
+from deeprob.hip._binding import Binding, HipError, bound_module, parse_header  # noqa: F401  (re-exported)
 
+# ---- the native libraries: one Binding per header, one shared object per exported prefix ----------------------------
+# Each module of this package (learn, clt, dgc, spnq, rat, slice) takes its binding from here and adds its operators;
+# BINDINGS is what __graft_entry__.build() checks and what the export test runs over.  A new library is one line here.
+MAIN = Binding('hip', 'dpk', env='DEEPROB_HIP_LIB')      # DEEPROB_HIP_LIB: measurement builds (profiles/README)
+SLICE = Binding('slice', 'dps', onto=MAIN)               # host-side knobs of a kernel that lives in libdeeprob_hip.so
+LEARN = Binding('learn', 'dpl')
+# 2 added the ``dpc_cnq_*`` queries of cutset networks (3 added the ``dpc_mar_*`` posterior marginals: a library without
+# them fails when its symbols are bound)
+CLT = Binding('clt', 'dpc', min_abi=2)
+DGC = Binding('dgc', 'dpg')
+SPNQ = Binding('spnq', 'dpq')
+RAT = Binding('rat', 'dpr', not_implemented='DPR_EUNSUPPORTED')
+BINDINGS = (MAIN, SLICE, LEARN, CLT, DGC, SPNQ, RAT)
 
-class HipError(RuntimeError):
-    """Raised when the native library or its header is missing, or a C-ABI call reports a failure."""
-
-
-# ---- the C ABI: include/deeprob_hip.h is its only declaration -------------------------------------------------------
-# The prototypes, the DPK_* constants and the argument structs below are read from the header when this module is
-# imported; nothing of them is written down a second time.  The header is regular C: comments, `#define NAME value`,
-# `typedef struct { ... } name;` and one prototype per `;`.
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_hip.h'))
-
-_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'uint32_t': ctypes.c_uint32,
-            'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float, 'double': ctypes.c_double}
-
-
-def _ctype(decl: str, named: bool, where: str, header: str = 'deeprob_hip.h'):
-    """ctypes type of ``[const] type [*...] [name]``: every pointer is a ``c_void_p``, a scalar must be a known word."""
-    if '*' in decl:
-        return ctypes.c_void_p
-    words = re.sub(r'\bconst\b', ' ', decl).split()
-    if named and len(words) > 1:
-        words = words[:-1]
-    if len(words) != 1 or words[0] not in _SCALARS:
-        raise HipError("{}: cannot read the type of '{}' in {}".format(header, decl.strip(), where))
-    return _SCALARS[words[0]]
-
-
-def parse_header(text: str, prefix: str = 'dpk', header: str = 'deeprob_hip.h'):
-    """``(signatures, constants, structs)`` of a header text: ``{name: (restype, argtypes)}``, ``{DPK_NAME: int}`` and
-    ``{struct name: [(field, ctype)]}``.  Raises HipError on anything it does not understand -- it never guesses.
-    ``prefix``: what the entry points (lower case) and constants (upper case) of this header begin with; ``header``: its
-    name in error messages."""
-    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
-    constants = {}
-    for m in re.finditer(r'^#define\s+(' + prefix.upper() + r'_\w+)[ \t]+(.*)$', text, re.M):
-        value = re.fullmatch(r'\(?(-?\d+)u?\)?', m.group(2).strip())
-        if value is None:
-            raise HipError("{}: cannot read the value '{}' of {}".format(header, m.group(2).strip(), m.group(1)))
-        constants[m.group(1)] = int(value.group(1))
-    text = re.sub(r'^\s*#.*$', '', text, flags=re.M)
-    structs = {}
-    for m in re.finditer(r'typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;', text, re.S):
-        fields = []
-        for line in filter(None, (l.strip() for l in m.group(1).split(';'))):
-            first, *more = line.split(',')
-            base = re.sub(r'[\s\*]*\w+\s*$', '', first)          # the type words in front of the first declarator
-            for d in [first[len(base):]] + more:
-                fields.append((d.replace('*', '').strip(), _ctype(base + ' ' + d, True, 'struct ' + m.group(2), header)))
-        structs[m.group(2)] = fields
-    text = re.sub(r'typedef\s+struct\s*\w*\s*\{.*?\}\s*\w+\s*;', '', text, flags=re.S)
-    text = re.sub(r'extern\s+"C"\s*\{', '', text)
-    signatures = {}
-    for stmt in filter(None, (s.strip() for s in text.split(';'))):
-        if stmt == '}':            # (closes extern "C")
-            continue
-        m = re.fullmatch(r'(.+?)\b(' + prefix + r'_\w+)\s*\((.*)\)', stmt, re.S)
-        if m is None:
-            raise HipError("{}: not a prototype: '{}'".format(header, stmt))
-        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
-        if '*' in ret:
-            if re.sub(r'\s+', ' ', ret).strip() != 'const char *':
-                raise HipError("{}: cannot read the return type '{}' of {}".format(header, ret.strip(), name))
-            restype = ctypes.c_char_p
-        else:
-            restype = _ctype(ret, False, name, header)
-        argtypes = [] if params == 'void' else [_ctype(p, True, name, header) for p in params.split(',')]
-        signatures[name] = (restype, argtypes)
-    return signatures, constants, structs
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_hip.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return parse_header(f.read())
-
-
-# name -> (restype, argtypes) of every entry point; DPK_OK, DPK_E*, DPK_FLAG_*, DPK_KERNEL_* as module-level names
-SIGNATURES, CONSTANTS, _STRUCT_FIELDS = _read_header()
+# name -> (restype, argtypes) of every dpk_ entry point; DPK_OK, DPK_E*, DPK_FLAG_*, DPK_KERNEL_* as module-level names
+SIGNATURES, CONSTANTS = MAIN.signatures, MAIN.constants
 globals().update(CONSTANTS)
+BINDING = MAIN
+load_library, check, call, _read_header = MAIN.load, MAIN.check, MAIN.call, MAIN.read_header
+bound_module(__name__)        # LIB_PATH, HEADER_PATH and _lib are views of MAIN (tests/buffer_contract.py puts its proxy at _lib)
 LL_SPREAD = 16            # partial sums in front of the count of a spread {sum LL, count} slot (17 doubles)
 
-
-def _struct(c_name: str, doc: str):
-    return type(c_name, (ctypes.Structure,), {'_fields_': _STRUCT_FIELDS[c_name], '__doc__': doc})
-
-
+_struct = MAIN.struct
 FlatSpnCircuit = _struct('dpk_flat_spn_circuit', "sizes and device addresses of a flattened node-graph SPN")
 PairsTablesArgs = _struct('dpk_pairs_tables_args', "one layer of dpk_coupling1d_pairs_tables")
 BnFoldArgs = _struct('dpk_bn1d_fold_args', "one layer of dpk_bn1d_fold_many")
@@ -133,48 +63,10 @@ def cached_tables_flag() -> int:
     return DPK_FLAG_PARAMS_CACHED if _trust_versions else DPK_FLAG_PARAMS_VERIFY
 
 
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_hip.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_hip.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH)
-        )
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)  # AttributeError if the .so and the header disagree
-        except AttributeError:
-            if 'DEEPROB_HIP_LIB' in os.environ:   # measurement builds of an older ABI (A/B runs): what exists is bound
-                continue
-            raise
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def check(rc: int, fn):
-    """Raise ``HipError("<name> failed (<rc>): <last error>")`` for the negative result ``rc`` of entry point ``fn``."""
-    if rc < 0:
-        msg = load_library().dpk_last_error()
-        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
-
-
-def call(fn, *args) -> int:
-    """``fn(*args)`` for an entry point that returns a status or a ``*_workspace_bytes`` size: the (non-negative) result,
-    HipError on a negative one.  The routing calls that read DPK_EUNSUPPORTED as "take the other route", and the knobs
-    whose negative results are values, call ``fn`` itself and get the raw code."""
-    rc = fn(*args)
-    if rc < 0:
-        check(rc, fn)
-    return rc
+# ``call(fn, *args)``: the (non-negative) result of a dpk_ entry point that returns a status or a ``*_workspace_bytes``
+# size, HipError("<fn> failed (<rc>): <last error>") on a negative one (``check(rc, fn)`` raises it for a result already in
+# hand).  The routing calls that read DPK_EUNSUPPORTED as "take the other route", and the knobs whose negative results are
+# values, call ``fn`` itself and get the raw code.
 
 
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -198,6 +90,32 @@ def require_device_f32(t: torch.Tensor, name: str) -> torch.Tensor:
             raise HipError("{} must be a floating point tensor, got {}".format(name, t.dtype))
         t = t.float()
     return t.contiguous()
+
+
+def require_model_f32(who: str, t: torch.Tensor, name: str, shape, device: torch.device, keep: list) -> torch.Tensor:
+    """``require_device_f32`` of an argument of operator ``who`` that must have ``shape`` (ValueError) and live on the
+    model's ``device`` (HipError).  ``keep`` holds what was converted until the launch is queued."""
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("{}: expected {} of shape {}, got {}".format(who, name, tuple(shape), tuple(t.shape)))
+    t = require_device_f32(t.detach(), name)
+    if t.device != device:
+        raise HipError("{} lives on '{}', the model on '{}'".format(name, t.device, device))
+    keep.append(t)
+    return t
+
+
+def require_labels(who: str, y: torch.Tensor, B: int, classes: int, device: torch.device, trusted: bool = False):
+    """``y`` as the contiguous int64 ``[B]`` labels on ``device`` that operator ``who`` passes down.  The kernels clamp a
+    label so as not to read past the root's table; a wrong label is the caller's error and is reported here (ValueError),
+    at the cost of one read-back of two numbers (``trusted``: the caller drew them itself, no check and no read-back)."""
+    yd = y.to(device=device, dtype=torch.int64).contiguous()
+    if tuple(yd.shape) != (B,):
+        raise ValueError("{}: expected y of shape ({},), got {}".format(who, B, tuple(yd.shape)))
+    if B > 0 and not trusted:
+        lo, hi = (int(v) for v in torch.stack([yd.min(), yd.max()]).tolist())
+        if lo < 0 or hi >= classes:
+            raise ValueError("{}: labels must lie in [0, {}), got {} .. {}".format(who, classes, lo, hi))
+    return yd
 
 
 def tensors_key(*tensors) -> tuple:
@@ -258,10 +176,10 @@ class Workspace:
         # the library keeps a few words per workspace ADDRESS (fingerprint slots, the marginalised-evidence hint): hand
         # them back before the allocator reuses the memory
         try:
-            if _lib is not None:
+            if MAIN.lib is not None:
                 for t in [self.buf] + list(self._retired):
                     if t is not None and t.is_cuda:
-                        _lib.dpk_workspace_forget(t.data_ptr(), t.numel())
+                        MAIN.lib.dpk_workspace_forget(t.data_ptr(), t.numel())
         except Exception:   # (interpreter shutdown: modules may be gone)
             pass
 

@@ -5,8 +5,6 @@ nothing of them is written down a second time.  There is no CPU fallback: a miss
 The operators below take device tensors, allocate their outputs and scratch with ``torch.empty`` and return device
 tensors; :class:`DeviceTree` holds the five tables of a tree, uploaded in one copy.
 """
-import ctypes
-import os
 
 import numpy as np
 import torch
@@ -14,65 +12,19 @@ import torch
 from deeprob import hip
 from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_clt.h'))
-LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_clt.so'))
+BINDING = hip.CLT
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
+globals().update(CONSTANTS)
+load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_header
+hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 #: floats of scratch per query launch (128 MiB): a long batch is evaluated in pieces of WORK_FLOATS / (2 D) rows
 WORK_FLOATS = 1 << 25
-#: the oldest ``dpc_abi_version()`` this binding loads: 2 added the ``dpc_cnq_*`` queries of cutset networks (3 added the
-#: ``dpc_mar_*`` posterior marginals: a library without them fails in the binding loop of :func:`load_library`)
-ABI_VERSION = 2
 
 
 def query_rows(d: int) -> int:
     """Rows per query launch for ``d`` variables: a multiple of 64 (a wave of rows), at least 1024."""
     return max(1024, WORK_FLOATS // (2 * d) // 64 * 64)
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_clt.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dpc', header='deeprob_clt.h')
-
-
-SIGNATURES, CONSTANTS, _ = _read_header()
-globals().update(CONSTANTS)
-
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_clt.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_clt.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    version = lib.dpc_abi_version() if hasattr(lib, 'dpc_abi_version') else 0
-    if version < ABI_VERSION:
-        raise HipError(
-            "libdeeprob_clt.so at {} has ABI version {}, this binding needs {} -- rebuild it with "
-            "`make -C deeprob-kit_amd/csrc` (or __graft_entry__.build())".format(LIB_PATH, version, ABI_VERSION))
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def call(fn, *args) -> int:
-    rc = fn(*args)
-    if rc < 0:
-        msg = load_library().dpc_last_error()
-        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
-    return rc
 
 
 def _rows(x: torch.Tensor, name: str) -> torch.Tensor:

@@ -3,56 +3,17 @@ top-down pass of a DGC-SPN.  The prototypes and the ``DPG_*`` constants are read
 ``deeprob.hip``; nothing of them is written down a second time.  There is no CPU fallback: a missing library raises.
 """
 import ctypes
-import os
 
 import torch
 
 from deeprob import hip
 from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_dgc.h'))
-LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_dgc.so'))
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_dgc.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dpg', header='deeprob_dgc.h')
-
-
-SIGNATURES, CONSTANTS, _ = _read_header()
+BINDING = hip.DGC
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
 globals().update(CONSTANTS)
-
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_dgc.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_dgc.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def call(fn, *args) -> int:
-    rc = fn(*args)
-    if rc < 0:
-        msg = load_library().dpg_last_error()
-        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
-    return rc
+load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_header
+hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 
 def product_geometry(layers):
@@ -82,14 +43,8 @@ def dgcspn_topdown(mode: int, n_samples: int, in_features, geom, classes: int, x
     L, B, device = len(geom), int(n_samples), loc.device
     keep = []
 
-    def dev(t, name, shape=None):
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError("dgcspn_topdown: expected {} of shape {}, got {}".format(name, tuple(shape), tuple(t.shape)))
-        t = hip.require_device_f32(t.detach(), name)
-        if t.device != device:
-            raise HipError("{} lives on '{}', the model on '{}'".format(name, t.device, device))
-        keep.append(t)
-        return t
+    def dev(t, name, shape):
+        return hip.require_model_f32('dgcspn_topdown', t, name, shape, device, keep)
 
     if len(logws) != L:
         raise ValueError('dgcspn_topdown: %d weight tensors for %d levels' % (len(logws), L))
@@ -107,17 +62,7 @@ def dgcspn_topdown(mode: int, n_samples: int, in_features, geom, classes: int, x
     logw_arr[L] = hip.ptr(dev(logws[-1], 'root logw', (classes, geom[-1][3] * geom[-1][4] * geom[-1][5])))
     K = geom[0][0]
     locd, scaled = dev(loc, 'loc', (K, C, H, W)), dev(scale, 'scale', (K, C, H, W))
-    yd = None
-    if y is not None:
-        yd = y.to(device=device, dtype=torch.int64).contiguous()
-        if tuple(yd.shape) != (B,):
-            raise ValueError("dgcspn_topdown: expected y of shape ({},), got {}".format(B, tuple(yd.shape)))
-        # (the kernel clamps a label so as not to read past the root's table; a wrong label is the caller's error and is
-        # reported here, at the cost of one read-back of two numbers)
-        if B > 0 and not labels_trusted:
-            lo, hi = (int(v) for v in torch.stack([yd.min(), yd.max()]).tolist())
-            if lo < 0 or hi >= classes:
-                raise ValueError("dgcspn_topdown: labels must lie in [0, {}), got {} .. {}".format(classes, lo, hi))
+    yd = None if y is None else hip.require_labels('dgcspn_topdown', y, B, classes, device, trusted=labels_trusted)
     garr = (ctypes.c_int32 * (L * DPG_GEOM_INTS))(*[int(v) for row in geom for v in row])
     out = torch.empty((B, C, H, W), dtype=torch.float32, device=device)
     choice = torch.empty((B, 1 + H * W), dtype=torch.int32, device=device) if want_choice else None

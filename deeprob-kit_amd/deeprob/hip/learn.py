@@ -6,8 +6,6 @@ The operators below take the training set as :class:`DeviceData` and a generatio
 outputs with ``torch.empty`` and return them; the small integer tables of a launch go up in ONE host-to-device copy
 (``upload``).  ``COUNTERS`` counts kernel launches, host reads and uploads for ``learn_spn``'s ``info``.
 """
-import ctypes
-import os
 
 import numpy as np
 import torch
@@ -15,49 +13,11 @@ import torch
 from deeprob import hip
 from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_learn.h'))
-LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_learn.so'))
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_learn.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dpl', header='deeprob_learn.h')
-
-
-SIGNATURES, CONSTANTS, _ = _read_header()
+BINDING = hip.LEARN
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
 globals().update(CONSTANTS)
-
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_learn.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_learn.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def call(fn, *args) -> int:
-    rc = fn(*args)
-    if rc < 0:
-        msg = load_library().dpl_last_error()
-        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
-    return rc
+load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_header
+hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 
 #: kernel launches outside the Lloyd loop, kernel launches inside it, device-to-host reads, host-to-device uploads

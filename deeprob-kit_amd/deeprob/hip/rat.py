@@ -4,59 +4,17 @@ header with the parser of ``deeprob.hip``; nothing of them is written down a sec
 missing library raises.
 """
 import ctypes
-import os
 
 import torch
 
 from deeprob import hip
 from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_rat.h'))
-LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_rat.so'))
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_rat.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dpr', header='deeprob_rat.h')
-
-
-SIGNATURES, CONSTANTS, _ = _read_header()
+BINDING = hip.RAT
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
 globals().update(CONSTANTS)
-
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_rat.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_rat.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def call(fn, *args) -> int:
-    rc = fn(*args)
-    if rc < 0:
-        msg = load_library().dpr_last_error()
-        text = "{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else '')
-        if rc == DPR_EUNSUPPORTED:
-            raise NotImplementedError(text)
-        raise HipError(text)
-    return rc
+load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_header
+hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 
 def ratspn_moments(dist: int, lctx, x: torch.Tensor, y, acts, logws, src: torch.Tensor, p0: torch.Tensor, p1,
@@ -80,13 +38,7 @@ def ratspn_moments(dist: int, lctx, x: torch.Tensor, y, acts, logws, src: torch.
     keep = []
 
     def dev(t, name, shape):
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("ratspn_moments: expected {} of shape {}, got {}".format(name, tuple(shape), tuple(t.shape)))
-        t = hip.require_device_f32(t.detach(), name)
-        if t.device != device:
-            raise HipError("{} lives on '{}', the model on '{}'".format(name, t.device, device))
-        keep.append(t)
-        return t
+        return hip.require_model_f32('ratspn_moments', t, name, shape, device, keep)
 
     xd = dev(x, 'x', (B, D))
     if len(acts) != depth:
@@ -108,17 +60,7 @@ def ratspn_moments(dist: int, lctx, x: torch.Tensor, y, acts, logws, src: torch.
     p1d = dev(p1, 'p1', (reps * G0, lctx.I, lctx.d)) if p1 is not None else None
     if dist == DPR_DIST_GAUSSIAN and p1d is None:
         raise ValueError('ratspn_moments: Gaussian leaves need their scales')
-    yd = None
-    if y is not None:
-        yd = y.to(device=device, dtype=torch.int64).contiguous()
-        if tuple(yd.shape) != (B,):
-            raise ValueError("ratspn_moments: expected y of shape ({},), got {}".format(B, tuple(yd.shape)))
-        # (the kernel clamps a label so as not to read past the root's table; a wrong label is the caller's error and is
-        # reported here, at the cost of one read-back of two numbers)
-        if B > 0:
-            lo, hi = (int(v) for v in torch.stack([yd.min(), yd.max()]).tolist())
-            if lo < 0 or hi >= lctx.C:
-                raise ValueError("ratspn_moments: labels must lie in [0, {}), got {} .. {}".format(lctx.C, lo, hi))
+    yd = None if y is None else hip.require_labels('ratspn_moments', y, B, lctx.C, device)
     mean = torch.empty((B, D), dtype=torch.float32, device=device)
     var = torch.empty((B, D), dtype=torch.float32, device=device) if want_var else None
     flow = torch.empty((B, reps * G0, lctx.I), dtype=torch.float32, device=device) if want_leaf_flow else None

@@ -3,40 +3,13 @@ prefix ``dps_``; the entry points live in ``libdeeprob_hip.so``).  The prototype
 the header with the parser of ``deeprob.hip``; nothing of them is written down a second time.  Host side only: no call
 here touches the device.
 """
-import os
-
 from deeprob import hip
-from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_slice.h'))
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_slice.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dps', header='deeprob_slice.h')
-
-
-SIGNATURES, CONSTANTS, _ = _read_header()
+BINDING = hip.SLICE
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
 globals().update(CONSTANTS)
-
-_bound = False
-
-
-def load_library():
-    """``libdeeprob_hip.so`` with the ``dps_`` entry points bound."""
-    global _bound
-    lib = hip.load_library()
-    if not _bound:
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _bound = True
-    return lib
+load_library = BINDING.load           # ``libdeeprob_hip.so`` with the ``dps_`` entry points bound
+hip.bound_module(__name__)         # HEADER_PATH and LIB_PATH are views of BINDING
 
 
 def grid(ntiles: int, cus: int, lanes: int = 1, np: int = 0) -> int:

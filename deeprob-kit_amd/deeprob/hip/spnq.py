@@ -4,7 +4,6 @@ queries on a node-graph SPN -- conditional moments and the posterior of one disc
 written down a second time.  There is no CPU fallback: a missing library or a CPU tensor raises.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -12,52 +11,14 @@ import torch
 from deeprob import hip
 from deeprob.hip import HipError
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', '..', 'include', 'deeprob_spnq.h'))
-LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'lib', 'libdeeprob_spnq.so'))
-
-
-def _read_header():
-    if not os.path.isfile(HEADER_PATH):
-        raise HipError("deeprob_spnq.h not found at {} -- it is the declaration of the C ABI this binding is built "
-                       "from".format(HEADER_PATH))
-    with open(HEADER_PATH) as f:
-        return hip.parse_header(f.read(), prefix='dpq', header='deeprob_spnq.h')
-
-
-SIGNATURES, CONSTANTS, _STRUCT_FIELDS = _read_header()
+BINDING = hip.SPNQ
+SIGNATURES, CONSTANTS = BINDING.signatures, BINDING.constants
 globals().update(CONSTANTS)
+load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_header
+hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 #: the header's mirror of ``dpk_flat_spn_circuit``; the record ``FlatSpn.circuit(device)`` builds is passed as it is
-FlatSpnCircuit = type('dpq_flat_spn_circuit', (ctypes.Structure,), {'_fields_': _STRUCT_FIELDS['dpq_flat_spn_circuit']})
-
-_lib = None
-
-
-def load_library() -> ctypes.CDLL:
-    """Load ``libdeeprob_spnq.so`` (built in-tree by ``__graft_entry__.build()``) and bind every symbol."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise HipError(
-            "libdeeprob_spnq.so not found at {} -- build it with `make -C deeprob-kit_amd/csrc` "
-            "(or __graft_entry__.build()); there is no CPU fallback".format(LIB_PATH))
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError if the .so and the header disagree
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
-
-
-def call(fn, *args) -> int:
-    rc = fn(*args)
-    if rc < 0:
-        msg = load_library().dpq_last_error()
-        raise HipError("{} failed ({}): {}".format(fn.__name__, rc, msg.decode() if msg else ''))
-    return rc
+FlatSpnCircuit = BINDING.struct('dpq_flat_spn_circuit')
 
 
 def leaf_table(spn):

@@ -262,7 +262,7 @@ def ratspn_mpe(sd: Dict[str, torch.Tensor], x: torch.Tensor, depth: int, y: Opti
 
 
 def hash_uniform(seed: int, ctr: np.ndarray) -> np.ndarray:
-    """The library's counter-based uniform (csrc/ratspn_topdown.hip: td_uniform; the dropout hash of csrc/common.h):
+    """The library's counter-based uniform (csrc/shared/device.h: counter_uniform; the dropout hash of csrc/common.h):
     (splitmix64(seed + ctr * golden) >> 40) / 2^24, as float32."""
     with np.errstate(over='ignore'):
         z = np.uint64(seed) + ctr.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)

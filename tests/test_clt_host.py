@@ -286,14 +286,6 @@ def test_clt_header_parses_and_matches_the_exports():
     assert exported == sorted(sigs)
 
 
-def test_other_libraries_export_no_clt_name():
-    from deeprob import hip
-    from deeprob.hip import learn
-    for path in (hip.LIB_PATH, learn.LIB_PATH):
-        out = subprocess.run(['nm', '-D', '--defined-only', path], check=True, capture_output=True, text=True).stdout
-        assert not [l for l in out.splitlines() if ' dpc_' in l]
-
-
 def test_missing_clt_library_names_the_make_command(monkeypatch):
     from deeprob.hip import HipError, clt
     from deeprob.spn.structure.cltree import BinaryCLT

@@ -255,9 +255,3 @@ def test_missing_learn_library_names_the_make_command(monkeypatch):
         learn.load_library()
     assert 'make -C deeprob-kit_amd/csrc' in str(e.value)
 
-
-def test_hip_library_exports_are_untouched_by_the_learn_library():
-    """The learn kernels live in their own library: libdeeprob_hip.so exports no dpl_ name."""
-    from deeprob import hip
-    out = subprocess.run(['nm', '-D', '--defined-only', hip.LIB_PATH], check=True, capture_output=True, text=True).stdout
-    assert not [l for l in out.splitlines() if ' dpl_' in l]
