@@ -1233,8 +1233,10 @@ __device__ __forceinline__ void load_children(const float *__restrict__ xa, cons
     mc = (m2 == -INFINITY) ? 0.f : m2;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) {
-        ea[i] = __expf(a[i] - ma);
-        ec[i] = __expf(c[i] - mc);
+        // (a +inf input -- Bernoulli leaves under +-inf evidence: two terms at nan_to_num's +FLT_MAX meet in a product
+        // below -- is the maximum: weight 1, not exp(inf - inf); the result is then +inf like torch.logsumexp's)
+        ea[i] = (a[i] == INFINITY) ? 1.f : __expf(a[i] - ma);
+        ec[i] = (c[i] == INFINITY) ? 1.f : __expf(c[i] - mc);
     }
 }
 
@@ -1313,7 +1315,7 @@ __global__ __launch_bounds__(256) void prodroot_fwd_kernel(const float *__restri
                     rs = rs * __expf(rm - m) + v;
                     rm = m;
                 } else {
-                    rs += v * __expf(m - rm);
+                    rs += v * ((m == rm) ? 1.f : __expf(m - rm));   // (m == rm: also two partitions at +inf)
                 }
             }
         }

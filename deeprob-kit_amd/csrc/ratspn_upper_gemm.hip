@@ -364,6 +364,13 @@ __global__ __launch_bounds__(256) void prodsum_mfma_kernel(const UpperArgs a) {
                 }
             }
         }
+        // rare: a +inf input (Bernoulli leaves under +-inf evidence: two terms at nan_to_num's +FLT_MAX met in a product
+        // below).  Its exponential above is exp(inf - inf); every output of the partition is +inf like torch.logsumexp's
+        const bool top = (ma == INFINITY) || (mc == INFINITY);
+        if (__any(top)) {
+            if (top && row_ok && h == 0)
+                for (int o = 0; o < S; ++o) a.out[(b * P + p) * S + o] = INFINITY;
+        }
     }
 }
 
@@ -386,6 +393,9 @@ __global__ __launch_bounds__(256) void prodroot_mfma_kernel(const UpperArgs a) {
     }
     bool vanished = false;
     unsigned cmask = 0u;   // classes of this lane's sample with a vanished partition share (CT * CPT <= 32)
+    // rare: a partition at +inf (Bernoulli leaves under +-inf evidence: inputs at nan_to_num's +FLT_MAX, or their +inf sums
+    // from the level below).  The running sums below then hold exp(inf - inf); every class is +inf like torch.logsumexp's
+    bool top = false;
     // Partition p + 1's inputs and fragments are requested before the arithmetic of partition p, into a SECOND register
     // set (two partitions per trip: a copy between the sets makes hipcc wait for the request in the trip that issued it).
     // A wave used to pay two dependent L2 round trips per partition: 18 us for the 8 partitions of the (16,16) root at
@@ -425,6 +435,7 @@ __global__ __launch_bounds__(256) void prodroot_mfma_kernel(const UpperArgs a) {
         half8 eh, el8;
         split8(eb, eh, el8);
         const float m = ma + mc;
+        top = top || (m == INFINITY);
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
             const half8 wh = o.fh[t], wl = o.fl[t];
@@ -470,12 +481,12 @@ __global__ __launch_bounds__(256) void prodroot_mfma_kernel(const UpperArgs a) {
     for (int k = 0; k < CT * CPT; ++k) {
         if (k < C) {
             const float r = (rm[k] > -INFINITY) ? fmaf(__builtin_amdgcn_logf(rs[k]), kUpLn2, rm[k]) : -INFINITY;
-            if (row_ok && h == 0) a.out[b * C + k] = r;
+            if (row_ok && h == 0) a.out[b * C + k] = top ? INFINITY : r;
         }
     }
     if (__any(vanished)) {
         cmask |= (unsigned)__shfl_xor((int)cmask, 32, 64);          // (both lane halves of a sample saw the same sums)
-        unsigned long long lanes = __ballot(cmask != 0u && row_ok && h == 0);
+        unsigned long long lanes = __ballot(cmask != 0u && row_ok && h == 0 && !top);
         while (lanes) {
             const int src = __builtin_ctzll(lanes);
             lanes &= lanes - 1;

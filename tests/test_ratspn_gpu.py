@@ -609,26 +609,27 @@ def test_mpe_bernoulli_golden(golden):
     assert np.array_equal(model.mpe(x, y=torch.from_numpy(g['y']).cuda()).cpu().numpy(), g['mpe_y'])
 
 
-@pytest.mark.parametrize('kw', [dict(in_features=15, rg_depth=2, rg_repetitions=3, rg_batch=3, rg_sum=5, optimize_scale=True),
-                                dict(in_features=15, rg_depth=3, rg_repetitions=2, rg_batch=2, rg_sum=2),
-                                dict(in_features=70, out_classes=4, rg_depth=4, rg_repetitions=3, rg_batch=5, rg_sum=3),
-                                dict(in_features=784, rg_depth=2, rg_repetitions=8, rg_batch=16, rg_sum=16),
-                                dict(in_features=33, rg_depth=5, rg_repetitions=2, rg_batch=2, rg_sum=2)])
-def test_mpe_vs_oracle_padded_and_deep(kw):
-    """The top-down kernel where the reference cannot go (padded region graphs: its unpad_samples raises, see
-    oracle/ratspn_oracle.py::_unpad_samples) and at depths 4 / 5, 16 nodes per region, several classes: against the oracle's
-    restatement, with the chosen repetition / leaf channels compared on the rows whose decisions are not fp32 ties."""
+MPE_CASES = [dict(in_features=15, rg_depth=2, rg_repetitions=3, rg_batch=3, rg_sum=5, optimize_scale=True),
+             dict(in_features=15, rg_depth=3, rg_repetitions=2, rg_batch=2, rg_sum=2),
+             dict(in_features=70, out_classes=4, rg_depth=4, rg_repetitions=3, rg_batch=5, rg_sum=3),
+             dict(in_features=784, rg_depth=2, rg_repetitions=8, rg_batch=16, rg_sum=16),
+             dict(in_features=33, rg_depth=5, rg_repetitions=2, rg_batch=2, rg_sum=2)]
+
+
+def _check_mpe_vs_oracle(kw, B):
     from deeprob.spn.models import GaussianRatSpn
     from deeprob.hip import ops
+    from tests.ratspn_mpe_ref import mpe_replay
+    from tests.ratspn_posterior_ref import host_activations
     torch.manual_seed(5)
     model = GaussianRatSpn(random_state=9, **kw).eval()
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     D = kw['in_features']
     gen = torch.Generator().manual_seed(6)
-    x = torch.randn(300, D, generator=gen)
-    x[torch.rand(300, D, generator=gen) < 0.5] = float('nan')
+    x = torch.randn(B, D, generator=gen)
+    x[torch.rand(B, D, generator=gen) < 0.5] = float('nan')
     x[0] = float('nan')
-    y = (torch.arange(300) % kw['out_classes']) if kw.get('out_classes', 1) > 1 else None
+    y = (torch.arange(B) % kw['out_classes']) if kw.get('out_classes', 1) > 1 else None
     want, og, oo = orc.ratspn_mpe(sd, x, kw['rg_depth'], y=y, return_choice=True)
     model.cuda()
     got = model.mpe(x.cuda(), y=None if y is None else y.cuda()).cpu()
@@ -640,13 +641,38 @@ def test_mpe_vs_oracle_padded_and_deep(kw):
     # every completed value is the mean of SOME channel of the region that holds the variable in the chosen repetition
     acts = model._upward_for_mpe(x.cuda())
     leaf = model._leaf_params()
-    out, choice = ops.ratspn_topdown(0, leaf[0], 300, model._fused_ctx, x.cuda(), None if y is None else y.cuda(), acts,
+    out, choice = ops.ratspn_topdown(0, leaf[0], B, model._fused_ctx, x.cuda(), None if y is None else y.cuda(), acts,
                                      model._topdown_logw(), model._topdown_src(), leaf[1], leaf[2], want_choice=True)
     assert torch.equal(out.cpu(), got)
     G0 = 2 ** kw['rg_depth']
     choice = choice.cpu()
     assert torch.equal(choice[same, 0].long(), torch.div(og[same, 0], G0, rounding_mode='floor'))
     assert torch.equal(choice[same, 1:].long(), oo[same])
+    # EVERY row, the set-aside ones included: (1) the activations the top-down pass starts from against the oracle's in
+    # float64, (2) the pass itself against its restatement from those device activations (tests/ratspn_mpe_ref.py: fp32
+    # additions and comparisons only, nothing left to rounding) -- repetition, leaf channels and the output bit for bit
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    for t, (a, a64) in enumerate(zip(acts, host_activations(sd64, x.double(), kw['rg_depth']))):
+        assert rel_err(a.detach().cpu().numpy(), a64.numpy()) <= LL_TOL, t
+    with torch.no_grad():
+        r_out, r_rep, r_chan = mpe_replay(acts, model._topdown_logw(), model._topdown_src(), leaf, x, y)
+    assert torch.equal(choice[:, 0].long(), r_rep)
+    assert torch.equal(choice[:, 1:].long(), r_chan)
+    assert torch.equal(out.cpu(), r_out)
+
+
+@pytest.mark.parametrize('kw', MPE_CASES)
+def test_mpe_vs_oracle_padded_and_deep(kw):
+    """The top-down kernel where the reference cannot go (padded region graphs: its unpad_samples raises, see
+    oracle/ratspn_oracle.py::_unpad_samples) and at depths 4 / 5, 16 nodes per region, several classes: against the oracle's
+    restatement, with the chosen repetition / leaf channels compared on the rows whose decisions are not fp32 ties -- and on
+    every row against the replay of the pass from the device's own activations, which are held to the oracle's."""
+    _check_mpe_vs_oracle(kw, 300)
+
+
+def test_mpe_vs_oracle_ragged_last_group_with_labels():
+    """301 rows: the last work-group of the top-down kernel (a wave per row, 4 rows) holds one row; four classes, labels."""
+    _check_mpe_vs_oracle(MPE_CASES[2], 301)
 
 
 def test_sample_shapes_and_statistics():
