@@ -17,8 +17,8 @@ from deeprob.hip._binding import Binding, HipError, bound_module, parse_header  
 MAIN = Binding('hip', 'dpk', env='DEEPROB_HIP_LIB')      # DEEPROB_HIP_LIB: measurement builds (profiles/README)
 SLICE = Binding('slice', 'dps', onto=MAIN)               # host-side knobs of a kernel that lives in libdeeprob_hip.so
 LEARN = Binding('learn', 'dpl')
-# 2 added the ``dpc_cnq_*`` queries of cutset networks (3 added the ``dpc_mar_*`` posterior marginals: a library without
-# them fails when its symbols are bound)
+# 2 added the ``dpc_cnq_*`` queries of cutset networks (3 added the ``dpc_mar_*`` posterior marginals, 4 the ``dpc_xpc_*`` split of
+# the XPC learners: a library without them fails when its symbols are bound)
 CLT = Binding('clt', 'dpc', min_abi=2)
 DGC = Binding('dgc', 'dpg')
 SPNQ = Binding('spnq', 'dpq')

@@ -20,18 +20,37 @@ def _host(data) -> np.ndarray:
     return data.cpu().numpy()
 
 
+#: the arguments of the XPC learners that have no default: ``learn_estimator`` routes to them when all are given
+XPC_KEYWORDS = {'xpc': ('det', 'sd', 'min_part_inst', 'conj_len', 'arity'),
+                'ensemble-xpc': ('ensemble_dim', 'det', 'sd_level', 'min_part_inst', 'conj_len', 'arity')}
+
+
 def learn_estimator(data, distributions: list, domains: Optional[List[Union[list, tuple]]] = None, method: str = 'learnspn',
                     **kwargs):
     """
     Learn a SPN density estimator given some training data, the features distributions and domains
-    (reference wrappers.py:15-52): ``learn_spn`` followed by ``prune``.
+    (reference wrappers.py:15-52): ``learn_spn`` followed by ``prune``, or ``learn_xpc`` / ``learn_expc``.
 
-    :param method: 'learnspn'.  'xpc' and 'ensemble-xpc' are not built on the HIP path.
+    :param method: 'learnspn', 'xpc' or 'ensemble-xpc'.  The XPC learners have required arguments without defaults
+                   (``det``, ``sd`` -- ``sd_level`` and ``ensemble_dim`` for the ensemble --, ``min_part_inst``,
+                   ``conj_len``, ``arity``): they are given as keywords.
     :raises ValueError: If the method used for structure learning is not known.
-    :raises NotImplementedError: For 'xpc' and 'ensemble-xpc'.
+    :raises ValueError: If the method is 'xpc' or 'ensemble-xpc' but the variable domains are not binary.
+    :raises NotImplementedError: For 'xpc' and 'ensemble-xpc' without their required keywords.
     """
-    if method in ('xpc', 'ensemble-xpc'):
-        raise NotImplementedError("structure learning method '{}' is not built on the HIP path (built: learnspn)".format(method))
+    if method in XPC_KEYWORDS:
+        if domains is None:
+            domains = compute_data_domains(_host(data), distributions)
+        if not all(d == [0, 1] for d in domains):
+            raise ValueError("The domains must be binary for learning {}".format(
+                'a XPC' if method == 'xpc' else 'an Ensemble-XPC'))
+        missing = [k for k in XPC_KEYWORDS[method] if k not in kwargs]
+        if missing:
+            raise NotImplementedError("structure learning method '{}' has no defaults for {}: pass them as "
+                                      "keywords".format(method, ', '.join(missing)))
+        from deeprob.spn.learning.xpc import learn_expc, learn_xpc
+        root, _ = (learn_xpc if method == 'xpc' else learn_expc)(data, **kwargs)
+        return root
     if method != 'learnspn':
         raise ValueError("Unknown SPN learning method called {}".format(method))
     if domains is None:

@@ -229,7 +229,13 @@ class BinaryCLT(Leaf):
         ``exp(params[v][l])`` over the two (a leaf of the tree) or over two products "indicator x the children's sums for
         this value".  The circuit's root is the sum for l = 1 of the tree's root.
         """
-        from deeprob.spn.learning.learnspn import new_node, to_flat
+        from deeprob.spn.learning.learnspn import to_flat
+        return to_flat(self.to_pc_nodes())
+
+    def to_pc_nodes(self) -> dict:
+        """The circuit of :meth:`to_pc` as the node records ``to_flat`` takes (``learnspn.new_node``): its root, a Sum.  A
+        learner that builds a larger circuit (``learn_xpc``) hangs it under its own nodes."""
+        from deeprob.spn.learning.learnspn import new_node
         weights = {self.scope[i]: np.exp(self.params[i]) for i in range(len(self.tree))}
         sums = ([], [])                 # per parent value l: the sums of the nodes visited and not yet consumed
         for node in _post_order(build_tree_structure(self.tree, scope=self.scope)):
@@ -242,7 +248,7 @@ class BinaryCLT(Leaf):
                     branches[k] = dict(new_node('Product', [s for c in kids for s in c['scope']]), children=kids)
             for l in (0, 1):
                 sums[l].append(dict(new_node('Sum', branches[0]['scope'], weights=weights[v][l]), children=list(branches)))
-        return to_flat(sums[1][0])
+        return sums[1][0]
 
     def get_scopes(self):
         """The scope of every inner node of the tree, as in the circuit of ``to_pc``: each once, children first."""

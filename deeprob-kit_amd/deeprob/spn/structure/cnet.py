@@ -26,7 +26,7 @@ silently drops a row from the sum at the first OR node whose variable is NaN (cn
 The reference has neither ``sample`` nor ``mpe`` nor ``marginals`` for cutset networks, so there is nothing to reproduce: all
 are exact here (the OR nodes are deterministic).  Exact MPE is built at kernel, ABI and binding level --
 ``deeprob.hip.cnet.mpe(model._on_device(device), x)``, ``dpc_cnq_mpe`` -- and the one-line ``mpe`` method on the class awaits
-a follow-up.  Not built: the xpc learners.  The scored learners ``learn_cnet_bd`` / ``learn_cnet_bic`` are built in
+a follow-up.  The XPC learners are ``deeprob.spn.learning.xpc``.  The scored learners ``learn_cnet_bd`` / ``learn_cnet_bic`` are built in
 ``deeprob.spn.learning.cnet_bayesian`` and return a ``BinaryCNet``.
 """
 import time

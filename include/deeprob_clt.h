@@ -290,6 +290,44 @@ int dpc_mar_cnet(const float *x, const uint8_t *codes, int64_t b, int d, int n_n
 int dpc_cut_pair_counts(const uint64_t *planes, int64_t n_words, int d, const int32_t *word_off, int n_tasks,
                         const int32_t *entry_task, const int32_t *entry_col, int n_entries, int32_t *ones1, void *stream);
 
+/* ---- XPC learners (deeprob.spn.learning.xpc; reference spn/learning/xpc.py, spn/utils/partitioning.py) ----
+ *
+ * An XPC splits the rows of a partition by a CONJUNCTION of conj_len binary variables, 2^conj_len ways at most.  Both
+ * entries read the bit planes of the WHOLE training matrix, planes [d, n_words] from dpc_pack_bits for the n rows
+ * (n_words = (n + 63) / 64), through a row index: task t owns rows[seg_off[t] .. seg_off[t+1]) (indices into the
+ * training matrix, the convention of the dpc_cnet_* section) and the conj_len columns conj_cols[t][0 .. conj_len).
+ * The code of a row r is
+ *     code(r) = sum over i < conj_len of bit(x[r][conj_cols[t][i]]) << i,
+ * one word read per column and 64 consecutive rows.  A row index outside 0 .. n-1 and a column outside 0 .. d-1 read
+ * as zeros.  A task's segment is cut into chunks of DPC_XPC_CHUNK rows, one work-group each:
+ *     chunk_off[t+1] - chunk_off[t] = (n_t + DPC_XPC_CHUNK - 1) / DPC_XPC_CHUNK,  chunk_off[0] = 0,
+ *     chunk_off[n_tasks] = n_chunks; a task of 0 rows owns no chunk.
+ * seg_off, chunk_off: [n_tasks + 1] int32, trusted like `rows`.  conj_cols: [n_tasks, conj_len] int32.  Integer results
+ * only; no global atomics; no work-group waits on another. */
+#define DPC_XPC_MAX_CONJ 8 /* the longest conjunction: 256 codes, one per thread of a work-group */
+#define DPC_XPC_CHUNK 1024 /* rows per work-group                                                  */
+
+/* hist[t][code] = rows of task t with that code; chunk_hist[c][code] = the same for chunk c alone (dpc_xpc_partition
+ * reads it), so that hist[t] is the sum of chunk_hist over the chunks chunk_off[t] .. chunk_off[t+1).
+ * hist: [n_tasks, 2^conj_len] int32, all zero for a task of 0 rows; chunk_hist: [n_chunks, 2^conj_len] int32 (may be
+ * null when n_chunks = 0). */
+int dpc_xpc_code_counts(const uint64_t *planes, int64_t n_words, int64_t n, int d, const int32_t *rows,
+                        const int32_t *seg_off, const int32_t *chunk_off, const int32_t *conj_cols, int conj_len,
+                        int n_tasks, int n_chunks, int32_t *chunk_hist, int32_t *hist, void *stream);
+
+/* Stable k-way split of every task.  child_of_code[t][code] in 0 .. 2^conj_len - 1 names the child a row with that code
+ * goes to (anything else is taken as child 0); the rows of child k of task t are written to
+ * rows_out[out_off[t][k] ..] IN THE ORDER THEY HAVE IN `rows`, so an ascending segment gives ascending children.  The
+ * caller lays the children out so that they tile rows_out: out_off[t][k + 1] - out_off[t][k] = the sum of hist[t][code]
+ * over the codes of child k; a child without rows writes nothing.  chunk_hist: the output of dpc_xpc_code_counts for the
+ * SAME tasks and columns: a work-group starts each child at out_off plus the rows of that child in the task's chunks in
+ * front of it, and ranks its own rows with wave ballots and popcounts.
+ * child_of_code, out_off: [n_tasks, 2^conj_len] int32; rows_out: int32, sum of n_t entries. */
+int dpc_xpc_partition(const uint64_t *planes, int64_t n_words, int64_t n, int d, const int32_t *rows, const int32_t *seg_off,
+                      const int32_t *chunk_off, const int32_t *conj_cols, int conj_len, const int32_t *chunk_hist,
+                      const int32_t *child_of_code, const int32_t *out_off, int n_tasks, int n_chunks, int32_t *rows_out,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
