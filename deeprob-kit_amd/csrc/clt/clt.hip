@@ -6,12 +6,17 @@
 // LDS, a ballot per column), then work-groups tile the (i, j) pairs 32 x 32, stage 32 words of each plane in LDS and add
 // popcounts in registers; only tiles on or above the diagonal are computed, each writes its mirror image too.  Queries:
 // one thread per row over column-major codes, the row's 2 D floats of state in `work` as [2 D][B], so that the lanes of
-// a wave read and write consecutive addresses and the tree tables are wave-uniform loads.
+// a wave read and write consecutive addresses and the tree tables are wave-uniform loads; the passes over the tree are the
+// Leaf functions of clt_common.h, which the leaves of a cutset network and the marginals use too.
 #include "clt_common.h"
 
 namespace {
 
-using dpc_detail::lse2;
+using dpc_detail::Leaf;
+using dpc_detail::leaf_gather;
+using dpc_detail::leaf_messages;
+using dpc_detail::leaf_pull;
+using dpc_detail::leaf_root;
 using dp_device::counter_uniform;
 
 typedef unsigned long long u64;
@@ -124,18 +129,7 @@ struct QueryArgs {
     float *work, *out;
 };
 
-// m_j: the children's contributions, pulled in list order
-__device__ __forceinline__ void pull(const QueryArgs &a, const float *t, int j, float &m0, float &m1) {
-    m0 = 0.f;
-    m1 = 0.f;
-    const int e1 = a.child_off[j + 1];
-    for (int e = a.child_off[j]; e < e1; ++e) {
-        const int64_t c = a.child_idx[e];
-        m0 += t[2 * c * a.b];
-        m1 += t[(2 * c + 1) * a.b];
-    }
-}
-
+// The tree's passes are those of a leaf of a cutset network (clt_common.h) with position j as column j.
 template <int MODE>
 __global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
     const int64_t r = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
@@ -144,52 +138,21 @@ __global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
     const int D = a.d;
     const uint8_t *q = a.codes + r;     // q[j * B]
     float *t = a.work + r;              // t[(2 j + l) * B]
+    const Leaf f = {D, nullptr, a.bfs, a.parent, a.child_off, a.child_idx, a.params};
 
     if (MODE == kLogLikelihood) {
         double s = 0.0;
-        bool missing = false;
-        for (int i = 0; i < D; ++i) {
-            const int pa = a.parent[i];
-            const int ci = q[(int64_t)i * B], cp = pa < 0 ? 0 : q[(int64_t)pa * B];
-            if (ci == DPC_MISSING) missing = true;
-            if (ci != DPC_MISSING && cp != DPC_MISSING) s += (double)a.params[i * 4 + cp * 2 + ci];
-        }
-        if (!missing) {
+        if (leaf_gather<false>(f, q, B, s)) {
             a.out[r] = (float)s;
             return;
         }
     }
 
     // upward: t_j of every node but the root, children before parents
-    for (int p = D - 1; p >= 1; --p) {
-        const int j = a.bfs[p];
-        const float *pj = a.params + j * 4;
-        const int cj = q[(int64_t)j * B];
-        float m0, m1;
-        pull(a, t, j, m0, m1);
-        float t0, t1;
-        if (cj != DPC_MISSING) {
-            const float m = cj ? m1 : m0;
-            t0 = pj[cj] + m;
-            t1 = pj[2 + cj] + m;
-        } else if (MODE == kMpe) {
-            t0 = fmaxf(pj[0] + m0, pj[1] + m1);
-            t1 = fmaxf(pj[2] + m0, pj[3] + m1);
-        } else {
-            t0 = lse2(pj[0] + m0, pj[1] + m1);
-            t1 = lse2(pj[2] + m0, pj[3] + m1);
-        }
-        t[2 * (int64_t)j * B] = t0;
-        t[(2 * (int64_t)j + 1) * B] = t1;
-    }
+    leaf_messages<MODE == kMpe, false>(f, q, B, t);
 
     if (MODE == kLogLikelihood) {
-        const int j = a.bfs[0];
-        const float *pj = a.params + j * 4;
-        const int cj = q[(int64_t)j * B];
-        float m0, m1;
-        pull(a, t, j, m0, m1);
-        a.out[r] = cj != DPC_MISSING ? pj[cj] + (cj ? m1 : m0) : lse2(pj[0] + m0, pj[1] + m1);
+        a.out[r] = leaf_root<false, false>(f, q, B, t);
         return;
     }
 
@@ -208,7 +171,7 @@ __global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
         } else {
             const float *pj = a.params + j * 4 + xp * 2;
             float m0, m1;
-            pull(a, t, j, m0, m1);
+            leaf_pull(f, t, B, j, m0, m1);
             if (MODE == kMpe) {
                 v = (pj[1] + m1) > (pj[0] + m0);
             } else {

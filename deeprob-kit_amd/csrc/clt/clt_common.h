@@ -1,7 +1,11 @@
 // What the translation units of libdeeprob_clt.so share: the library's instance of the shared entry-point scaffolding
-// (error text, checks), lse2 / lse64 of the header's order of operations, the shape of the segmented pair-count tile, and a
-// cutset network's leaf: its tables, the gather path and the upward pass (cnet.hip evaluates with them, cnet_queries.hip
-// evaluates and then walks back down).  The samplers draw with dp_device::counter_uniform (shared/device.h).
+// (error text, checks, check_net for the arguments every network query takes), lse2 / lse64 of the header's order of
+// operations, the shape of the segmented pair-count tile, copy_rows (a work-group's rows of x to out), a tree as a Leaf
+// with its passes (gather, upward, beliefs: a leaf of a cutset network, or with COLS = false a stand-alone tree), and a
+// cutset network as a Net with THE walk of its OR tree: or_walk owns the explicit stack and the guard that keeps a row
+// inside it, a visitor says what a query computes on the way (ValueVisitor here: the log likelihood, for cnet.hip and
+// the first walk of marginals.hip; cnet_queries.hip and marginals.hip bring their own).  The samplers draw with
+// dp_device::counter_uniform (shared/device.h).
 #pragma once
 #include "../../../include/deeprob_clt.h"
 #define DP_ENTRY_NS dpc_detail
@@ -34,29 +38,55 @@ __device__ __forceinline__ double lse64(double x, double y) {
     return hi + log1p(exp(lo - hi));
 }
 
-// ---- a leaf of a cutset network: one thread per row, codes as q[col * B], the pass's state as t[(2 j + l) * B] ----------
+// the work-group's rows of x to out as bits, consecutive lanes on consecutive addresses: rows r0 .. r0 + THREADS of b are
+// one contiguous piece of [b][d].  The caller synchronises before a row's thread overwrites what another lane copied.
+template <int THREADS>
+__device__ __forceinline__ void copy_rows(const uint32_t *x, uint32_t *out, int64_t b, int d) {
+    const int64_t r0 = (int64_t)blockIdx.x * THREADS;
+    const int64_t rows = b - r0 < THREADS ? b - r0 : THREADS;
+    const int64_t e0 = r0 * d, n = rows * d;
+    for (int64_t e = threadIdx.x; e < n; e += THREADS) out[e0 + e] = x[e0 + e];
+}
+
+// ---- a tree: one thread per row, codes as q[col * B], the pass's state as t[(2 j + l) * B] ------------------------------
 struct Leaf {
     int d;
     const int32_t *col, *bfs, *parent, *child_off, *child_idx;
     const float *params;
 };
 
-__device__ __forceinline__ Leaf leaf_of(const int32_t *leaf_meta, const int32_t *leaf_ints, const float *leaf_params, int l) {
-    const int32_t *m = leaf_meta + 3 * (int64_t)l;
+// the tables of a cutset network in the order of the entry points' arguments, and the levels they declare
+struct Net {
+    const int32_t *node_col, *node_child;
+    const double *node_logw;
+    const int32_t *leaf_meta, *leaf_ints;
+    const float *leaf_params;
+    int levels;
+};
+
+__device__ __forceinline__ Leaf leaf_of(const Net &net, int l) {
+    const int32_t *m = net.leaf_meta + 3 * (int64_t)l;
     const int d = m[0];
-    const int32_t *ints = leaf_ints + m[1];
-    return {d, ints, ints + d, ints + 2 * d, ints + 3 * d, ints + 4 * d + 1, leaf_params + m[2]};
+    const int32_t *ints = net.leaf_ints + m[1];
+    return {d, ints, ints + d, ints + 2 * d, ints + 3 * d, ints + 4 * d + 1, net.leaf_params + m[2]};
 }
 
-// s += params[i][x_parent(i)][x_i] over the leaf's positions in order; false (and s unspecified) if an entry is missing
+// s += params[i][x_parent(i)][x_i] over the tree's positions in order; false (and s unspecified) if an entry is missing.
+// COLS = false: a stand-alone tree, position i is column i and f.col is unused.  A leaf of a network leaves at the first
+// missing entry (most of the leaves a row with NaN visits hold one); the stand-alone tree, whose complete rows are the
+// case that counts, has no exit inside the loop, so that the loads of successive positions overlap (measured on 784
+// columns: 1.14 ms against 1.33 ms with the exit).
+template <bool COLS = true>
 __device__ __forceinline__ bool leaf_gather(const Leaf &f, const uint8_t *q, int64_t B, double &s) {
+    bool whole = true;
     for (int i = 0; i < f.d; ++i) {
         const int pa = f.parent[i];
-        const int ci = q[(int64_t)f.col[i] * B], cp = pa < 0 ? 0 : q[(int64_t)f.col[pa] * B];
-        if (ci == DPC_MISSING) return false;
-        s += (double)f.params[i * 4 + cp * 2 + ci];
+        const int ci = q[(int64_t)(COLS ? f.col[i] : i) * B], cp = pa < 0 ? 0 : q[(int64_t)(COLS ? f.col[pa] : pa) * B];
+        if (ci != DPC_MISSING && cp != DPC_MISSING) s += (double)f.params[i * 4 + cp * 2 + ci];
+        else if (COLS) return false;
+        else whole = false;
     }
-    return true;
+    return whole;
 }
 
 __device__ __forceinline__ void leaf_pull(const Leaf &f, const float *t, int64_t B, int j, float &m0, float &m1) {
@@ -70,10 +100,11 @@ __device__ __forceinline__ void leaf_pull(const Leaf &f, const float *t, int64_t
     }
 }
 
-// the upward pass of dpc_clt_log_likelihood (R = lse) or of dpc_clt_mpe (MAX: R = max) over the leaf's columns, ending
-// at the root as the log likelihood does.  COLS = false: a stand-alone tree, position j is column j and f.col is unused.
+// the upward pass of dpc_clt_log_likelihood (R = lse) or of dpc_clt_mpe (MAX: R = max) over the tree's columns, in two
+// parts: the messages t_j of every node but the root, children before parents, and the root's value, which is the log
+// likelihood (a query that only goes back down never asks for it).  COLS as in leaf_gather.
 template <bool MAX, bool COLS = true>
-__device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+__device__ void leaf_messages(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
     for (int p = f.d - 1; p >= 1; --p) {
         const int j = f.bfs[p];
         const float *pj = f.params + j * 4;
@@ -95,6 +126,10 @@ __device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *
         t[2 * (int64_t)j * B] = t0;
         t[(2 * (int64_t)j + 1) * B] = t1;
     }
+}
+
+template <bool MAX, bool COLS = true>
+__device__ __forceinline__ float leaf_root(const Leaf &f, const uint8_t *q, int64_t B, const float *t) {
     const int j = f.bfs[0];
     const float *pj = f.params + j * 4;
     const int cj = q[(int64_t)(COLS ? f.col[j] : j) * B];
@@ -104,7 +139,13 @@ __device__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *
     return MAX ? fmaxf(pj[0] + m0, pj[1] + m1) : lse2(pj[0] + m0, pj[1] + m1);
 }
 
-// the downward pass of the posterior marginals (dpc_mar_*), after leaf_upward<false>: in `bfs` order the normalised log
+template <bool MAX, bool COLS = true>
+__device__ __forceinline__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+    leaf_messages<MAX, COLS>(f, q, B, t);
+    return leaf_root<MAX, COLS>(f, q, B, t);
+}
+
+// the downward pass of the posterior marginals (dpc_mar_*), after leaf_messages<false>: in `bfs` order the normalised log
 // belief b_j takes the slot of t_j (t_j is read here for the last time; the children's t are still whole when j pulls
 // them), and sink(column, expf(b_j[1])) is called for every NaN position
 template <bool COLS, typename Sink>
@@ -135,6 +176,99 @@ __device__ __forceinline__ void leaf_beliefs(const Leaf &f, const uint8_t *q, in
         t[(2 * j + 1) * B] = b1;
         if (cj == DPC_MISSING) sink(col, expf(b1));
     }
+}
+
+// ---- the walk of a cutset network's OR tree ----------------------------------------------------------------------------
+// One row, depth first, with an explicit stack ns[depth * B] of at most `levels` entries.  An entry is 4 * node + state:
+// 0 = new, 1 = NaN, left child running, 2 = NaN, right child running, 3 = observed, its one child running.  What a query
+// computes is its visitor's business; depth * B is the slot of the node in the visitor's own [levels][b] scratch:
+//     v.leaf(k, depth)             node k is a leaf (its tree: leaf_of(net, net.node_child[2 * k]))
+//     v.left_done(k, depth)        the left side of the NaN node k has returned, the right side is about to start
+//     v.descend(k, side, depth)    the walk goes down to child `side` of k, whose slot will be depth + 1
+//     v.both_done(k, col, depth)   the right side of the NaN node k, of column col, has returned
+//     v.one_done(k, c, depth)      the one side c of the observed node k has returned
+// False if the tables are deeper than `levels`: the walk stops before it writes past the stack, the visitor's scratch is
+// then half used and the caller writes its own NaN answer.
+template <typename Visitor>
+__device__ __forceinline__ bool or_walk(const Net &net, const uint8_t *q, int64_t B, int32_t *ns, Visitor &v) {
+    int depth = 0;
+    ns[0] = 0;
+    while (depth >= 0) {
+        const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
+        const int col = net.node_col[k];
+        if (col < 0) {
+            v.leaf(k, depth);
+            --depth;
+            continue;
+        }
+        const int c = q[(int64_t)col * B];
+        if (st == 0 || st == 1) {
+            if (depth + 1 >= net.levels) return false;
+            int side;
+            if (st == 1) {
+                v.left_done(k, depth);
+                ns[depth * B] = 4 * k + 2;
+                side = 1;
+            } else if (c != DPC_MISSING) {
+                ns[depth * B] = 4 * k + 3;
+                side = c;
+            } else {
+                ns[depth * B] = 4 * k + 1;
+                side = 0;
+            }
+            v.descend(k, side, depth);
+            const int next = net.node_child[2 * k + side];
+            ++depth;
+            ns[depth * B] = 4 * next;
+        } else if (st == 2) {
+            v.both_done(k, col, depth);
+            --depth;
+        } else {
+            v.one_done(k, c, depth);
+            --depth;
+        }
+    }
+    return true;
+}
+
+// the value of a tree under the row's evidence: the gather path where nothing of it is missing, else the upward pass
+template <bool MAX>
+__device__ __forceinline__ double leaf_value(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+    double s = 0.0;
+    return leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward<MAX>(f, q, B, t);
+}
+
+// The log likelihood: `ret` is the value the node just left returned, in float64; val [levels][b], t [2 max_leaf_d][b].
+struct ValueVisitor {
+    const Net &net;
+    const uint8_t *q;
+    int64_t B;
+    double *val;
+    float *t;
+    double ret;
+
+    __device__ __forceinline__ void leaf(int k, int) { ret = leaf_value<false>(leaf_of(net, net.node_child[2 * k]), q, B, t); }
+    __device__ __forceinline__ void left_done(int k, int depth) { val[depth * B] = net.node_logw[2 * k] + ret; }
+    __device__ __forceinline__ void descend(int, int, int) {}
+    __device__ __forceinline__ void both_done(int k, int, int depth) {
+        ret = lse64(val[depth * B], net.node_logw[2 * k + 1] + ret);
+    }
+    __device__ __forceinline__ void one_done(int k, int c, int) { ret = net.node_logw[2 * k + c] + ret; }
+};
+
+// the checks every network query makes of its arguments, in this order; `pointers`: whether the entry point's own
+// pointers (all but node_logw, which a network of one node may leave out) are there
+inline int check_net(const char *what, int64_t b, int d, int n_nodes, int levels, int max_leaf_d, bool pointers,
+                     const double *node_logw, const void *work) {
+    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "%s: d = %d is outside 1..%d", what, d, DPC_MAX_D);
+    DPC_REQUIRE(b >= 0 && b <= kMaxGridX, "%s: b = %lld is out of domain", what, (long long)b);
+    DPC_REQUIRE(n_nodes >= 1 && n_nodes < (1 << 29), "%s: n_nodes = %d is outside 1..2^29-1", what, n_nodes);
+    DPC_REQUIRE(levels >= 1 && levels <= d + 1, "%s: levels = %d is outside 1..d+1", what, levels);
+    DPC_REQUIRE(max_leaf_d >= 1 && max_leaf_d <= d, "%s: max_leaf_d = %d is outside 1..d", what, max_leaf_d);
+    DPC_REQUIRE(pointers, "%s: null pointer", what);
+    DPC_REQUIRE(node_logw || n_nodes == 1, "%s: null pointer (node_logw)", what);
+    DPC_REQUIRE(((uintptr_t)work & 7) == 0, "%s: work is not 8-byte aligned", what);
+    return DPC_OK;
 }
 
 }  // namespace dpc_detail

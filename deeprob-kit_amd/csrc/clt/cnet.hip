@@ -8,16 +8,16 @@
 // words only; the scores are one thread per (task, column) for the conditional entropies and one thread per task for the
 // serial sums the header orders; partition_kernel splits a segment by the bits of its cut column, one work-group per task,
 // the position of a row from popcounts (no atomics, no scan through memory).  The query is one thread per row: a complete
-// row walks one path, a row with NaN walks the OR tree depth first with its stack in `work`.
+// row walks one path, a row with NaN walks the OR tree depth first with its stack in `work` (or_walk of clt_common.h).
 #include "clt_common.h"
 
 namespace {
 
-using dpc_detail::Leaf;
 using dpc_detail::leaf_gather;
 using dpc_detail::leaf_of;
-using dpc_detail::leaf_upward;
-using dpc_detail::lse64;
+using dpc_detail::Net;
+using dpc_detail::or_walk;
+using dpc_detail::ValueVisitor;
 
 typedef unsigned long long u64;
 constexpr int kThreads = 256;
@@ -240,11 +240,7 @@ __global__ __launch_bounds__(kThreads) void partition_kernel(const u64 *__restri
 struct CnetArgs {
     const uint8_t *codes;
     int64_t b;
-    const int32_t *node_col, *node_child;
-    const double *node_logw;
-    const int32_t *leaf_meta, *leaf_ints;
-    const float *leaf_params;
-    int levels;
+    Net net;
     double *val;        // [levels][b]
     float *t;           // [2 max_leaf_d][b]
     int32_t *ns;        // [levels][b]
@@ -261,67 +257,24 @@ __global__ __launch_bounds__(kRowThreads) void cnet_query_kernel(const CnetArgs 
         int k = 0;
         double s = 0.0;
         bool complete = true;
-        for (int col = a.node_col[k]; col >= 0; col = a.node_col[k]) {
+        for (int col = a.net.node_col[k]; col >= 0; col = a.net.node_col[k]) {
             const int c = q[(int64_t)col * B];
             if (c == DPC_MISSING) {
                 complete = false;
                 break;
             }
-            s += a.node_logw[2 * k + c];
-            k = a.node_child[2 * k + c];
+            s += a.net.node_logw[2 * k + c];
+            k = a.net.node_child[2 * k + c];
         }
-        if (complete && leaf_gather(leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]), q, B, s)) {
+        if (complete && leaf_gather(leaf_of(a.net, a.net.node_child[2 * k]), q, B, s)) {
             a.out[r] = (float)s;
             return;
         }
     }
 
-    // depth first; a stack entry is 4 * node + state: 0 = new, 1 = NaN, left child running, 2 = NaN, right child
-    // running, 3 = observed, its one child running
-    double *val = a.val + r;
-    int32_t *ns = a.ns + r;
-    int depth = 0;
-    double ret = 0.0;
-    ns[0] = 0;
-    while (depth >= 0) {
-        const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
-        const int col = a.node_col[k];
-        if (col < 0) {
-            const Leaf f = leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]);
-            double s = 0.0;
-            ret = leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward<false>(f, q, B, a.t + r);
-            --depth;
-            continue;
-        }
-        const int c = q[(int64_t)col * B];
-        if (st == 0 || st == 1) {
-            if (depth + 1 >= a.levels) {        // the tables are not a tree of `levels` levels: no write past the stack
-                a.out[r] = NAN;
-                return;
-            }
-            int next;
-            if (st == 1) {
-                val[depth * B] = a.node_logw[2 * k] + ret;
-                ns[depth * B] = 4 * k + 2;
-                next = a.node_child[2 * k + 1];
-            } else if (c != DPC_MISSING) {
-                ns[depth * B] = 4 * k + 3;
-                next = a.node_child[2 * k + c];
-            } else {
-                ns[depth * B] = 4 * k + 1;
-                next = a.node_child[2 * k];
-            }
-            ++depth;
-            ns[depth * B] = 4 * next;
-        } else if (st == 2) {
-            ret = lse64(val[depth * B], a.node_logw[2 * k + 1] + ret);
-            --depth;
-        } else {
-            ret = a.node_logw[2 * k + c] + ret;
-            --depth;
-        }
-    }
-    a.out[r] = (float)ret;
+    // a row with NaN: the walk of clt_common.h; tables that are not a tree of `levels` levels give NaN
+    ValueVisitor v = {a.net, q, B, a.val + r, a.t + r, 0.0};
+    a.out[r] = or_walk(a.net, q, B, a.ns + r, v) ? (float)v.ret : NAN;
 }
 
 }  // namespace
@@ -386,20 +339,15 @@ int dpc_cnet_log_likelihood(const uint8_t *codes, int64_t b, int d, int n_nodes,
                             const int32_t *node_child, const double *node_logw, const int32_t *leaf_meta,
                             const int32_t *leaf_ints, const float *leaf_params, int levels, int max_leaf_d, void *work,
                             float *out, void *stream) {
-    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_cnet_log_likelihood: d = %d is outside 1..%d", d, DPC_MAX_D);
-    DPC_REQUIRE(b >= 0 && b <= kMaxGridX, "dpc_cnet_log_likelihood: b = %lld is out of domain", (long long)b);
-    DPC_REQUIRE(n_nodes >= 1 && n_nodes < (1 << 29), "dpc_cnet_log_likelihood: n_nodes = %d is outside 1..2^29-1", n_nodes);
-    DPC_REQUIRE(levels >= 1 && levels <= d + 1, "dpc_cnet_log_likelihood: levels = %d is outside 1..d+1", levels);
-    DPC_REQUIRE(max_leaf_d >= 1 && max_leaf_d <= d, "dpc_cnet_log_likelihood: max_leaf_d = %d is outside 1..d", max_leaf_d);
-    DPC_REQUIRE(codes && node_col && node_child && leaf_meta && leaf_ints && leaf_params && work && out,
-                "dpc_cnet_log_likelihood: null pointer");
-    DPC_REQUIRE(node_logw || n_nodes == 1, "dpc_cnet_log_likelihood: null pointer (node_logw)");
-    DPC_REQUIRE(((uintptr_t)work & 7) == 0, "dpc_cnet_log_likelihood: work is not 8-byte aligned");
+    if (int rc = dpc_detail::check_net("dpc_cnet_log_likelihood", b, d, n_nodes, levels, max_leaf_d,
+                                       codes && node_col && node_child && leaf_meta && leaf_ints && leaf_params && work && out,
+                                       node_logw, work))
+        return rc;
     if (b == 0) return DPC_OK;
     char *w = (char *)work;
-    CnetArgs a = {codes, b, node_col, node_child, node_logw, leaf_meta, leaf_ints, leaf_params, levels,
-                  (double *)w, (float *)(w + 8 * (int64_t)levels * b),
-                  (int32_t *)(w + (8 * (int64_t)levels + 8 * (int64_t)max_leaf_d) * b), out};
+    const CnetArgs a = {codes, b, {node_col, node_child, node_logw, leaf_meta, leaf_ints, leaf_params, levels},
+                        (double *)w, (float *)(w + 8 * (int64_t)levels * b),
+                        (int32_t *)(w + (8 * (int64_t)levels + 8 * (int64_t)max_leaf_d) * b), out};
     DPC_LAUNCH("dpc_cnet_log_likelihood", cnet_query_kernel, dim3((unsigned)((b + kRowThreads - 1) / kRowThreads)),
                dim3(kRowThreads), 0, (hipStream_t)stream, a);
     return DPC_OK;

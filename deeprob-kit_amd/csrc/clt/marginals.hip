@@ -6,12 +6,12 @@
 // Layout of the work.  One thread per row, one wave per work-group, scratch as [slot][b] so that the lanes of a wave read
 // and write consecutive addresses and the tables are wave-uniform loads.
 //
-// The tree: the wave copies its 64 rows of x to `out` with consecutive lanes on consecutive addresses; a row with NaN
-// then runs the upward pass of dpc_clt_log_likelihood and one downward pass (clt_common.h, leaf_beliefs) that turns the
-// messages into normalised beliefs in place, and overwrites its NaN entries of `out`.
+// The tree: the wave copies its 64 rows of x to `out` (copy_rows); a row with NaN then runs the messages of
+// dpc_clt_log_likelihood and one downward pass (clt_common.h, leaf_beliefs) that turns them into normalised beliefs in
+// place, and overwrites its NaN entries of `out`.
 //
-// The network: a row with NaN walks the OR tree depth first twice with the explicit stack of cnet_query_kernel.  The first
-// walk is the log likelihood and keeps log P(e) in float64.  The second carries the prefix weight of the path down; at a
+// The network: a row with NaN walks the OR tree twice with or_walk of clt_common.h.  The first walk is the log
+// likelihood (ValueVisitor) and keeps log P(e) in float64.  The second carries the prefix weight of the path down; at a
 // leaf it forms pi_l = exp(W_l - log P(e)) and, where the leaf holds NaN columns, runs the leaf's two passes and adds
 // pi_l * mu_l to the row's accumulators; every node returns the sum of pi_l below it, which is what a NaN cut variable
 // adds to its own accumulator for the right side.  The D accumulators of a row are float64 scratch [d][b]: a leaf's pass
@@ -27,8 +27,10 @@ using dpc_detail::Leaf;
 using dpc_detail::leaf_beliefs;
 using dpc_detail::leaf_gather;
 using dpc_detail::leaf_of;
+using dpc_detail::leaf_messages;
 using dpc_detail::leaf_upward;
-using dpc_detail::lse64;
+using dpc_detail::Net;
+using dpc_detail::or_walk;
 using dpc_detail::kMaxGridX;
 
 constexpr int kRowThreads = 64;
@@ -52,12 +54,7 @@ struct TreeArgs {
 __global__ __launch_bounds__(kRowThreads) void clt_marginals_kernel(const TreeArgs a) {
     const int64_t B = a.b;
     const int D = a.d;
-    {   // the work-group's rows are one contiguous piece of x
-        const int64_t r0 = (int64_t)blockIdx.x * kRowThreads;
-        const int64_t rows = B - r0 < kRowThreads ? B - r0 : kRowThreads;
-        const int64_t e0 = r0 * D, n = rows * D;
-        for (int64_t e = threadIdx.x; e < n; e += kRowThreads) a.out[e0 + e] = a.x[e0 + e];
-    }
+    dpc_detail::copy_rows<kRowThreads>(a.x, a.out, B, D);
     __syncthreads();        // a row's thread overwrites what another lane copied
     const int64_t r = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
     if (r >= B) return;
@@ -68,7 +65,7 @@ __global__ __launch_bounds__(kRowThreads) void clt_marginals_kernel(const TreeAr
     const Leaf f = {D, nullptr, a.bfs, a.parent, a.child_off, a.child_idx, a.params};
     float *t = a.work + r;
     uint32_t *o = a.out + r * D;
-    leaf_upward<false, false>(f, q, B, t);
+    leaf_messages<false, false>(f, q, B, t);
     leaf_beliefs<false>(f, q, B, t, [o](int col, float p1) { o[col] = __float_as_uint(p1); });
 }
 
@@ -78,11 +75,7 @@ struct NetArgs {
     const uint8_t *codes;
     int64_t b;
     int d;
-    const int32_t *node_col, *node_child;
-    const double *node_logw;
-    const int32_t *leaf_meta, *leaf_ints;
-    const float *leaf_params;
-    int levels;
+    Net net;
     double *val;        // [levels][b]: the value (first walk) or the sum of pi (second walk) the left side returned
     double *pre;        // [levels][b]: the prefix weight of the node on the stack
     double *acc;        // [d][b]
@@ -91,127 +84,65 @@ struct NetArgs {
     uint32_t *out;
 };
 
+// The second walk: pre[depth * B] is the prefix weight W of the node on the stack, `ret` the sum of pi_l over the
+// consistent leaves below the node just left; acc [d][b] takes pi_l * mu_l of every such leaf with NaN columns and, at a NaN
+// cut variable, the sum of pi_l of its right side.
+struct PrefixVisitor {
+    const Net &net;
+    const uint8_t *q;
+    int64_t B;
+    double *val, *pre, *acc;
+    float *t;
+    double log_pe, ret;
+
+    __device__ __forceinline__ void leaf(int k, int depth) {
+        const Leaf f = leaf_of(net, net.node_child[2 * k]);
+        const double p = pre[depth * B];
+        double s = 0.0;
+        if (leaf_gather(f, q, B, s)) {
+            ret = exp((p + (double)(float)s) - log_pe);
+        } else {
+            const double pi = exp((p + (double)leaf_upward<false>(f, q, B, t)) - log_pe);
+            if (pi > 0.0)
+                leaf_beliefs<true>(f, q, B, t, [acc = acc, B = B, pi](int c, float p1) { acc[(int64_t)c * B] += pi * (double)p1; });
+            ret = pi;
+        }
+    }
+    __device__ __forceinline__ void left_done(int, int depth) { val[depth * B] = ret; }
+    __device__ __forceinline__ void descend(int k, int side, int depth) {
+        pre[(depth + 1) * B] = pre[depth * B] + net.node_logw[2 * k + side];
+    }
+    __device__ __forceinline__ void both_done(int, int col, int depth) {
+        acc[(int64_t)col * B] += ret;
+        ret = val[depth * B] + ret;
+    }
+    __device__ __forceinline__ void one_done(int, int, int) {}
+};
+
 __device__ __forceinline__ void fill_nan(const NetArgs &a, int64_t r) {
     for (int c = 0; c < a.d; ++c) a.acc[(int64_t)c * a.b + r] = (double)NAN;
 }
 
 // the row's accumulators: p(x_c = 1 | e) for every NaN column c, NaN in all of them for a row that cannot be answered
+// (tables that are not a tree of `levels` levels, or evidence of probability zero)
 __device__ void net_row(const NetArgs &a, int64_t r) {
     const int64_t B = a.b;
     const uint8_t *q = a.codes + r;
     bool missing = false;
     for (int c = 0; c < a.d; ++c) missing = missing || q[(int64_t)c * B] == DPC_MISSING;
     if (!missing) return;       // nothing of the accumulators is read
-    double *val = a.val + r, *pre = a.pre + r, *acc = a.acc + r;
-    int32_t *ns = a.ns + r;
-    float *t = a.t + r;
+    double *acc = a.acc + r;
 
-    // depth first; a stack entry is 4 * node + state: 0 = new, 1 = NaN, left child running, 2 = NaN, right child
-    // running, 3 = observed, its one child running
-    double log_pe;
-    {
-        int depth = 0;
-        double ret = 0.0;
-        ns[0] = 0;
-        while (depth >= 0) {
-            const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
-            const int col = a.node_col[k];
-            if (col < 0) {
-                const Leaf f = leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]);
-                double s = 0.0;
-                ret = leaf_gather(f, q, B, s) ? (double)(float)s : (double)leaf_upward<false>(f, q, B, t);
-                --depth;
-                continue;
-            }
-            const int c = q[(int64_t)col * B];
-            if (st == 0 || st == 1) {
-                if (depth + 1 >= a.levels) {        // the tables are not a tree of `levels` levels: no write past the stack
-                    fill_nan(a, r);
-                    return;
-                }
-                int next;
-                if (st == 1) {
-                    val[depth * B] = a.node_logw[2 * k] + ret;
-                    ns[depth * B] = 4 * k + 2;
-                    next = a.node_child[2 * k + 1];
-                } else if (c != DPC_MISSING) {
-                    ns[depth * B] = 4 * k + 3;
-                    next = a.node_child[2 * k + c];
-                } else {
-                    ns[depth * B] = 4 * k + 1;
-                    next = a.node_child[2 * k];
-                }
-                ++depth;
-                ns[depth * B] = 4 * next;
-            } else if (st == 2) {
-                ret = lse64(val[depth * B], a.node_logw[2 * k + 1] + ret);
-                --depth;
-            } else {
-                ret = a.node_logw[2 * k + c] + ret;
-                --depth;
-            }
-        }
-        log_pe = ret;
-    }
-    if (log_pe == -INFINITY) {      // evidence of probability zero
+    dpc_detail::ValueVisitor value = {a.net, q, B, a.val + r, a.t + r, 0.0};
+    if (!or_walk(a.net, q, B, a.ns + r, value) || value.ret == -INFINITY) {
         fill_nan(a, r);
         return;
     }
     for (int c = 0; c < a.d; ++c) acc[(int64_t)c * B] = 0.0;
 
-    // the same walk; `ret` is the sum of pi_l over the consistent leaves below the node
-    int depth = 0;
-    double ret = 0.0;
-    ns[0] = 0;
-    pre[0] = 0.0;
-    while (depth >= 0) {
-        const int enc = ns[depth * B], k = enc >> 2, st = enc & 3;
-        const int col = a.node_col[k];
-        if (col < 0) {
-            const Leaf f = leaf_of(a.leaf_meta, a.leaf_ints, a.leaf_params, a.node_child[2 * k]);
-            const double p = pre[depth * B];
-            double s = 0.0;
-            if (leaf_gather(f, q, B, s)) {
-                ret = exp((p + (double)(float)s) - log_pe);
-            } else {
-                const double pi = exp((p + (double)leaf_upward<false>(f, q, B, t)) - log_pe);
-                if (pi > 0.0) leaf_beliefs<true>(f, q, B, t, [acc, B, pi](int c, float p1) { acc[(int64_t)c * B] += pi * (double)p1; });
-                ret = pi;
-            }
-            --depth;
-            continue;
-        }
-        const int c = q[(int64_t)col * B];
-        if (st == 0 || st == 1) {
-            if (depth + 1 >= a.levels) {
-                fill_nan(a, r);
-                return;
-            }
-            int next, side;
-            if (st == 1) {
-                val[depth * B] = ret;
-                ns[depth * B] = 4 * k + 2;
-                side = 1;
-            } else if (c != DPC_MISSING) {
-                ns[depth * B] = 4 * k + 3;
-                side = c;
-            } else {
-                ns[depth * B] = 4 * k + 1;
-                side = 0;
-            }
-            next = a.node_child[2 * k + side];
-            const double p = pre[depth * B] + a.node_logw[2 * k + side];
-            ++depth;
-            ns[depth * B] = 4 * next;
-            pre[depth * B] = p;
-        } else if (st == 2) {
-            acc[(int64_t)col * B] += ret;
-            ret = val[depth * B] + ret;
-            --depth;
-        } else {
-            --depth;
-        }
-    }
+    PrefixVisitor prefix = {a.net, q, B, a.val + r, a.pre + r, acc, a.t + r, value.ret, 0.0};
+    prefix.pre[0] = 0.0;
+    if (!or_walk(a.net, q, B, a.ns + r, prefix)) fill_nan(a, r);
 }
 
 __global__ __launch_bounds__(kRowThreads) void cnet_marginals_kernel(const NetArgs a) {
@@ -253,21 +184,16 @@ int dpc_mar_clt(const float *x, const uint8_t *codes, int64_t b, int d, const in
 int dpc_mar_cnet(const float *x, const uint8_t *codes, int64_t b, int d, int n_nodes, const int32_t *node_col,
                  const int32_t *node_child, const double *node_logw, const int32_t *leaf_meta, const int32_t *leaf_ints,
                  const float *leaf_params, int levels, int max_leaf_d, void *work, float *out, void *stream) {
-    DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_mar_cnet: d = %d is outside 1..%d", d, DPC_MAX_D);
-    DPC_REQUIRE(b >= 0 && b <= kMaxGridX, "dpc_mar_cnet: b = %lld is out of domain", (long long)b);
-    DPC_REQUIRE(n_nodes >= 1 && n_nodes < (1 << 29), "dpc_mar_cnet: n_nodes = %d is outside 1..2^29-1", n_nodes);
-    DPC_REQUIRE(levels >= 1 && levels <= d + 1, "dpc_mar_cnet: levels = %d is outside 1..d+1", levels);
-    DPC_REQUIRE(max_leaf_d >= 1 && max_leaf_d <= d, "dpc_mar_cnet: max_leaf_d = %d is outside 1..d", max_leaf_d);
-    DPC_REQUIRE(x && codes && node_col && node_child && leaf_meta && leaf_ints && leaf_params && work && out,
-                "dpc_mar_cnet: null pointer");
-    DPC_REQUIRE(node_logw || n_nodes == 1, "dpc_mar_cnet: null pointer (node_logw)");
-    DPC_REQUIRE(((uintptr_t)work & 7) == 0, "dpc_mar_cnet: work is not 8-byte aligned");
+    if (int rc = dpc_detail::check_net("dpc_mar_cnet", b, d, n_nodes, levels, max_leaf_d,
+                                       x && codes && node_col && node_child && leaf_meta && leaf_ints && leaf_params && work && out,
+                                       node_logw, work))
+        return rc;
     if (b == 0) return DPC_OK;
     char *w = (char *)work;
     const int64_t o_pre = 8 * (int64_t)levels * b, o_acc = 2 * o_pre, o_t = o_acc + 8 * (int64_t)d * b,
                   o_ns = o_t + 8 * (int64_t)max_leaf_d * b;
-    const NetArgs a = {(const uint32_t *)x, codes, b, d, node_col, node_child, node_logw, leaf_meta, leaf_ints, leaf_params,
-                       levels, (double *)w, (double *)(w + o_pre), (double *)(w + o_acc), (float *)(w + o_t),
+    const NetArgs a = {(const uint32_t *)x, codes, b, d,
+                       {node_col, node_child, node_logw, leaf_meta, leaf_ints, leaf_params, levels}, (double *)w, (double *)(w + o_pre), (double *)(w + o_acc), (float *)(w + o_t),
                        (int32_t *)(w + o_ns), (uint32_t *)out};
     DPC_LAUNCH("dpc_mar_cnet", cnet_marginals_kernel, dim3((unsigned)((b + kRowThreads - 1) / kRowThreads)),
                dim3(kRowThreads), 0, (hipStream_t)stream, a);

@@ -34,6 +34,26 @@ def _rows(x: torch.Tensor, name: str) -> torch.Tensor:
     return x
 
 
+def run_on_device(model, name: str, op, x, *args):
+    """``op(model._on_device(device), x on the device, *args)`` under the input rules of ``BinaryCLT`` and ``BinaryCNet``
+    (``model``: one of them, ``name``: what it calls itself in a message): numpy in, numpy out through the current device;
+    a device tensor stays on its device; a CPU tensor or a missing library raises ``HipError``."""
+    load_library()
+    as_numpy = not isinstance(x, torch.Tensor)
+    if as_numpy:
+        if not torch.cuda.is_available():
+            raise HipError("{} needs a HIP device (there is no CPU fallback)".format(name))
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
+    elif not x.is_cuda:
+        raise HipError("x lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
+                       "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
+                       "device tensor".format(x.device))
+    if x.dim() != 2 or x.shape[1] != len(model.scope):
+        raise ValueError("expected inputs [B, {}], got {}".format(len(model.scope), tuple(x.shape)))
+    out = op(model._on_device(x.device), x, *args)
+    return out.cpu().numpy() if as_numpy else out
+
+
 def children_csr(bfs, parent):
     """``(child_off [D + 1], child_idx [D - 1])`` int32: the children of every node in decreasing position in ``bfs``
     (the header's list order)."""

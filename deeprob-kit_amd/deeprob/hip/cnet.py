@@ -206,74 +206,67 @@ class DeviceCNet:
         #: whether every root-to-leaf path accounts for every column, as a cut or in the leaf's scope
         self.covered = bool(covered)
 
+    def pointers(self, parent: bool = False):
+        """The table arguments of a query in ABI order; ``parent``: with ``node_parent`` (the ``dpc_cnq_*`` entries)."""
+        nodes = (self.node_col, self.node_child) + ((self.node_parent,) if parent else ()) + (self.node_logw,)
+        return tuple(t.data_ptr() for t in nodes + (self.leaf_meta, self.leaf_ints, self.leaf_params)) \
+            + (self.levels, self.max_leaf_d)
 
-def _query_rows_of(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
+
+def _pieces(model: DeviceCNet, x: torch.Tensor, row_bytes: int, out_shape, want_choice: bool = False):
+    """A query over a long batch, in pieces of ``query_rows(row_bytes)`` rows that share one ``work`` buffer: checks ``x`` and
+    returns ``(out, choice or None, pieces)``, ``out`` float32 of ``out_shape(b, d)``, ``choice`` ``[B]`` int32 and a piece
+    ``(r0, xs, codes, n, work pointer, out pointer, choice pointer or None, stream)`` -- its packed codes and its slices."""
     x = hip.require_device_f32(x, 'x')
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != model.d:
         raise ValueError("expected inputs [B, {}], got {}".format(model.d, tuple(x.shape)))
     if x.device != model.device:
         raise HipError("x lives on '{}', the model on '{}'".format(x.device, model.device))
-    return x
+    b, d = x.shape
+    st = hip.stream_ptr(x.device)
+    out = torch.empty(out_shape(b, d), dtype=torch.float32, device=x.device)
+    choice = torch.empty(b, dtype=torch.int32, device=x.device) if want_choice else None
+    step = query_rows(row_bytes)
+    work = torch.empty(row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
+
+    def pieces():
+        for r0 in range(0, b, step):
+            xs = x[r0:r0 + step]
+            yield (r0, xs, clt.pack_query(xs), xs.shape[0], work.data_ptr(), out[r0:r0 + step].data_ptr(),
+                   choice[r0:r0 + step].data_ptr() if want_choice else None, st)
+    return out, choice, pieces()
 
 
 def log_likelihood(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
     """``[B]`` float32 (``dpc_cnet_log_likelihood``); NaN entries are marginalised."""
     lib = load_library()
-    x = _query_rows_of(model, x)
-    b, d = x.shape
-    st = hip.stream_ptr(x.device)
-    out = torch.empty(b, dtype=torch.float32, device=x.device)
-    step = query_rows(model.row_bytes)
-    work = torch.empty(model.row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
-    for r0 in range(0, b, step):
-        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
-        n = xs.shape[0]
-        codes = clt.pack_query(xs)
-        call(lib.dpc_cnet_log_likelihood, codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(),
-             model.node_child.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
-             model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d, work.data_ptr(),
-             os_.data_ptr(), st)
+    out, _, pieces = _pieces(model, x, model.row_bytes, lambda b, d: b)
+    for _, _, codes, n, work, os_, _, st in pieces:
+        call(lib.dpc_cnet_log_likelihood, codes.data_ptr(), n, model.d, model.n_nodes, *model.pointers(), work, os_, st)
     return out
-
-
-def _fill(model: DeviceCNet, x: torch.Tensor, seed, want_choice: bool):
-    """``(out [B, D] float32, choice [B] int32 or None)`` of ``dpc_cnq_mpe`` (``seed`` None) or ``dpc_cnq_sample``, a long batch in
-    pieces of :func:`query_rows` rows; a piece of the sampler starts its counters at its first row (``row0``)."""
-    lib = load_library()
-    x = _query_rows_of(model, x)
-    b, d = x.shape
-    st = hip.stream_ptr(x.device)
-    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
-    choice = torch.empty(b, dtype=torch.int32, device=x.device) if want_choice else None
-    step = query_rows(model.query_row_bytes)
-    work = torch.empty(model.query_row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
-    for r0 in range(0, b, step):
-        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
-        n = xs.shape[0]
-        codes = clt.pack_query(xs)
-        head = (xs.data_ptr(), codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(), model.node_child.data_ptr(),
-                model.node_parent.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
-                model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d)
-        tail = (work.data_ptr(), os_.data_ptr(), choice[r0:r0 + step].data_ptr() if want_choice else None, st)
-        if seed is None:
-            call(lib.dpc_cnq_mpe, *head, *tail)
-        else:
-            call(lib.dpc_cnq_sample, *head, seed, r0, *tail)
-    return out, choice
 
 
 def mpe(model: DeviceCNet, x: torch.Tensor, return_choice: bool = False):
     """``[B, D]`` float32: ``x`` with its NaN entries filled by a most probable completion (``dpc_cnq_mpe``, exact: the OR
     nodes are deterministic).  With ``return_choice`` also ``[B]`` int32, the node number of the winning leaf."""
-    out, choice = _fill(model, x, None, return_choice)
+    lib = load_library()
+    out, choice, pieces = _pieces(model, x, model.query_row_bytes, lambda b, d: (b, d), return_choice)
+    for _, xs, codes, n, work, os_, ch, st in pieces:
+        call(lib.dpc_cnq_mpe, xs.data_ptr(), codes.data_ptr(), n, model.d, model.n_nodes, *model.pointers(parent=True), work,
+             os_, ch, st)
     return (out, choice) if return_choice else out
 
 
 def sample(model: DeviceCNet, x: torch.Tensor, seed: int, return_choice: bool = False):
     """``[B, D]`` float32: ``x`` with its NaN entries drawn from the exact posterior given the observed ones
-    (``dpc_cnq_sample``); the same seed gives the same bytes.  With ``return_choice`` also ``[B]`` int32, the node number of
-    the drawn leaf."""
-    out, choice = _fill(model, x, int(seed) & 0xFFFFFFFFFFFFFFFF, return_choice)
+    (``dpc_cnq_sample``); the same seed gives the same bytes: a piece starts its counters at its first row (``row0``).  With
+    ``return_choice`` also ``[B]`` int32, the node number of the drawn leaf."""
+    lib = load_library()
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    out, choice, pieces = _pieces(model, x, model.query_row_bytes, lambda b, d: (b, d), return_choice)
+    for r0, xs, codes, n, work, os_, ch, st in pieces:
+        call(lib.dpc_cnq_sample, xs.data_ptr(), codes.data_ptr(), n, model.d, model.n_nodes, *model.pointers(parent=True),
+             seed, r0, work, os_, ch, st)
     return (out, choice) if return_choice else out
 
 
@@ -288,18 +281,7 @@ def marginals(model: DeviceCNet, x: torch.Tensor) -> torch.Tensor:
         raise ValueError("marginals need every root-to-leaf path to account for every column, as a cut or in the leaf's "
                          "scope: these tables leave a column out on some path")
     lib = load_library()
-    x = _query_rows_of(model, x)
-    b, d = x.shape
-    st = hip.stream_ptr(x.device)
-    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
-    step = query_rows(model.marginals_row_bytes)
-    work = torch.empty(model.marginals_row_bytes * min(b, step), dtype=torch.uint8, device=x.device)
-    for r0 in range(0, b, step):
-        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
-        n = xs.shape[0]
-        codes = clt.pack_query(xs)
-        call(lib.dpc_mar_cnet, xs.data_ptr(), codes.data_ptr(), n, d, model.n_nodes, model.node_col.data_ptr(),
-             model.node_child.data_ptr(), model.node_logw.data_ptr(), model.leaf_meta.data_ptr(),
-             model.leaf_ints.data_ptr(), model.leaf_params.data_ptr(), model.levels, model.max_leaf_d, work.data_ptr(),
-             os_.data_ptr(), st)
+    out, _, pieces = _pieces(model, x, model.marginals_row_bytes, lambda b, d: (b, d))
+    for _, xs, codes, n, work, os_, _, st in pieces:
+        call(lib.dpc_mar_cnet, xs.data_ptr(), codes.data_ptr(), n, model.d, model.n_nodes, *model.pointers(), work, os_, st)
     return out

@@ -30,7 +30,7 @@ from deeprob.spn.structure.cltree import BinaryCLT
 from deeprob.spn.structure.cnet import BinaryCNet
 from deeprob.utils.graph import maximum_spanning_tree
 from deeprob.utils.random import RandomState, check_random_state
-from deeprob.utils.statistics import compute_mutual_information, device_binary_rows, pair_counts, \
+from deeprob.utils.statistics import compute_mutual_information, device_binary_rows, device_training_rows, pair_counts, \
     priors_joints_from_counts
 
 #: the smoothing of the mutual information behind a BDeu trial tree (the reference's ``fit(..., alpha=0.01)``)
@@ -240,7 +240,7 @@ def select_cand_cuts(data, ess: float = 0.1, n_cand_cuts: int = 10) -> np.ndarra
     _check_ess(ess)
     if n_cand_cuts < 1:
         raise ValueError("n_cand_cuts must be at least 1")
-    x = _device_rows(data)
+    x = device_training_rows(data)
     n, d = x.shape
     gen = cnet.Generation(x, torch.arange(n, dtype=torch.int32, device=x.device), [n])
     gen.pack()
@@ -249,25 +249,6 @@ def select_cand_cuts(data, ess: float = 0.1, n_cand_cuts: int = 10) -> np.ndarra
 
 
 # ---- the learners ----------------------------------------------------------------------------------------------------------
-def _device_rows(data):
-    """The training rows as a contiguous float32 device tensor, checked as ``BinaryCNet.fit`` checks them."""
-    import torch
-    from deeprob.hip import HipError
-    from deeprob.hip.clt import DPC_MAX_D
-    if isinstance(data, torch.Tensor) and not data.is_cuda:
-        raise HipError("data lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
-                       "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
-                       "device tensor".format(data.device))
-    if len(data.shape) != 2 or data.shape[0] < 1 or data.shape[1] < 1:
-        raise ValueError("The data must be a matrix of samples by features")
-    if data.shape[1] > DPC_MAX_D:
-        raise ValueError("expected at most {} variables (DPC_MAX_D), got {}".format(DPC_MAX_D, data.shape[1]))
-    x = device_binary_rows(data)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        x = x.to(torch.float32).contiguous()
-    return x
-
-
 class _Task:
     """An open node: its rows' number, active columns (ascending), and the counts, tree and score it inherited."""
     __slots__ = ('node', 'n', 'cols', 'block', 'tree', 'score')
@@ -284,7 +265,7 @@ def _learn(data, kind: str, par: float, n_cand_cuts: int, random_state) -> Binar
     if n_cand_cuts < 1:
         raise ValueError("n_cand_cuts must be at least 1")
     random_state = check_random_state(random_state)
-    x = _device_rows(data)
+    x = device_training_rows(data)
     t_start, t_host = time.perf_counter(), 0.0
     n_rows, d = x.shape
     scorer = _Scorer(kind, par, n_rows)

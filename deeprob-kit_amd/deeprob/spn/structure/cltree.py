@@ -159,22 +159,8 @@ class BinaryCLT(Leaf):
 
     def _run(self, op, x, *args):
         """``op(tree, x on the device, *args)`` under the input rules of the module docstring."""
-        import torch
-        from deeprob.hip import HipError, clt
-        clt.load_library()
-        as_numpy = not isinstance(x, torch.Tensor)
-        if as_numpy:
-            if not torch.cuda.is_available():
-                raise HipError("BinaryCLT needs a HIP device (there is no CPU fallback)")
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
-        elif not x.is_cuda:
-            raise HipError("x lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
-                           "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
-                           "device tensor".format(x.device))
-        if x.dim() != 2 or x.shape[1] != len(self.scope):
-            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
-        out = op(self._on_device(x.device), x, *args)
-        return out.cpu().numpy() if as_numpy else out
+        from deeprob.hip import clt
+        return clt.run_on_device(self, 'BinaryCLT', op, x, *args)
 
     def log_likelihood(self, x):
         """``[B, 1]`` float32 log likelihoods; NaN entries are marginalised."""

@@ -124,20 +124,13 @@ class BinaryCNet(ORNode):
         """
         import torch
         from deeprob.hip import cnet
-        from deeprob.hip.clt import DPC_MAX_D
-        from deeprob.utils.statistics import device_binary_rows
+        from deeprob.utils.statistics import device_training_rows
         if alpha < 0.0:
             raise ValueError("The Laplace smoothing factor must be non-negative")
         if min_n_samples < 0 or min_n_features < 1:
             raise ValueError("min_n_samples must be non-negative and min_n_features at least 1")
-        if len(data.shape) != 2 or data.shape[0] < 1 or data.shape[1] < 1:
-            raise ValueError("The data must be a matrix of samples by features")
-        if data.shape[1] > DPC_MAX_D:
-            raise ValueError("expected at most {} variables (DPC_MAX_D), got {}".format(DPC_MAX_D, data.shape[1]))
         random_state = check_random_state(random_state)
-        x = device_binary_rows(data)
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.to(torch.float32).contiguous()
+        x = device_training_rows(data)
         t_start, t_host = time.perf_counter(), 0.0
         n_rows, d = x.shape
         self.scope, self.children, self.weights, self.or_id, self.clt = list(range(d)), [], None, None, None
@@ -235,22 +228,8 @@ class BinaryCNet(ORNode):
 
     def _run(self, op, x, *args):
         """``op(tables on the device, x on the device, *args)`` under the input rules of the module docstring."""
-        import torch
-        from deeprob.hip import HipError, clt
-        clt.load_library()
-        as_numpy = not isinstance(x, torch.Tensor)
-        if as_numpy:
-            if not torch.cuda.is_available():
-                raise HipError("BinaryCNet needs a HIP device (there is no CPU fallback)")
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
-        elif not x.is_cuda:
-            raise HipError("x lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
-                           "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
-                           "device tensor".format(x.device))
-        if x.dim() != 2 or x.shape[1] != len(self.scope):
-            raise ValueError("expected inputs [B, {}], got {}".format(len(self.scope), tuple(x.shape)))
-        out = op(self._on_device(x.device), x, *args)
-        return out.cpu().numpy() if as_numpy else out
+        from deeprob.hip import clt
+        return clt.run_on_device(self, 'BinaryCNet', op, x, *args)
 
     def log_likelihood(self, x):
         """``[B]`` float32 log likelihoods; NaN entries are marginalised."""

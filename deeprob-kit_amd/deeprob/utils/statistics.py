@@ -43,6 +43,27 @@ def device_binary_rows(data):
     return x
 
 
+def device_training_rows(data):
+    """The training rows of a cutset-network learner (``BinaryCNet.fit``, ``learn_cnet_bd`` / ``learn_cnet_bic``,
+    ``select_cand_cuts``) as a contiguous float32 device tensor: :func:`device_binary_rows` of a matrix of at least one row and
+    1 .. ``DPC_MAX_D`` columns.  HipError for a CPU tensor, before anything else; ValueError for the rest."""
+    import torch
+    from deeprob.hip import HipError
+    from deeprob.hip.clt import DPC_MAX_D
+    if isinstance(data, torch.Tensor) and not data.is_cuda:
+        raise HipError("data lives on '{}': the deeprob HIP path only works on tensors on a HIP device (there is no CPU "
+                       "fallback) -- build the libraries with `make -C deeprob-kit_amd/csrc` and pass a numpy array or a "
+                       "device tensor".format(data.device))
+    if len(data.shape) != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+        raise ValueError("The data must be a matrix of samples by features")
+    if data.shape[1] > DPC_MAX_D:
+        raise ValueError("expected at most {} variables (DPC_MAX_D), got {}".format(DPC_MAX_D, data.shape[1]))
+    x = device_binary_rows(data)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    return x
+
+
 def pair_counts(data) -> Tuple[np.ndarray, int]:
     """``(ones [D, D] int64, N)`` of binary ``data`` ``[N, D]``: a numpy array (counted on the current HIP device) or a
     device tensor.  ValueError for NaN or values other than 0 / 1; HipError for a CPU tensor or a missing library."""

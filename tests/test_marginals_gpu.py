@@ -204,13 +204,17 @@ def deep_tables():
                 leaves=[([1, 2], [0, 1], [-1, 0], two), ([2], [0], [-1], half), ([2], [0], [-1], half)])
 
 
+def deep_rows():
+    nan = np.nan
+    return np.array([[nan, nan, nan], [1.0, nan, 0.0], [0.0, nan, 1.0], [1.0, 0.0, 1.0], [nan, 1.0, nan]], np.float32)
+
+
 def test_tables_deeper_than_levels_give_nan_rows_and_stay_inside_the_stack():
     from deeprob.hip import clt, cnet
     lib = clt.load_library()
     net = cnet.DeviceCNet(device=here(), **deep_tables())
     assert net.levels == 3 and net.covered
-    nan = np.nan
-    x = np.array([[nan, nan, nan], [1.0, nan, 0.0], [0.0, nan, 1.0], [1.0, 0.0, 1.0], [nan, 1.0, nan]], np.float32)
+    x = deep_rows()
     want = run(cnet.marginals, net, x)
     assert np.abs(want - [[.5, .5, .5], [1, .5, 0], [0, .5, 1], [1, 0, 1], [.5, 1, .5]]).max() <= 1e-6
     xd = device(x)
@@ -232,6 +236,56 @@ def test_tables_deeper_than_levels_give_nan_rows_and_stay_inside_the_stack():
             # levels = 2 still holds the path root -> node 1 (x0 = 0); everything else needs the third level
             fits = np.array([False, False, levels == 2, True, False])
             assert np.isnan(out[~fits][np.isnan(x[~fits])]).all()
+            assert same_bits(out[fits], want[fits])
+
+
+@pytest.mark.parametrize('entry', ['dpc_cnet_log_likelihood', 'dpc_cnq_mpe', 'dpc_cnq_sample'])
+def test_the_other_network_queries_keep_the_same_guard(entry):
+    """The walk is one piece of code (or_walk, clt_common.h) and its guard must hold at every entry point that runs it:
+    with ``work`` sized for the declared ``levels`` only, a row whose walk needs a deeper stack is answered with NaN (the
+    fills: the whole row, observed entries included, and ``choice`` = -1), every other row with the bits of the
+    full-``levels`` answer, and nothing is written outside the buffers.  The likelihood answers the complete row 3 at any
+    ``levels`` (its stack-free path); the fills send it through the stack."""
+    from deeprob.hip import clt, cnet
+    lib = clt.load_library()
+    net = cnet.DeviceCNet(device=here(), **deep_tables())
+    x = deep_rows()
+    xd = device(x)
+    b, fill, seed = len(x), entry != 'dpc_cnet_log_likelihood', 12345
+    if entry == 'dpc_cnet_log_likelihood':
+        want, want_choice = cnet.log_likelihood(net, xd).cpu().numpy(), None
+    elif entry == 'dpc_cnq_mpe':
+        want, want_choice = (t.cpu().numpy() for t in cnet.mpe(net, xd, return_choice=True))
+    else:
+        want, want_choice = (t.cpu().numpy() for t in cnet.sample(net, xd, seed, return_choice=True))
+    assert np.isfinite(want).all()
+    for levels in (2, 1):
+        for pattern in PATTERNS:
+            with contract(pattern) as c:
+                c.frozen(xd, net._buf)
+                codes = clt.pack_query(xd)
+                work = torch.empty(b * ((16 if fill else 12) * levels + 8 * net.max_leaf_d), dtype=torch.uint8, device=xd.device)
+                out = torch.empty((b, 3) if fill else b, dtype=torch.float32, device=xd.device)
+                choice = torch.empty(b, dtype=torch.int32, device=xd.device) if fill else None
+                tables = (net.leaf_meta.data_ptr(), net.leaf_ints.data_ptr(), net.leaf_params.data_ptr(), levels, net.max_leaf_d)
+                if not fill:
+                    clt.call(lib.dpc_cnet_log_likelihood, codes.data_ptr(), b, 3, net.n_nodes, net.node_col.data_ptr(),
+                             net.node_child.data_ptr(), net.node_logw.data_ptr(), *tables, work.data_ptr(), out.data_ptr(), None)
+                else:
+                    head = (xd.data_ptr(), codes.data_ptr(), b, 3, net.n_nodes, net.node_col.data_ptr(),
+                            net.node_child.data_ptr(), net.node_parent.data_ptr(), net.node_logw.data_ptr()) + tables
+                    tail = (work.data_ptr(), out.data_ptr(), choice.data_ptr(), None)
+                    clt.call(getattr(lib, entry), *head, *((seed, 0) if entry == 'dpc_cnq_sample' else ()), *tail)
+                c.expect_written(out)       # (not `choice`: its -1 is the bytes of the poison 0xFF)
+            out = out.cpu().numpy()
+            if fill:
+                # levels = 2 still holds the path root -> node 1 (x0 = 0); the complete row 3 goes through node 2
+                fits = np.array([False, False, levels == 2, False, False])
+                choice = choice.cpu().numpy()
+                assert (choice[~fits] == -1).all() and np.array_equal(choice[fits], want_choice[fits])
+            else:
+                fits = np.array([False, False, levels == 2, True, False])
+            assert np.isnan(out[~fits]).all()
             assert same_bits(out[fits], want[fits])
 
 
