@@ -62,11 +62,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kWide = 64;            // a node of more inputs than this is scanned by a wave
 
-struct Level {
-    int cin, hin, win, cout, hout, wout, pl, pt, stride, dil, dw;
-    int cin2, cin3;                  // Cin^2, Cin^3 (channel decode of a level that is not depthwise)
-};
-
 struct TopDownArgs {
     int64_t B;
     int C, H, W, K, L, classes, cap;
@@ -81,26 +76,6 @@ struct TopDownArgs {
     float *out;
     int *choice;
 };
-
-__device__ __forceinline__ int tap_channel(const Level &g, int oc, int t) {
-    if (g.dw) return oc;
-    const int q = t == 0 ? oc / g.cin3 : t == 1 ? oc / g.cin2 : t == 2 ? oc / g.cin : oc;
-    return q % g.cin;
-}
-
-// fp32 value of product (oc, oh, ow) of level g over the sample's input map A [Cin, Hin, Win]: ((v0 + v1) + v2) + v3
-__device__ __forceinline__ float prod_value(const Level &g, const float *A, int oc, int oh, int ow) {
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ih = oh * g.stride + (t >> 1) * g.dil - g.pt, iw = ow * g.stride + (t & 1) * g.dil - g.pl;
-        float v = 0.f;
-        if ((unsigned)ih < (unsigned)g.hin && (unsigned)iw < (unsigned)g.win)
-            v = A[((int64_t)tap_channel(g, oc, t) * g.hin + ih) * g.win + iw];
-        s = t == 0 ? v : s + v;
-    }
-    return s;
-}
 
 // the taps of product (oc, oh, ow) inside the input map join the list of the level below
 __device__ __forceinline__ void activate(const Level &g, int oc, int oh, int ow, int *list, int *count, int cap) {
@@ -268,48 +243,16 @@ extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H,
                                   uint64_t seed, float *out, int32_t *choice, void *stream) {
     DPG_REQUIRE(mode == DPG_MODE_PRIOR || mode == DPG_MODE_POSTERIOR, "dpg_dgcspn_topdown: mode %d", mode);
     DPG_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && K > 0 && classes > 0, "dpg_dgcspn_topdown: bad sizes");
-    DPG_REQUIRE(n_levels >= 1 && n_levels <= DPG_MAX_LEVELS, "dpg_dgcspn_topdown: %d levels are outside 1..%d", n_levels,
-                DPG_MAX_LEVELS);
-    DPG_REQUIRE(geom != nullptr && logw != nullptr, "dpg_dgcspn_topdown: null table");
+    DPG_REQUIRE(logw != nullptr, "dpg_dgcspn_topdown: null table");
     DPG_REQUIRE((int64_t)C * H * W <= (1 << 28), "dpg_dgcspn_topdown: an image of more than 2^28 entries");
     TopDownArgs a{};
     a.B = B; a.C = C; a.H = H; a.W = W; a.K = K; a.L = n_levels; a.classes = classes;
     a.x = mode == DPG_MODE_POSTERIOR ? x : nullptr;
     a.y = y; a.loc = loc; a.scale = scale; a.seed = seed; a.out = out; a.choice = choice;
+    if (int rc = parse_geometry("dpg_dgcspn_topdown", n_levels, geom, K, H, W, a.lv)) return rc;
     int64_t cap = 4, slots = 1;
     for (int j = 0; j < n_levels; ++j) {
-        const int32_t *r = geom + (size_t)j * DPG_GEOM_INTS;
-        Level &g = a.lv[j];
-        g.cin = r[0]; g.hin = r[1]; g.win = r[2]; g.cout = r[3]; g.hout = r[4]; g.wout = r[5];
-        g.pl = r[6]; g.pt = r[8]; g.stride = r[10]; g.dil = r[11]; g.dw = r[12] != 0;
-        DPG_REQUIRE(g.cin >= 1 && g.cin <= 32767 && g.hin >= 1 && g.win >= 1 && (int64_t)g.hin * g.win <= 65535 &&
-                        g.hout >= 1 && g.wout >= 1 && (int64_t)g.hout * g.wout <= 65535 && g.stride >= 1 && g.stride <= 65535 && g.dil >= 1 &&
-                        g.dil <= 65535,
-                    "dpg_dgcspn_topdown: level %d: sizes out of domain", j);
-        // (with these bounds out * stride + dilation - pad stays far inside int)
-        for (int q = 6; q < 10; ++q)
-            DPG_REQUIRE(r[q] >= -65535 && r[q] <= 65535, "dpg_dgcspn_topdown: level %d: pad %d out of domain", j, r[q]);
-        // (the pads after a map shape its output only; they are checked through the output shape)
-        const int64_t eff = (int64_t)g.dil + 1;
-        const int64_t span_h = (int64_t)r[8] + r[9] + g.hin - eff + 1, span_w = (int64_t)r[6] + r[7] + g.win - eff + 1;
-        DPG_REQUIRE(span_h >= 1 && span_w >= 1 && g.hout == (span_h + g.stride - 1) / g.stride &&
-                        g.wout == (span_w + g.stride - 1) / g.stride,
-                    "dpg_dgcspn_topdown: level %d: the output shape does not follow from pads, stride and dilation", j);
-        if (g.dw) {
-            DPG_REQUIRE(g.cout == g.cin, "dpg_dgcspn_topdown: level %d: depthwise with %d -> %d channels", j, g.cin, g.cout);
-        } else {
-            const int64_t c2 = (int64_t)g.cin * g.cin, c4 = c2 * c2;
-            DPG_REQUIRE(g.cin <= 181 && g.cout == c4, "dpg_dgcspn_topdown: level %d: %d channels do not give %d = Cin^4", j,
-                        g.cin, g.cout);
-            g.cin2 = (int)c2;
-            g.cin3 = (int)(c2 * g.cin);
-        }
-        DPG_REQUIRE((int64_t)g.cout * g.hout * g.wout <= 0x7fffffff, "dpg_dgcspn_topdown: level %d: map too large", j);
-        if (j == 0)
-            DPG_REQUIRE(g.cin == K && g.hin == H && g.win == W, "dpg_dgcspn_topdown: level 0 does not read the leaf map");
-        else
-            DPG_REQUIRE(g.hin == a.lv[j - 1].hout && g.win == a.lv[j - 1].wout,
-                        "dpg_dgcspn_topdown: level %d does not read the map of level %d", j, j - 1);
+        const Level &g = a.lv[j];
         // entries of list j: at most the positions of the map, at most 4 per active node above
         const int64_t above = std::min<int64_t>((int64_t)1 << (2 * std::min(n_levels - j, 8)), 65536);
         cap = std::max<int64_t>(cap, std::min<int64_t>((int64_t)g.hin * g.win, above));

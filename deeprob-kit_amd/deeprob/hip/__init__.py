@@ -12,8 +12,8 @@ import torch
 from deeprob.hip._binding import Binding, HipError, bound_module, parse_header  # noqa: F401  (re-exported)
 
 # ---- the native libraries: one Binding per header, one shared object per exported prefix ----------------------------
-# Each module of this package (learn, clt, dgc, spnq, rat, slice) takes its binding from here and adds its operators;
-# BINDINGS is what __graft_entry__.build() checks and what the export test runs over.  A new library is one line here.
+# Each module of this package (learn, clt, dgc, dgcm, spnq, rat, slice) takes its binding from here and adds its operators;
+# ALL_BINDINGS is what __graft_entry__.build() checks, BINDINGS what the export test runs over.  A new library is one line here.
 MAIN = Binding('hip', 'dpk', env='DEEPROB_HIP_LIB')      # DEEPROB_HIP_LIB: measurement builds (profiles/README)
 SLICE = Binding('slice', 'dps', onto=MAIN)               # host-side knobs of a kernel that lives in libdeeprob_hip.so
 LEARN = Binding('learn', 'dpl')
@@ -24,6 +24,10 @@ DGC = Binding('dgc', 'dpg')
 SPNQ = Binding('spnq', 'dpq')
 RAT = Binding('rat', 'dpr', not_implemented='DPR_EUNSUPPORTED')
 BINDINGS = (MAIN, SLICE, LEARN, CLT, DGC, SPNQ, RAT)
+# further headers bound onto a library above: entry points added beside a header whose list is pinned
+DGCM = Binding('dgcm', 'dpm', onto=DGC)                  # DgcSpn.posterior_moments, in libdeeprob_dgc.so
+EXTENSIONS = (DGCM,)
+ALL_BINDINGS = BINDINGS + EXTENSIONS
 
 # name -> (restype, argtypes) of every dpk_ entry point; DPK_OK, DPK_E*, DPK_FLAG_*, DPK_KERNEL_* as module-level names
 SIGNATURES, CONSTANTS = MAIN.signatures, MAIN.constants

@@ -304,6 +304,44 @@ class DgcSpn(ProbabilisticModel):
                                   self._topdown_logw(), self.base_layer.loc, self.base_layer.scale,
                                   ops.draw_seed() if seed is None else int(seed), labels_trusted=drawn)
 
+    @torch.no_grad()
+    def posterior_moments(self, x: torch.Tensor, y: Optional[torch.Tensor] = None,
+                          want_var: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """Exact ``(E[x | e, y], Var[x | e, y])`` of every NaN entry of ``x [B,C,H,W]`` given the image's observed entries
+        ``e`` (and the class ``y``, when given): the bottom-up pass of ``sample_conditional``, then one top-down launch that
+        sends the posterior flow of every sum node to all of its inputs (csrc/dgc/dgcspn_moments.hip) and mixes the leaf
+        components' moments by the flow they receive.  An observed entry comes back as it is, with variance 0.  Without
+        labels a model with several classes answers for the mixture of its classes under the uniform class prior (class
+        ``c`` weighted by ``softmax(root outputs)[c]``); a model with one root ignores ``y``; a label outside
+        ``[0, out_classes)`` raises ``ValueError``.  A NaN entry of a pixel outside every scope stays NaN in both outputs,
+        as ``sample_conditional`` returns such a pixel as given.  ``mpe`` is the reference's gradient form of the mean:
+        autograd through every layer, and no variance."""
+        from deeprob.hip import Workspace, dgcm, ops
+        self._check_topdown('posterior_moments')
+        x = ops.require_device_f32(x, 'x')
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.in_features):
+            raise ValueError("expected inputs [B, {}], got {}".format(tuple(self.in_features), tuple(x.shape)))
+        acts = self._upward_for_sampling(x)
+        if self.out_classes == 1:
+            y = None
+        if getattr(self, '_moments_ws', None) is None:
+            self._moments_ws = Workspace()                      # the flow maps of the launch's work-groups
+        geom = dgcm.product_geometry(self._product_layers())
+        mean, var, _ = dgcm.dgcspn_moments(self.in_features, geom, self.out_classes, x, y, acts, self._topdown_logw(),
+                                           self.base_layer.loc, self.base_layer.scale, self._moments_ws,
+                                           all_classes=y is None, want_var=want_var)
+        return mean, var
+
+    def expectation(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``E[x_missing | x_observed, y]`` in the NaN entries of ``x``, the observed entries as they are: mean imputation,
+        the completion of least expected squared error.  See :meth:`posterior_moments`."""
+        return self.posterior_moments(x, y, want_var=False)[0]
+
+    def variance(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``Var[x_missing | x_observed, y]`` in the NaN entries of ``x``, 0 in the observed ones: the per-pixel uncertainty
+        of the imputation.  See :meth:`posterior_moments`."""
+        return self.posterior_moments(x, y)[1]
+
     def loss(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self.out_classes == 1:
             from deeprob.hip import ops
