@@ -694,8 +694,10 @@ int dpk_conv2d_forward(const float *in, int64_t in_bstride, int64_t B, int32_t C
         q.G = (int)std::max<int64_t>(1, std::min<int64_t>(kLdsPix / (H * W), 2048 / q.plane));
         q.G = (int)std::min<int64_t>(q.G, B);
         q.NP = q.G * H * W;
-        if ((int64_t)q.G * in_bstride < INT32_MAX) {
-            const size_t lds_bytes = (size_t)2 * kLdsCC * q.G * q.plane * sizeof(float);
+        // (a thin image -- 2x512, 1x681 -- has a padded plane above 2048 floats: G is clamped up to 1 and the two buffers
+        // would exceed the 64 KB of LDS a kernel gets unasked; such images take the routes below)
+        const size_t lds_bytes = (size_t)2 * kLdsCC * q.G * q.plane * sizeof(float);
+        if ((int64_t)q.G * in_bstride < INT32_MAX && lds_bytes <= 64 * 1024) {
             const float *wfrag = wpack + conv_valu_floats(Cout, Cin, ks);
             const dim3 lgrid((unsigned)cdiv(B, q.G), (unsigned)cdiv(Cout, 32));
             const int ntile = cdiv((int64_t)q.NP, 32);
