@@ -149,6 +149,39 @@ def partition_rows(row_index, src_off, src_n, label_off, label, dst_off, dst_n, 
     return out
 
 
+def pair_ones(data: DeviceData, row_index, blocks, row_chunk: int = None):
+    """The co-occurrence counts of every block (``dpl_pair_ones``): ``blocks`` is a list of ``(row_off, n, cols)``, one
+    leaf task each.  Returns ``(ones, out_off)``: a device int32 tensor with block t's ``[m, m]`` counts, row major, at
+    ``ones[out_off[t] : out_off[t] + m * m]``.  One table upload and one call (a zeroing launch and the counting launch);
+    ``row_chunk``: the rows of one unit, ``DPL_PAIR_ROW_CHUNK`` when None."""
+    assert not data.is_float and data.x.dtype == torch.uint8
+    tile = CONSTANTS['DPL_PAIR_TILE']
+    row_chunk = int(CONSTANTS['DPL_PAIR_ROW_CHUNK'] if row_chunk is None else row_chunk)
+    ms = [len(cols) for _, _, cols in blocks]
+    assert blocks and min(ms) >= 1 and min(int(n) for _, n, _ in blocks) >= 1 and row_chunk >= 1
+    col_off = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum([m * m for m in ms])]).astype(np.int64)
+    unit = {key: [] for key in ('blk', 'ti', 'tj', 'row0')}
+    for b, ((_, n, _), m) in enumerate(zip(blocks, ms)):
+        tiles = -(-m // tile)
+        for ti in range(tiles):
+            for tj in range(ti, tiles):
+                for row0 in range(0, int(n), row_chunk):
+                    for key, v in zip(('blk', 'ti', 'tj', 'row0'), (b, ti, tj, row0)):
+                        unit[key].append(v)
+    t = upload(data.device, col=np.concatenate([np.asarray(cols, np.int32).reshape(-1) for _, _, cols in blocks]),
+               col_off=col_off[:-1].copy(), m=np.asarray(ms, np.int32), row_off=np.asarray([b[0] for b in blocks], np.int64),
+               n=np.asarray([b[1] for b in blocks], np.int32), out_off=out_off[:-1].copy(),
+               **{'unit_' + key: np.asarray(v, np.int32) for key, v in unit.items()})
+    ones = torch.empty(int(out_off[-1]), dtype=torch.int32, device=data.device)
+    call(load_library().dpl_pair_ones, *data.head(row_index), t['col'].data_ptr(), t['col_off'].data_ptr(), t['m'].data_ptr(),
+         t['row_off'].data_ptr(), t['n'].data_ptr(), t['out_off'].data_ptr(), len(blocks), t['unit_blk'].data_ptr(),
+         t['unit_ti'].data_ptr(), t['unit_tj'].data_ptr(), t['unit_row0'].data_ptr(), len(unit['blk']), row_chunk,
+         ones.data_ptr(), ones.numel(), _stream(data.device))
+    COUNTERS['kernels'] += 2        # (the zeroing kernel and the counting kernel)
+    return ones, out_off[:-1]
+
+
 class KMeansBatch:
     """The k-means of all row-splitting tasks of one generation (header: "k-means", "k-means on float columns").
     ``tasks``: a list of ``(row_off, n, cols, ks, seeds)`` with ``seeds`` an ``[n_restarts, n_clusters]`` array of row

@@ -5,7 +5,8 @@ The reference pops one task at a time from a FIFO queue.  The queue is breadth f
 (one depth of the task tree, a retry counting as a child) are consecutive in it and their children follow in the same
 order; a generation is processed here as a whole: column statistics of all its tasks in one launch, the operations decided
 from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the
-statistics of all column-splitting tasks, the k-means of all row-splitting tasks together, and one partition launch that
+statistics of all column-splitting tasks, the co-occurrence counts of all Chow-Liu leaf tasks (``learn_leaf`` the function
+``leaf.learn_binary_clt``), the k-means of all row-splitting tasks together, and one partition launch that
 writes the next generation's row-index array.  The loop is written once; what depends on the kind of the columns --
 discrete (:class:`DiscreteColumns`, below) or Gaussian (``learnspn_cont.GaussianColumns``) -- is asked of a column-kind
 object.  See DESIGN.md, "LearnSPN on the device".
@@ -18,6 +19,7 @@ import torch
 
 from deeprob.hip import HipError, learn as L
 from deeprob.spn.learning.splitting import rdc as R
+from deeprob.spn.learning.leaf import learn_binary_clt, BERNOULLI_MESSAGE
 from deeprob.spn.structure.leaf import LeafType, Bernoulli, Categorical
 
 #: what ``get_learn_leaf_method`` / ``get_split_rows_method`` / ``get_split_cols_method`` of the reference know
@@ -29,6 +31,9 @@ BUILT_COLS = ('gvs', 'rgvs', 'random')
 KMEANS_RESTARTS = 5
 #: launches + host reads + uploads per generation, outside the Lloyd loop
 LAUNCHES_PER_GENERATION = 14
+#: what ``learn_leaf=learn_binary_clt`` adds to it: the table upload of ``pair_ones``, its zeroing and its counting kernel
+#: and the read of the counts ("Chow-Liu tree leaves in learn_spn")
+CLT_LAUNCHES_PER_GENERATION = 4
 
 _last_info = {}
 
@@ -37,7 +42,10 @@ def last_info() -> dict:
     """What the last ``learn_spn`` recorded: ``generations``, ``tasks_per_generation``, ``kernels`` (launches of the learn
     library outside the Lloyd loop; ``torch.sort`` and the gathers in front of it are not counted), ``reads``, ``uploads``,
     ``launches`` (the sum of the three), ``lloyd_launches`` and ``lloyd_iterations``; on discrete data also
-    ``launches_per_generation``, the bound DESIGN.md derives for ``launches`` there."""
+    ``launches_per_generation``, the bound DESIGN.md derives for ``launches`` there (``LAUNCHES_PER_GENERATION``, plus
+    ``CLT_LAUNCHES_PER_GENERATION`` with Chow-Liu leaves); and ``clt_leaves``: one record per Chow-Liu leaf in queue order,
+    with its ``scope``, ``root`` (a variable), ``tree``, ``params``, ``n`` and ``rows`` -- the leaf's slice of its
+    generation's row-index array, a device tensor (a view: nothing is read for it; it lives until the next ``learn_spn``)."""
     return dict(_last_info)
 
 
@@ -105,12 +113,20 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
     n_samples, n_features = data.shape
     if len(distributions) != n_features or len(domains) != n_features:
         raise ValueError("Each data column should correspond to a random variable having a distribution and a domain")
-    _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
+    clt = learn_leaf is learn_binary_clt      # (this package's own function, by identity; the string 'binary-clt' is not built)
+    if not clt:
+        _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
+    elif any(d is not Bernoulli for d in distributions):
+        raise ValueError(BERNOULLI_MESSAGE)                                               # leaf.py:138-139
     _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
     rdc = split_cols is R.rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
     if not rdc:
         kind.check_split_cols(split_cols)
-    leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
+    if clt:
+        leaf_kw = _kwargs(learn_leaf_kwargs, {'to_pc': False, 'alpha': 0.1, 'random_state': None}, 'learn_binary_clt')
+        check_random_state(leaf_kw['random_state'])             # (the type; a RandomState is returned as it is, untouched)
+    else:
+        leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
     rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
     if rdc:
         cols_kw = _kwargs(split_cols_kwargs, {'d': R.D_DEFAULT, 'k': R.K_DEFAULT, 's': R.S_DEFAULT}, 'rdc_cols')
@@ -329,12 +345,27 @@ class DiscreteColumns:
         return L.KMeansBatch(self.data, row_index, [(t.row_off, t.n, t.scope, [self.ks[s] for s in t.scope], t.draw) for t in tasks],
                              KMEANS_RESTARTS, n_clusters, self.kmax)
 
+    def clt_leaves(self, row_index, tasks, alpha):
+        """The Chow-Liu leaf of every task (learning/leaf.py:149-150; ``t.draw`` is the position of its root): the
+        co-occurrence counts of all of them from one launch and one read, then per task the host half of
+        ``BinaryCLT.fit``.  Returns the fitted trees, in the order of the tasks."""
+        from deeprob.spn.structure.cltree import BinaryCLT
+        ones, out_off = L.pair_ones(self.data, row_index, [(t.row_off, t.n, t.scope) for t in tasks])
+        ones = L.read(ones)
+        leaves = []
+        for t, off in zip(tasks, out_off):
+            m = len(t.scope)
+            leaf = BinaryCLT(t.scope, root=t.scope[t.draw])
+            leaf.fit_counts(ones[off:off + m * m].reshape(m, m).astype(np.int64), t.n, alpha=alpha)
+            leaves.append(leaf)
+        return leaves
+
 
 def learn_spn(
     data,
     distributions: list,
     domains: List[Union[list, tuple]],
-    learn_leaf: str = 'mle',
+    learn_leaf='mle',
     split_rows: str = 'kmeans',
     split_cols: str = 'rdc',
     learn_leaf_kwargs: dict = None,
@@ -350,7 +381,9 @@ def learn_spn(
     (reference learnspn.py:41-222), on the HIP device.
 
     Built: discrete data with ``Bernoulli`` (domain ``[0, 1]``) and ``Categorical`` leaves, every domain
-    ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``; ``split_rows`` in ``'kmeans'``, ``'random'``;
+    ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``, or the function
+    ``deeprob.spn.learning.leaf.learn_binary_clt`` itself (recognised by identity; all-``Bernoulli`` data): Chow-Liu tree
+    leaves, see below; ``split_rows`` in ``'kmeans'``, ``'random'``;
     ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``, or the function
     ``deeprob.spn.learning.splitting.rdc.rdc_cols`` itself (recognised by identity): the RDC split as the exact maximal
     correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``.  Also built: all-continuous data, every distribution
@@ -362,13 +395,27 @@ def learn_spn(
     ``split_cols=rdc_cols`` or ``split_cols='gvs'``.  ``'kmeans'`` is this project's own k-means, not
     scikit-learn's: the same kind of split, not the same labels.
 
+    Chow-Liu tree leaves (``learn_leaf=learn_binary_clt``, ``learn_leaf_kwargs`` in ``to_pc``, ``alpha``, ``random_state``):
+    a leaf task with more than one column becomes a ``BinaryCLT`` fitted to the task's rows -- the co-occurrence counts of
+    all such tasks of a generation come from one launch (``dpl_pair_ones``) --; one-column leaves and the factorisations of
+    constant columns stay MLE leaves, as in the reference.  ``FlatSpn`` has no multivariate leaf, so the circuit always
+    holds the tree's ``to_pc`` expansion: ``to_pc`` is accepted and both values give the same ``FlatSpn``, whose likelihood,
+    MPE and sampling distribution are those of the leaf; ``expectation_maximization`` on the result updates the expansion's
+    sum weights freely, not as the tied CPTs of a tree.  The root of each tree is
+    ``check_random_state(learn_leaf_kwargs['random_state']).choice(len(scope))``, evaluated per leaf in queue order among
+    the other draws: an int re-seeds for every leaf, a ``RandomState`` is consumed in queue order and may be the very
+    object passed as ``random_state`` (which is what the reference does with whatever is passed: its ``learn_spn``
+    overwrites the key with its own generator, learnspn.py:112), None is a fresh unseeded generator per leaf.  The STRING
+    ``'binary-clt'``, a wrapper around the function and a non-``Bernoulli`` distribution (``ValueError``) raise before any
+    device work.
+
     :param data: The training data: a numpy array or a tensor on a HIP device, complete (no NaN).
     :param distributions: A list of distribution classes of ``deeprob.spn.structure.leaf`` (one for each feature).
     :param domains: A list of domains (one for each feature), each ``list(range(K))`` (``(lo, hi)`` for ``Gaussian``).
-    :param learn_leaf: The method to use to learn a distribution leaf node: 'mle'.
+    :param learn_leaf: The method to use to learn a distribution leaf node: 'mle' or the function ``learn_binary_clt``.
     :param split_rows: The rows splitting method: 'kmeans' or 'random'.
     :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random' or the function ``rdc_cols``.
-    :param learn_leaf_kwargs: The parameters of the learn leaf method (``alpha``).
+    :param learn_leaf_kwargs: The parameters of the learn leaf method (``alpha`` | ``to_pc``, ``alpha``, ``random_state``).
     :param split_rows_kwargs: The parameters of the rows splitting method (``n`` | ``a``, ``b``).
     :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b`` | ``d``, ``k``, ``s``).
     :param min_rows_slice: The minimum number of samples required to split horizontally.
@@ -391,6 +438,7 @@ def learn_spn(
     random_state = check_random_state(random_state)
     if split_cols is R.rdc_cols:
         split_cols = 'rdc'
+    clt = learn_leaf is learn_binary_clt
     dev_data = kind.upload(data)
     device = dev_data.device
     n_total, n_features = dev_data.n_rows, dev_data.n_cols
@@ -400,7 +448,7 @@ def learn_spn(
 
     tmp_node = new_node('Product', range(n_features))
     generation = [_Task(tmp_node, n_total, list(range(n_features)), is_first=True)]
-    tasks_per_generation, lloyd_iterations = [], 0
+    tasks_per_generation, lloyd_iterations, clt_records = [], 0, []
     while generation:
         tasks_per_generation.append(len(generation))
         # ---- column statistics of every task, the operation of every task (learnspn.py:130-147) ----------------------
@@ -435,9 +483,20 @@ def learn_spn(
                 t.draw = random_state.binomial(1, p, size=len(t.scope))
             elif t.op == 'cols':
                 t.draw = kind.draw_split_cols(random_state, t, split_cols, cols_kw)
+            elif t.op == 'leaf' and clt and len(t.scope) > 1:
+                # the root of the tree, drawn where the reference's leaf function draws it (cltree.py:185-189)
+                t.draw = int(check_random_state(leaf_kw['random_state']).choice(len(t.scope)))
         # ---- the column clusters of every column-splitting task that is not 'random' ---------------------------------
         tested = [t for t in generation if t.op == 'cols' and split_cols != 'random']
         clusters_of = {id(t): c for t, c in zip(tested, kind.split_cols_clusters(row_index, tested, split_cols, cols_kw))}
+        # ---- the Chow-Liu trees of every multivariate leaf task -------------------------------------------------------
+        clt_tasks = [t for t in generation if t.op == 'leaf' and clt and len(t.scope) > 1]
+        clt_of = {}
+        if clt_tasks:
+            for t, leaf in zip(clt_tasks, kind.clt_leaves(row_index, clt_tasks, alpha)):
+                clt_of[id(t)] = leaf
+                clt_records.append({'scope': list(t.scope), 'root': leaf.scope[leaf.root], 'tree': leaf.tree, 'params': leaf.params,
+                                    'n': t.n, 'rows': row_index[t.row_off:t.row_off + t.n]})
         # ---- k-means of every row-splitting task ----------------------------------------------------------------------
         km_tasks = [t for t in generation if t.op == 'rows' and split_rows == 'kmeans']
         km_labels, km_result = None, {}
@@ -465,6 +524,8 @@ def learn_spn(
                                                             alpha))
                 child(_Task(node, t.n, [scope[i] for i in range(nf) if not zero_var[i]], is_first=t.is_first), t)
                 t.parent['children'].append(node)
+            elif id(t) in clt_of:
+                t.parent['children'].append(clt_of[id(t)].to_pc_nodes())      # (FlatSpn has no multivariate leaf)
             elif t.op == 'leaf' and nf == 1:
                 t.parent['children'].append(kind.leaf(scope[0], t.counts[0], t.n, alpha))
             elif t.op in ('leaf', 'naive'):
@@ -514,7 +575,7 @@ def learn_spn(
     _last_info.update(generations=len(tasks_per_generation), launches=c['kernels'] + c['reads'] + c['uploads'],
                       kernels=c['kernels'], reads=c['reads'], uploads=c['uploads'],
                       lloyd_launches=c['lloyd_kernels'] + c['lloyd_reads'], lloyd_iterations=lloyd_iterations,
-                      tasks_per_generation=tasks_per_generation)
+                      tasks_per_generation=tasks_per_generation, clt_leaves=clt_records)
     if kind.launches_per_generation is not None:
-        _last_info['launches_per_generation'] = kind.launches_per_generation
+        _last_info['launches_per_generation'] = kind.launches_per_generation + (CLT_LAUNCHES_PER_GENERATION if clt else 0)
     return to_flat(tmp_node['children'][0])

@@ -13,8 +13,11 @@ Two deliberate differences from the reference, both documented in DESIGN.md ("Ch
 it only fixes the order of float32 additions.  ``sample`` draws from a counter-based generator with an explicit ``seed``
 (the reference uses scipy's global generator and cannot be replayed).
 
-The class is not a leaf of node-graph SPNs here (``learn_spn(learn_leaf='binary-clt')`` raises), so the reference's
-``em_init`` / ``em_step`` are not built.
+``FlatSpn`` has no multivariate leaf, so the class is never a node of a node-graph SPN here: ``learn_spn`` with
+``learn_leaf=deeprob.spn.learning.leaf.learn_binary_clt`` (the function, by identity; the string ``'binary-clt'`` still
+raises) fits one tree per multivariate leaf task from counts taken on the learner's own data layout (``fit_counts``) and
+hangs its ``to_pc_nodes()`` expansion into the circuit.  The reference's ``em_init`` / ``em_step`` (tied CPTs) are not
+built: EM on such a circuit updates the expansion's sum weights freely.
 """
 from typing import List, Optional, Union
 

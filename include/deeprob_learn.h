@@ -29,7 +29,8 @@
  *   4. it leaves its `const` inputs alone.
  * There is no workspace.  Index arrays handed in are trusted to lie inside the arrays they index,
  * a value x >= the K stated for its column is not counted.  Counts are exact integers (LDS integer
- * atomics); no floating-point value is accumulated atomically, every float64 sum has a fixed order.
+ * atomics; global ones in dpl_pair_ones, onto an output the entry zeroes itself); no floating-point
+ * value is accumulated atomically, every float64 sum has a fixed order.
  *
  * The return value is 0 on success and a negative DPL_E* code otherwise; dpl_last_error() returns
  * a thread-local message for the last failure.
@@ -154,6 +155,30 @@ int dpl_kmeans_inertia(const uint8_t *x, int64_t n_rows, int n_cols, const int32
                        const int64_t *task_lab_off, int n_tasks, int n_restarts, int n_clusters, int kmax,
                        const double *cent, const uint8_t *labels, int64_t n_lab, double *inertia, int32_t *sizes,
                        void *stream);
+
+/* ---- Chow-Liu tree leaves (learning/leaf.py:149-150: the counts behind BinaryCLT.fit) -------------
+ * Co-occurrence counts of binary columns.  BLOCK t -- a leaf task -- has the rows row_index[blk_row_off[t]
+ * .. + blk_n[t]) and the m = blk_m[t] columns blk_col[blk_col_off[t] .. + m), in any order; columns may
+ * recur in other blocks.  ones[blk_out_off[t] + i * m + j] = number of rows of the segment with
+ * x[col_i][row] == 1 and x[col_j][row] == 1: exact int32, symmetric, the diagonal holds the column
+ * counts.  The caller lays the blocks' m * m outputs out so that they tile [0, n_ones).
+ * A UNIT is the work of one work-group: block unit_blk[u], the pair of 64-column tiles unit_ti[u] <=
+ * unit_tj[u] of that block's columns (tile k holds the column positions [64 k, 64 k + 64)), and the rows
+ * [unit_row0[u], + row_chunk) of its segment, clipped to blk_n.  The caller lists, for every block,
+ * every tile pair ti <= tj over every row chunk row0 = 0, row_chunk, 2 row_chunk, ... < blk_n; units of
+ * one block add into the same elements by integer atomics (the order of integer additions is free), so
+ * the entry first sets all of `ones` to zero with a kernel of its own: every element is written for
+ * every shape, and nothing depends on what `ones` held.  The bit planes of a pass (64 columns x 1024
+ * rows, two tiles) live in LDS only; a block of any width is tiled, none is refused.  The number of
+ * work-groups is the number of units: the row and pair work, whatever the number of blocks.
+ * ones: [n_ones] int32. */
+#define DPL_PAIR_TILE 64
+#define DPL_PAIR_ROW_CHUNK 8192 /* the row chunk the package passes */
+int dpl_pair_ones(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                  const int32_t *blk_col, const int64_t *blk_col_off, const int32_t *blk_m, const int64_t *blk_row_off,
+                  const int32_t *blk_n, const int64_t *blk_out_off, int64_t n_blocks, const int32_t *unit_blk,
+                  const int32_t *unit_ti, const int32_t *unit_tj, const int32_t *unit_row0, int64_t n_units, int row_chunk,
+                  int32_t *ones, int64_t n_ones, void *stream);
 
 /* ==== continuous data (deeprob.spn.learning.learnspn_cont: all-Gaussian learn_spn) =================
  * `xf` is the training set as float32, COLUMN MAJOR: xf[col * n_rows + row]; `row_index`, segments and
