@@ -3,8 +3,9 @@
 // restatement in the same order reproduces them up to the rounding of expf / log1pf.
 //
 // Layout of the work.  Learning: the data become bit planes (one 64 x 64 tile of x per work-group, transposed through
-// LDS, a ballot per column), then work-groups tile the (i, j) pairs 32 x 32, stage 32 words of each plane in LDS and add
-// popcounts in registers; only tiles on or above the diagonal are computed, each writes its mirror image too.  Queries:
+// LDS, a ballot per column: pack_tile of clt_common.h), then work-groups tile the (i, j) pairs 32 x 32, stage 32 words of
+// each plane in LDS and add popcounts in registers; only tiles on or above the diagonal are computed, each writes its
+// mirror image too (pair_tile of clt_common.h, which the cutset learners' kernels in cnet.hip and cut.hip call too).  Queries:
 // one thread per row over column-major codes, the row's 2 D floats of state in `work` as [2 D][B], so that the lanes of
 // a wave read and write consecutive addresses and the tree tables are wave-uniform loads; the passes over the tree are the
 // Leaf functions of clt_common.h, which the leaves of a cutset network and the marginals use too.
@@ -20,35 +21,22 @@ using dpc_detail::leaf_root;
 using dp_device::counter_uniform;
 
 typedef unsigned long long u64;
+using dpc_detail::kMaxGridX;
+using dpc_detail::kPackThreads;
+using dpc_detail::kPairThreads;
+using dpc_detail::kPairTile;
+using dpc_detail::pack_tile;
+using dpc_detail::pair_tile;
 constexpr int kThreads = 256;
-constexpr int kTile = 64;          // rows and columns of x per packing work-group
-constexpr int kPairTile = 32;      // variables per side of a pair tile
-constexpr int kPairWords = 32;     // plane words staged per step
+constexpr int kTile = dpc_detail::kPackTile;      // rows and columns of x per packing work-group
 constexpr int kRowThreads = 64;    // query rows per work-group: one wave, so that few rows still spread over the CUs
-constexpr int64_t kMaxGridX = 2147483647;
 
 // ---- packing ---------------------------------------------------------------------------------------------------------
-// One work-group per 64 rows x 64 columns of x.  Loads are coalesced along a row; the tile is read back by column.
-__global__ __launch_bounds__(kThreads) void pack_bits_kernel(const float *__restrict__ x, int64_t n, int d, int64_t n_words,
-                                                             u64 *__restrict__ planes) {
-    __shared__ float tile[kTile][kTile + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// One work-group per 64 rows x 64 columns of x: line rr of the tile is row r0 + rr.
+__global__ __launch_bounds__(kPackThreads) void pack_bits_kernel(const float *__restrict__ x, int64_t n, int d,
+                                                                 int64_t n_words, u64 *__restrict__ planes) {
     const int64_t word = blockIdx.x, r0 = word * kTile;
-    const int c0 = blockIdx.y * kTile;
-    for (int rr = wave; rr < kTile; rr += kThreads / 64) {
-        const int64_t r = r0 + rr;
-        const int c = c0 + lane;
-        tile[rr][lane] = (r < n && c < d) ? x[r * d + c] : 0.f;
-    }
-    __syncthreads();
-    // wave w owns columns 16 w .. 16 w + 15 of the tile; lane c keeps the word of "its" column and stores it
-    u64 mine = 0;
-    for (int cc = 0; cc < 16; ++cc) {
-        const u64 m = __ballot(tile[lane][wave * 16 + cc] == 1.f);
-        if (lane == cc) mine = m;
-    }
-    const int c = c0 + wave * 16 + lane;
-    if (lane < 16 && c < d) planes[(int64_t)c * n_words + word] = mine;
+    pack_tile([&](int rr, int c) { return (r0 + rr < n && c < d) ? x[(r0 + rr) * d + c] : 0.f; }, word, d, n_words, planes);
 }
 
 __global__ __launch_bounds__(kThreads) void pack_query_kernel(const float *__restrict__ x, int64_t b, int d,
@@ -76,41 +64,10 @@ __global__ __launch_bounds__(kThreads) void pack_query_kernel(const float *__res
 }
 
 // ---- pair counts -----------------------------------------------------------------------------------------------------
-// Thread (ty, tx) of the 16 x 16 work-group owns the pairs (ty + 16 a, tx + 16 b), a, b in {0, 1}, of its tile.
-__global__ __launch_bounds__(kThreads) void pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
-                                                               int32_t *__restrict__ ones) {
-    const int ti = blockIdx.y, tj = blockIdx.x;
-    if (tj < ti) return;            // the mirror image is written by tile (tj, ti)
-    __shared__ u64 pi[kPairTile][kPairWords + 1], pj[kPairTile][kPairWords + 1];
-    const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
-    int acc[2][2] = {{0, 0}, {0, 0}};
-    for (int64_t w0 = 0; w0 < n_words; w0 += kPairWords) {
-        for (int e = t; e < kPairTile * kPairWords; e += kThreads) {
-            const int r = e / kPairWords, w = e % kPairWords;
-            const int i = ti * kPairTile + r, j = tj * kPairTile + r;
-            const bool in = w0 + w < n_words;
-            pi[r][w] = (in && i < d) ? planes[(int64_t)i * n_words + w0 + w] : 0ull;
-            pj[r][w] = (in && j < d) ? planes[(int64_t)j * n_words + w0 + w] : 0ull;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int w = 0; w < kPairWords; ++w) {
-            const u64 a0 = pi[ty][w], a1 = pi[ty + 16][w], b0 = pj[tx][w], b1 = pj[tx + 16][w];
-            acc[0][0] += __popcll(a0 & b0);
-            acc[0][1] += __popcll(a0 & b1);
-            acc[1][0] += __popcll(a1 & b0);
-            acc[1][1] += __popcll(a1 & b1);
-        }
-        __syncthreads();
-    }
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b) {
-            const int i = ti * kPairTile + ty + 16 * a, j = tj * kPairTile + tx + 16 * b;
-            if (i < d && j < d) {
-                ones[(int64_t)i * d + j] = acc[a][b];
-                ones[(int64_t)j * d + i] = acc[a][b];
-            }
-        }
+// the whole plane, one matrix (pair_tile of clt_common.h)
+__global__ __launch_bounds__(kPairThreads) void pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
+                                                                   int32_t *__restrict__ ones) {
+    pair_tile<false>(planes, n_words, d, 0, n_words, nullptr, ones);
 }
 
 // ---- queries -----------------------------------------------------------------------------------------------------------
@@ -216,7 +173,7 @@ int dpc_pack_bits(const float *x, int64_t n, int d, uint64_t *planes, void *stre
     DPC_REQUIRE(x && planes, "dpc_pack_bits: null pointer");
     const int64_t n_words = (n + 63) / 64;
     DPC_LAUNCH("dpc_pack_bits", pack_bits_kernel, dim3((unsigned)n_words, (unsigned)((d + kTile - 1) / kTile)),
-               dim3(kThreads), 0, (hipStream_t)stream, x, n, d, n_words, (u64 *)planes);
+               dim3(kPackThreads), 0, (hipStream_t)stream, x, n, d, n_words, (u64 *)planes);
     return DPC_OK;
 }
 
@@ -236,7 +193,7 @@ int dpc_pair_counts(const uint64_t *planes, int64_t n_words, int d, int32_t *one
                 (long long)n_words);
     DPC_REQUIRE(planes && ones, "dpc_pair_counts: null pointer");
     const unsigned nt = (unsigned)((d + kPairTile - 1) / kPairTile);
-    DPC_LAUNCH("dpc_pair_counts", pair_counts_kernel, dim3(nt, nt), dim3(kThreads), 0, (hipStream_t)stream,
+    DPC_LAUNCH("dpc_pair_counts", pair_counts_kernel, dim3(nt, nt), dim3(kPairThreads), 0, (hipStream_t)stream,
                (const u64 *)planes, n_words, d, ones);
     return DPC_OK;
 }

@@ -1,6 +1,7 @@
 // What the translation units of libdeeprob_clt.so share: the library's instance of the shared entry-point scaffolding
 // (error text, checks, check_net for the arguments every network query takes), lse2 / lse64 of the header's order of
-// operations, the shape of the segmented pair-count tile, copy_rows (a work-group's rows of x to out), a tree as a Leaf
+// operations, pack_tile (a tile of x to bit planes) and pair_tile (the 32 x 32 pair-count tile, plain, segmented or under a
+// cut) of the learners, copy_rows (a work-group's rows of x to out), a tree as a Leaf
 // with its passes (gather, upward, beliefs: a leaf of a cutset network, or with COLS = false a stand-alone tree), and a
 // cutset network as a Net with THE walk of its OR tree: or_walk owns the explicit stack and the guard that keeps a row
 // inside it, a visitor says what a query computes on the way (ValueVisitor here: the log likelihood, for cnet.hip and
@@ -18,13 +19,86 @@
 
 namespace dpc_detail {
 
-// The segmented pair counts (cnet.hip, cut.hip): a work-group of kPairThreads owns kPairTile x kPairTile variable pairs
-// and stages kPairWords plane words of both operands per step; grid.z is the task or the entry.
+// The pair counts (clt.hip, cnet.hip, cut.hip): a work-group of kPairThreads owns kPairTile x kPairTile variable pairs
+// and stages kPairWords plane words of both operands per step; grid.z is the task or the entry of the segmented ones.
 constexpr int kPairThreads = 256;
 constexpr int kPairTile = 32;
 constexpr int kPairWords = 32;
+constexpr int kPackThreads = 256;
+constexpr int kPackTile = 64;      // rows and columns of x per packing work-group
 constexpr int kMaxGridZ = 65535;
 constexpr int64_t kMaxGridX = 2147483647;
+static_assert(kPairThreads % kPairWords == 0, "a thread stages one word column");
+
+// Rows of x to bit planes, the step pack_bits_kernel (clt.hip) and gather_pack_kernel (cnet.hip) share: a work-group of
+// kPackThreads owns plane word `word` of the 64 columns from 64 blockIdx.y.  value(rr, c) is x at line rr of the tile,
+// column c (0 past the rows or the columns); a line is loaded by one wave, coalesced, and the tile is read back by column.
+template <typename Value>
+__device__ __forceinline__ void pack_tile(Value value, int64_t word, int d, int64_t n_words,
+                                          unsigned long long *__restrict__ planes) {
+    __shared__ float tile[kPackTile][kPackTile + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.y * kPackTile;
+    for (int rr = wave; rr < kPackTile; rr += kPackThreads / 64) tile[rr][lane] = value(rr, c0 + lane);
+    __syncthreads();
+    // wave w owns columns 16 w .. 16 w + 15 of the tile; lane c keeps the word of "its" column and stores it
+    unsigned long long mine = 0;
+    for (int cc = 0; cc < 16; ++cc) {
+        const unsigned long long m = __ballot(tile[lane][wave * 16 + cc] == 1.f);
+        if (lane == cc) mine = m;
+    }
+    const int c = c0 + wave * 16 + lane;
+    if (lane < 16 && c < d) planes[(int64_t)c * n_words + word] = mine;
+}
+
+// One 32 x 32 tile of co-occurrence counts over the plane words [w_begin, w_end): out[i][j] = sum_w popc(plane_i & plane_j
+// [& cut]) for the pairs of tile (blockIdx.y, blockIdx.x).  Only tiles on or above the diagonal are computed, each writes
+// its mirror image too.  Thread (ty, tx) of the 16 x 16 work-group owns the pairs (ty + 16 a, tx + 16 b), a, b in {0, 1}.
+// The rows of the LDS tiles are padded to kPairWords + 1 words: the 16 rows a half-wave reads then lie 2 banks apart (66
+// dwords a row, 64 banks for a 64-bit read), and the lanes that share a row read one address.  CUT: the words of the plane
+// `cut` are ANDed into the j operand while the step is staged, so the popcount loop is that of the unconditioned counts
+// (`cut` is one of `planes`: both are only read; without CUT it is not read at all and may be null).
+template <bool CUT>
+__device__ __forceinline__ void pair_tile(const unsigned long long *__restrict__ planes, int64_t n_words, int d,
+                                          int64_t w_begin, int64_t w_end, const unsigned long long *__restrict__ cut,
+                                          int32_t *__restrict__ out) {
+    typedef unsigned long long u64;
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj < ti) return;            // the mirror image is written by tile (tj, ti)
+    __shared__ u64 pi[kPairTile][kPairWords + 1], pj[kPairTile][kPairWords + 1];
+    const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
+    int acc[2][2] = {{0, 0}, {0, 0}};
+    for (int64_t w0 = w_begin; w0 < w_end; w0 += kPairWords) {
+        // kPairThreads is a multiple of kPairWords: a thread stages the same word of every row it touches
+        const int w = t % kPairWords;
+        const bool in = w0 + w < w_end;
+        const u64 pc = (CUT && in) ? cut[w0 + w] : 0ull;
+        for (int e = t; e < kPairTile * kPairWords; e += kPairThreads) {
+            const int r = e / kPairWords;
+            const int i = ti * kPairTile + r, j = tj * kPairTile + r;
+            pi[r][w] = (in && i < d) ? planes[(int64_t)i * n_words + w0 + w] : 0ull;
+            pj[r][w] = (in && j < d) ? planes[(int64_t)j * n_words + w0 + w] & (CUT ? pc : ~0ull) : 0ull;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int k = 0; k < kPairWords; ++k) {
+            const u64 a0 = pi[ty][k], a1 = pi[ty + 16][k], b0 = pj[tx][k], b1 = pj[tx + 16][k];
+            acc[0][0] += __popcll(a0 & b0);
+            acc[0][1] += __popcll(a0 & b1);
+            acc[1][0] += __popcll(a1 & b0);
+            acc[1][1] += __popcll(a1 & b1);
+        }
+        __syncthreads();
+    }
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            const int i = ti * kPairTile + ty + 16 * a, j = tj * kPairTile + tx + 16 * b;
+            if (i < d && j < d) {
+                out[(int64_t)i * d + j] = acc[a][b];
+                out[(int64_t)j * d + i] = acc[a][b];
+            }
+        }
+}
 
 __device__ __forceinline__ float lse2(float a, float b) {
     const float hi = fmaxf(a, b), lo = fminf(a, b);

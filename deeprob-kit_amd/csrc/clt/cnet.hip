@@ -4,8 +4,8 @@
 //
 // Layout of the work.  Learning is level synchronous: a generation is every open node of one depth, each with a segment
 // of a row-index array.  gather_pack_kernel makes bit planes of the generation's rows through the index, every segment on
-// a word boundary; seg_pair_counts_kernel is the 32 x 32 pair tile of clt.hip with the task on grid.z and the task's
-// words only; the scores are one thread per (task, column) for the conditional entropies and one thread per task for the
+// a word boundary (pack_tile of clt_common.h, a tile line taken through `rows`); seg_pair_counts_kernel is the 32 x 32
+// pair tile of clt_common.h (pair_tile, the one clt.hip and cut.hip call) with the task on grid.z and the task's words only; the scores are one thread per (task, column) for the conditional entropies and one thread per task for the
 // serial sums the header orders; partition_kernel splits a segment by the bits of its cut column, one work-group per task,
 // the position of a row from popcounts (no atomics, no scan through memory).  The query is one thread per row: a complete
 // row walks one path, a row with NaN walks the OR tree depth first with its stack in `work` (or_walk of clt_common.h).
@@ -20,24 +20,25 @@ using dpc_detail::or_walk;
 using dpc_detail::ValueVisitor;
 
 typedef unsigned long long u64;
-constexpr int kThreads = 256;
-constexpr int kTile = 64;
-using dpc_detail::kPairTile;
-using dpc_detail::kPairWords;
-constexpr int kRowThreads = 64;
-constexpr int kScoreThreads = 64;
 using dpc_detail::kMaxGridX;
 using dpc_detail::kMaxGridZ;
+using dpc_detail::kPackThreads;
+using dpc_detail::kPairThreads;
+using dpc_detail::kPairTile;
+using dpc_detail::pack_tile;
+using dpc_detail::pair_tile;
+constexpr int kThreads = 256;
+constexpr int kTile = dpc_detail::kPackTile;
+constexpr int kRowThreads = 64;
+constexpr int kScoreThreads = 64;
 
 // ---- gather-pack ---------------------------------------------------------------------------------------------------------
 // One work-group per plane word x 64 columns; the word's task is found by bisection of word_off (empty tasks own no word).
-__global__ __launch_bounds__(kThreads) void gather_pack_kernel(const float *__restrict__ x, int64_t n, int d,
+__global__ __launch_bounds__(kPackThreads) void gather_pack_kernel(const float *__restrict__ x, int64_t n, int d,
                                                                const int32_t *__restrict__ rows,
                                                                const int32_t *__restrict__ seg_off,
                                                                const int32_t *__restrict__ word_off, int n_tasks,
                                                                int64_t n_words, u64 *__restrict__ planes) {
-    __shared__ float tile[kTile][kTile + 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t word = blockIdx.x;
     int lo = 0, hi = n_tasks - 1;
     while (lo < hi) {
@@ -45,65 +46,25 @@ __global__ __launch_bounds__(kThreads) void gather_pack_kernel(const float *__re
         if ((int64_t)word_off[mid + 1] <= word) lo = mid + 1; else hi = mid;
     }
     const int64_t p0 = (int64_t)seg_off[lo] + (word - word_off[lo]) * kTile, p_end = seg_off[lo + 1];
-    const int c0 = blockIdx.y * kTile;
-    for (int rr = wave; rr < kTile; rr += kThreads / 64) {
-        const int64_t p = p0 + rr;
-        const int c = c0 + lane;
-        float v = 0.f;
-        if (p < p_end && c < d) {
-            const int64_t r = rows[p];
-            if (r >= 0 && r < n) v = x[r * d + c];
-        }
-        tile[rr][lane] = v;
-    }
-    __syncthreads();
-    u64 mine = 0;
-    for (int cc = 0; cc < 16; ++cc) {
-        const u64 m = __ballot(tile[lane][wave * 16 + cc] == 1.f);
-        if (lane == cc) mine = m;
-    }
-    const int c = c0 + wave * 16 + lane;
-    if (lane < 16 && c < d) planes[(int64_t)c * n_words + word] = mine;
+    pack_tile(
+        [&](int rr, int c) {
+            const int64_t p = p0 + rr;
+            float v = 0.f;
+            if (p < p_end && c < d) {
+                const int64_t r = rows[p];
+                if (r >= 0 && r < n) v = x[r * d + c];
+            }
+            return v;
+        },
+        word, d, n_words, planes);
 }
 
 // ---- segmented pair counts -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void seg_pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
+__global__ __launch_bounds__(kPairThreads) void seg_pair_counts_kernel(const u64 *__restrict__ planes, int64_t n_words, int d,
                                                                    const int32_t *__restrict__ word_off,
                                                                    int32_t *__restrict__ ones) {
-    const int ti = blockIdx.y, tj = blockIdx.x;
-    if (tj < ti) return;            // the mirror image is written by tile (tj, ti)
-    __shared__ u64 pi[kPairTile][kPairWords + 1], pj[kPairTile][kPairWords + 1];
-    const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
-    const int64_t w_begin = word_off[blockIdx.z], w_end = word_off[blockIdx.z + 1];
-    int acc[2][2] = {{0, 0}, {0, 0}};
-    for (int64_t w0 = w_begin; w0 < w_end; w0 += kPairWords) {
-        for (int e = t; e < kPairTile * kPairWords; e += kThreads) {
-            const int r = e / kPairWords, w = e % kPairWords;
-            const int i = ti * kPairTile + r, j = tj * kPairTile + r;
-            const bool in = w0 + w < w_end;
-            pi[r][w] = (in && i < d) ? planes[(int64_t)i * n_words + w0 + w] : 0ull;
-            pj[r][w] = (in && j < d) ? planes[(int64_t)j * n_words + w0 + w] : 0ull;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int w = 0; w < kPairWords; ++w) {
-            const u64 a0 = pi[ty][w], a1 = pi[ty + 16][w], b0 = pj[tx][w], b1 = pj[tx + 16][w];
-            acc[0][0] += __popcll(a0 & b0);
-            acc[0][1] += __popcll(a0 & b1);
-            acc[1][0] += __popcll(a1 & b0);
-            acc[1][1] += __popcll(a1 & b1);
-        }
-        __syncthreads();
-    }
-    int32_t *out = ones + (int64_t)blockIdx.z * d * d;
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b) {
-            const int i = ti * kPairTile + ty + 16 * a, j = tj * kPairTile + tx + 16 * b;
-            if (i < d && j < d) {
-                out[(int64_t)i * d + j] = acc[a][b];
-                out[(int64_t)j * d + i] = acc[a][b];
-            }
-        }
+    pair_tile<false>(planes, n_words, d, word_off[blockIdx.z], word_off[blockIdx.z + 1], nullptr,
+                     ones + (int64_t)blockIdx.z * d * d);
 }
 
 // ---- scores --------------------------------------------------------------------------------------------------------------
@@ -291,7 +252,7 @@ int dpc_cnet_gather_pack(const float *x, int64_t n, int d, const int32_t *rows, 
     DPC_REQUIRE(x && rows && seg_off && word_off && planes, "dpc_cnet_gather_pack: null pointer");
     if (n_words == 0) return DPC_OK;
     DPC_LAUNCH("dpc_cnet_gather_pack", gather_pack_kernel, dim3((unsigned)n_words, (unsigned)((d + kTile - 1) / kTile)),
-               dim3(kThreads), 0, (hipStream_t)stream, x, n, d, rows, seg_off, word_off, n_tasks, n_words, (u64 *)planes);
+               dim3(kPackThreads), 0, (hipStream_t)stream, x, n, d, rows, seg_off, word_off, n_tasks, n_words, (u64 *)planes);
     return DPC_OK;
 }
 
@@ -304,7 +265,7 @@ int dpc_cnet_pair_counts(const uint64_t *planes, int64_t n_words, int d, const i
                 (long long)n_words);
     DPC_REQUIRE((planes || n_words == 0) && word_off && ones, "dpc_cnet_pair_counts: null pointer");
     const unsigned nt = (unsigned)((d + kPairTile - 1) / kPairTile);
-    DPC_LAUNCH("dpc_cnet_pair_counts", seg_pair_counts_kernel, dim3(nt, nt, (unsigned)n_tasks), dim3(kThreads), 0,
+    DPC_LAUNCH("dpc_cnet_pair_counts", seg_pair_counts_kernel, dim3(nt, nt, (unsigned)n_tasks), dim3(kPairThreads), 0,
                (hipStream_t)stream, (const u64 *)planes, n_words, d, word_off, ones);
     return DPC_OK;
 }

@@ -55,6 +55,8 @@ static_assert(DPM_OK == DPG_OK && DPM_EINVAL == DPG_EINVAL && DPM_ELAUNCH == DPG
 
 namespace dpg_detail {
 
+using dp_device::block_max_nan;
+using dp_device::block_sum;
 using dp_device::wave_max_nan;
 using dp_device::wave_sum;
 
@@ -77,31 +79,6 @@ struct MomentsArgs {
     float *ws;
     int64_t nF, nG;                      // floats of the two buffers of a slice
 };
-
-__device__ __forceinline__ float block_max_nan(float m, float *red) {
-    m = wave_max_nan(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = red[0];
-#pragma unroll
-    for (int w = 1; w < kMoWaves; ++w) {
-        const float t = red[w];
-        m = (t > m || t != t) ? t : m;
-    }
-    __syncthreads();
-    return m;
-}
-
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int w = 1; w < kMoWaves; ++w) v += red[w];
-    __syncthreads();
-    return v;
-}
 
 // CMAX: the most inputs of a sum node that a thread keeps in registers, kMoSmall or kMoWide
 template <int CMAX>
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(kMoThreads) void dgcspn_moments_kernel(const Moment
                     const float v = score(cc, i);
                     m = (v > m || v != v) ? v : m;
                 }
-            m = block_max_nan(m, red);
+            m = block_max_nan<kMoWaves>(m, red);
             if (!(m > -INFINITY)) {
                 // evidence impossible under the model (or undefined): NaN in the NaN entries, the observed ones as given
                 for (int f = tid; f < CHW; f += kMoThreads) {
@@ -152,7 +129,7 @@ __global__ __launch_bounds__(kMoThreads) void dgcspn_moments_kernel(const Moment
             float tot = 0.f;
             for (int cc = 0; cc < ncls; ++cc)
                 for (int i = tid; i < N; i += kMoThreads) tot += expf(score(cc, i) - m);
-            tot = block_sum(tot, red);
+            tot = block_sum<kMoWaves>(tot, red);
             for (int i = tid; i < N; i += kMoThreads) {
                 float c = 0.f;
                 for (int cc = 0; cc < ncls; ++cc) c += expf(score(cc, i) - m);

@@ -1,22 +1,17 @@
 // Bottom-up log-likelihood of a vanilla (node-graph) SPN flattened into arrays -- BASELINE config 1.
 //
 // Replaces, for one batch, the node-by-node numpy pass of deeprob/spn/algorithms/evaluation.py:37-96 with the
-// node functions of deeprob/spn/algorithms/inference.py:94-103 (every node value clamped at -1e31, float32):
-//   Sum      node.py:116-117   logsumexp(children, b = weights)
-//   Product  node.py:152-153   sum(children)
-//   leaves   leaf.py:182-186 (Bernoulli), :301-305 (Categorical), :475-479 (Uniform), :553-557 (Gaussian);
-//            0 where the input is NaN (marginalised)
+// node functions of deeprob/spn/algorithms/inference.py:94-103 (every node value clamped at -1e31, float32), which
+// shared/flat_spn_nodes.h defines once for this file, flat_spn_queries.hip and spnq/flat_spn_posterior.hip.
 // Layout: lane = sample, the node loop is uniform over the wave (node records come through scalar loads); the
 // table of node values is [row][sample], so every access is one 256-byte row per wave.  In LDS (one 64-sample wave
 // per work-group) a node's row is a slot that the host recycles after the node's last parent has been evaluated
 // (a tree-like circuit needs a handful of slots, so the wave count per CU is not bounded by LDS); a circuit whose
 // live set does not fit, or a caller that wants every node's value, uses a [n_nodes, B] buffer with row = node id.
 #include "common.h"
+#include "shared/flat_spn_nodes.h"
 
 namespace dpk {
-
-enum FlatKind : int32_t { kFlatSum = 0, kFlatProduct = 1, kFlatBernoulli = 2, kFlatCategorical = 3, kFlatUniform = 4,
-                          kFlatGaussian = 5 };
 
 struct FlatSpnArgs {
     const float *x;
@@ -34,7 +29,6 @@ struct FlatSpnArgs {
     float *out;
 };
 
-constexpr float kFlatFloor = -1e31f;            // inference.py:103
 constexpr int kFlatLdsSlots = 256;              // 256 rows x 64 samples x 4 B = 64 KB of LDS
 
 template <bool kLds>
@@ -49,45 +43,7 @@ __global__ __launch_bounds__(64) void flat_spn_kernel(const FlatSpnArgs a) {
     for (int t = 0; t < a.n_nodes; ++t) {
         const int i = a.order[t];
         const int kind = a.kind[i];
-        float v;
-        if (kind == kFlatSum) {
-            // scipy logsumexp with weights: zero-weight terms are dropped, m = max of the rest (0 if not finite)
-            const int c0 = a.arg0[i], nc = a.arg1[i];
-            float m = -INFINITY;
-            for (int j = 0; j < nc; ++j)
-                if (a.child_weight[c0 + j] != 0.f) m = fmaxf(m, load(a.child_index[c0 + j]));
-            if (!(fabsf(m) < INFINITY)) m = 0.f;
-            float s = 0.f;
-            for (int j = 0; j < nc; ++j) {
-                const float w = a.child_weight[c0 + j];
-                if (w != 0.f) s += w * expf(load(a.child_index[c0 + j]) - m);
-            }
-            v = logf(s) + m;
-        } else if (kind == kFlatProduct) {
-            const int c0 = a.arg0[i], nc = a.arg1[i];
-            v = 0.f;
-            for (int j = 0; j < nc; ++j) v += load(a.child_index[c0 + j]);
-        } else {
-            const float xv = xrow[a.arg0[i]];
-            if (xv != xv) {
-                v = 0.f;
-            } else if (kind == kFlatBernoulli) {          // par0 = log p, par1 = log1p(-p)
-                v = (xv == 1.f) ? (float)a.par0[i] : (xv == 0.f) ? (float)a.par1[i] : -INFINITY;
-            } else if (kind == kFlatCategorical) {        // x.astype(int64): truncation toward zero
-                const int c0 = a.arg1[i], nc = a.arg2[i];
-                const long long cat = (long long)xv;
-                v = -INFINITY;
-                for (int j = 0; j < nc; ++j)
-                    if ((long long)a.cat_value[c0 + j] == cat) v = a.cat_logp[c0 + j];
-            } else if (kind == kFlatUniform) {            // par0 = start, par1 = width
-                const double z = ((double)xv - a.par0[i]) / a.par1[i];
-                v = (z >= 0.0 && z <= 1.0) ? (float)(-log(a.par1[i])) : -INFINITY;
-            } else {                                      // Gaussian: par0 = mean, par1 = stddev
-                const double z = ((double)xv - a.par0[i]) / a.par1[i];
-                v = (float)(-0.5 * z * z - 0.91893853320467274178 - log(a.par1[i]));
-            }
-        }
-        v = fmaxf(v, kFlatFloor);
+        const float v = dp_device::flat::node_value(a, i, kind, xrow, a.child_index, load);
         if (kLds)
             lds[a.node_slot[i] * 64 + lane] = v;
         else if (own)

@@ -35,61 +35,18 @@
 // the update to its own parameters (raw and derived).  No work-group reads a parameter another one writes.
 #include "common.h"
 #include "shared/device.h"
+#include "shared/flat_spn_nodes.h"
 #include <math.h>
 
 namespace dpk {
 namespace fq {
 
-enum : int32_t { kSum = 0, kProduct = 1, kBernoulli = 2, kCategorical = 3, kUniform = 4, kGaussian = 5 };
-constexpr float kFloor = -1e31f;            // inference.py:103
+using namespace dp_device::flat;     // the kinds, node_value, log_add_exp
 constexpr int kLdsBytes = 65536;
 constexpr int kUpdThreads = 256;
 using Circuit = dpk_flat_spn_circuit;
 typedef unsigned long long u64;
 using dp_device::counter_uniform;
-
-// value of node i from its children's rows / its input (flat_spn.hip's node functions)
-template <class Load>
-__device__ __forceinline__ float node_value(const Circuit &c, int i, int kind, const float *xrow, const int32_t *cidx, Load load) {
-    float v;
-    if (kind == kSum) {
-        const int c0 = c.arg0[i], nc = c.arg1[i];
-        float m = -INFINITY;
-        for (int j = 0; j < nc; ++j)
-            if (c.child_weight[c0 + j] != 0.f) m = fmaxf(m, load(cidx[c0 + j]));
-        if (!(fabsf(m) < INFINITY)) m = 0.f;
-        float s = 0.f;
-        for (int j = 0; j < nc; ++j) {
-            const float w = c.child_weight[c0 + j];
-            if (w != 0.f) s += w * expf(load(cidx[c0 + j]) - m);
-        }
-        v = logf(s) + m;
-    } else if (kind == kProduct) {
-        const int c0 = c.arg0[i], nc = c.arg1[i];
-        v = 0.f;
-        for (int j = 0; j < nc; ++j) v += load(cidx[c0 + j]);
-    } else {
-        const float xv = xrow[c.arg0[i]];
-        if (xv != xv) {
-            v = 0.f;
-        } else if (kind == kBernoulli) {
-            v = (xv == 1.f) ? (float)c.par0[i] : (xv == 0.f) ? (float)c.par1[i] : -INFINITY;
-        } else if (kind == kCategorical) {
-            const int k0 = c.arg1[i], nk = c.arg2[i];
-            const long long cat = (long long)xv;
-            v = -INFINITY;
-            for (int j = 0; j < nk; ++j)
-                if ((long long)c.cat_value[k0 + j] == cat) v = c.cat_logp[k0 + j];
-        } else if (kind == kUniform) {
-            const double z = ((double)xv - c.par0[i]) / c.par1[i];
-            v = (z >= 0.0 && z <= 1.0) ? (float)(-log(c.par1[i])) : -INFINITY;
-        } else {
-            const double z = ((double)xv - c.par0[i]) / c.par1[i];
-            v = (float)(-0.5 * z * z - 0.91893853320467274178 - log(c.par1[i]));
-        }
-    }
-    return fmaxf(v, kFloor);
-}
 
 __device__ __forceinline__ u64 wave_uniform(u64 v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
@@ -248,12 +205,6 @@ __global__ __launch_bounds__(64) void flat_topdown_kernel(const TopdownArgs a) {
             }
         }
     }
-}
-
-__device__ __forceinline__ float log_add_exp(float p, float q) {
-    const float m = fmaxf(p, q);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log1pf(expf(-fabsf(p - q)));
 }
 
 // parents before children over column b of the tables (row = node id, row stride B)

@@ -75,12 +75,6 @@ __global__ void maf_act_bwd_kernel(float *__restrict__ dh, const float *__restri
         dh[e] *= act_grad_from_out(act, y[e]);
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // u = (x - t) exp(-a tanh(s)), ildj = -sum a tanh(s): one wave per row
 __global__ __launch_bounds__(256) void maf_epilogue_kernel(const float *__restrict__ x, const float *__restrict__ Z,
                                                            int64_t B, int D, const float *__restrict__ aw,
@@ -96,7 +90,7 @@ __global__ __launch_bounds__(256) void maf_epilogue_kernel(const float *__restri
         u[row * D + d] = (x[row * D + d] - z[d]) * expf(-s);
         acc += s;
     }
-    acc = wave_sum(acc);
+    acc = wave_reduce_sum(acc);
     if (lane == 0) ildj[row] = -acc;
 }
 
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(256) void maf_epilogue_bwd_kernel(const float *__re
         dZ[row * 2 * D + D + d] = ds * a * (1.f - th * th);
         acc += ds * th;
     }
-    acc = wave_sum(acc);
+    acc = wave_reduce_sum(acc);
     if (lane == 0) pa[row] = acc;
 }
 

@@ -43,6 +43,8 @@
 
 namespace dpr_detail {
 
+using dp_device::block_max_nan;
+using dp_device::block_sum;
 using dp_device::wave_max_nan;
 using dp_device::wave_sum;
 
@@ -66,31 +68,6 @@ struct MomentsArgs {
     float *mean, *var, *leaf_flow;          // [B, D], [B, D] or null, [B, reps 2^depth, I] or null
     int even_floats, odd_floats;            // sizes of the two flow tables
 };
-
-__device__ __forceinline__ float block_max_nan(float m, float *red) {
-    m = wave_max_nan(m);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = red[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) {
-        const float t = red[w];
-        m = (t > m || t != t) ? t : m;
-    }
-    __syncthreads();
-    return m;
-}
-
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) v += red[w];
-    __syncthreads();
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void ratspn_moments_kernel(const MomentsArgs a) {
     extern __shared__ float mo_lds[];
@@ -136,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void ratspn_moments_kernel(const MomentsA
             const float v = score(q);
             m = (v > m || v != v) ? v : m;
         }
-        m = block_max_nan(m, red);
+        m = block_max_nan<kWaves>(m, red);
         if (!(m > -INFINITY)) {
             // evidence impossible under the model (or undefined): NaN in the NaN entries, the observed ones as given
             for (int f = tid; f < D; f += kThreads) {
@@ -150,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void ratspn_moments_kernel(const MomentsA
         }
         float tot = 0.f;
         for (int q = tid; q < Q; q += kThreads) tot += expf(score(q) - m);
-        tot = block_sum(tot, red);
+        tot = block_sum<kWaves>(tot, red);
         for (int f = tid; f < D; f += kThreads) {               // (a variable belongs to one thread throughout)
             stat[f] = 0.f;
             stat[D + f] = 0.f;

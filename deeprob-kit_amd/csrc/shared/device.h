@@ -1,5 +1,7 @@
-// Device primitives that the samplers and top-down passes of every library share.  Header-only and force-inlined: each
-// includer compiles them under its own flags (the small libraries with -ffp-contract=off, libdeeprob_hip.so without).
+// Device primitives that the samplers and top-down passes of every library share: counter_uniform (the draw), wave_max_nan
+// and wave_sum, block_max_nan<WAVES> and block_sum<WAVES> (the same over a work-group; the moment kernels of rat/ and dgc/),
+// wave_inverse_cdf.  Header-only and force-inlined: each includer compiles them under its own flags (the small libraries
+// with -ffp-contract=off, libdeeprob_hip.so without).  The node functions of a flattened SPN are in flat_spn_nodes.h.
 //
 // The draw.  Every sampler of the project is counter based, so that a test can replay it from Python:
 //
@@ -35,6 +37,35 @@ __device__ __forceinline__ float wave_max_nan(float m) {
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The same over a work-group of WAVES waves, through red[WAVES] in LDS: the waves' results are combined in wave order by
+// every thread, so all end with the same bits.  Every thread of the work-group calls; red is free again on return.
+template <int WAVES>
+__device__ __forceinline__ float block_max_nan(float m, float *red) {
+    m = wave_max_nan(m);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    m = red[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) {
+        const float t = red[w];
+        m = (t > m || t != t) ? t : m;
+    }
+    __syncthreads();
+    return m;
+}
+
+template <int WAVES>
+__device__ __forceinline__ float block_sum(float v, float *red) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = red[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) v += red[w];
+    __syncthreads();
     return v;
 }
 

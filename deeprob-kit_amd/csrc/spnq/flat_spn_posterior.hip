@@ -8,9 +8,11 @@
 // Organisation of flat_topdown_kernel (csrc/flat_spn_queries.hip): a 64-lane wave per 64 rows, lane = row, the node loop
 // uniform over the wave so that node records come through wave-uniform loads, tables [node][row] so that every access
 // is one 256-byte row per wave (one LDS bank per lane, no conflict).  A lane touches its own column only: there is no
-// barrier and no cross-lane traffic, and a tail lane simply leaves.  The node functions are this file's own copy of
-// those of flat_spn.hip / flat_spn_queries.hip; -ffp-contract=off (csrc/Makefile) keeps every product and sum as written.
+// barrier and no cross-lane traffic, and a tail lane simply leaves.  The node functions are those of
+// shared/flat_spn_nodes.h, the one definition flat_spn.hip and flat_spn_queries.hip use too; -ffp-contract=off
+// (csrc/Makefile) keeps every product and sum as written.
 #include "spnq_common.h"
+#include "../shared/flat_spn_nodes.h"
 #include <stddef.h>
 #include "../../../include/deeprob_hip.h"
 
@@ -29,58 +31,8 @@ DPQ_SAME_FIELD(par0); DPQ_SAME_FIELD(par1); DPQ_SAME_FIELD(raw0); DPQ_SAME_FIELD
 
 namespace dpq_detail {
 
-enum : int32_t { kSum = 0, kProduct = 1, kBernoulli = 2, kCategorical = 3, kUniform = 4, kGaussian = 5 };
-constexpr float kFloor = -1e31f;            // inference.py:103
+using namespace dp_device::flat;     // the kinds, kFloor, node_value, log_add_exp
 using Circuit = dpq_flat_spn_circuit;
-
-// value of node i from its children's rows / its input (flat_spn.hip's node functions; row = node id)
-template <class Load>
-__device__ __forceinline__ float node_value(const Circuit &c, int i, int kind, const float *xrow, Load load) {
-    float v;
-    if (kind == kSum) {
-        const int c0 = c.arg0[i], nc = c.arg1[i];
-        float m = -INFINITY;
-        for (int j = 0; j < nc; ++j)
-            if (c.child_weight[c0 + j] != 0.f) m = fmaxf(m, load(c.child_index[c0 + j]));
-        if (!(fabsf(m) < INFINITY)) m = 0.f;
-        float s = 0.f;
-        for (int j = 0; j < nc; ++j) {
-            const float w = c.child_weight[c0 + j];
-            if (w != 0.f) s += w * expf(load(c.child_index[c0 + j]) - m);
-        }
-        v = logf(s) + m;
-    } else if (kind == kProduct) {
-        const int c0 = c.arg0[i], nc = c.arg1[i];
-        v = 0.f;
-        for (int j = 0; j < nc; ++j) v += load(c.child_index[c0 + j]);
-    } else {
-        const float xv = xrow[c.arg0[i]];
-        if (xv != xv) {
-            v = 0.f;
-        } else if (kind == kBernoulli) {
-            v = (xv == 1.f) ? (float)c.par0[i] : (xv == 0.f) ? (float)c.par1[i] : -INFINITY;
-        } else if (kind == kCategorical) {
-            const int k0 = c.arg1[i], nk = c.arg2[i];
-            const long long cat = (long long)xv;
-            v = -INFINITY;
-            for (int j = 0; j < nk; ++j)
-                if ((long long)c.cat_value[k0 + j] == cat) v = c.cat_logp[k0 + j];
-        } else if (kind == kUniform) {
-            const double z = ((double)xv - c.par0[i]) / c.par1[i];
-            v = (z >= 0.0 && z <= 1.0) ? (float)(-log(c.par1[i])) : -INFINITY;
-        } else {
-            const double z = ((double)xv - c.par0[i]) / c.par1[i];
-            v = (float)(-0.5 * z * z - 0.91893853320467274178 - log(c.par1[i]));
-        }
-    }
-    return fmaxf(v, kFloor);
-}
-
-__device__ __forceinline__ float log_add_exp(float p, float q) {
-    const float m = fmaxf(p, q);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log1pf(expf(-fabsf(p - q)));
-}
 
 // non-central moments of order 1..4 of leaf i (the header's table)
 __device__ __forceinline__ void leaf_moments(const Circuit &c, int i, int kind, double &m1, double &m2, double &m3, double &m4) {
@@ -162,7 +114,7 @@ __global__ __launch_bounds__(64) void flat_posterior_kernel(const PosteriorArgs 
     // ---- 1. bottom-up: every node keeps its row ------------------------------------------------------------------------
     for (int t = 0; t < n; ++t) {
         const int i = c.order[t];
-        const float v = node_value(c, i, c.kind[i], xrow, val);
+        const float v = node_value(c, i, c.kind[i], xrow, c.child_index, val);
         if (kLds)
             lds[i * 64 + lane] = v;
         else
