@@ -356,8 +356,9 @@ __global__ __launch_bounds__(64 * kBwdWaves) void sum_bwd_kernel(const float *__
 #pragma unroll
             for (int q = 0; q < kBwdOB; ++q) {
                 const float xo = xo8[q];
-                // an all -inf row has out = -inf: its gradient is defined as zero (reference: the
-                // masked_fill guard inside torch.logsumexp's backward gives the same)
+                // an all -inf row has out = -inf: its gradient is DEFINED as zero, for its inputs and its
+                // weights.  A convention of this project, not the reference's result: autograd through
+                // torch.logsumexp yields NaN there (tests/test_ratspn_level_backward_host.py states both)
                 const float t = (ob + q < S && xo > -INFINITY) ? g8[q] * expf(fminf((xv - xo) + lw[q], kRespArgMax) - c8[q]) : 0.f;   // (large magnitudes cancel first, exactly; then the residual)
                 acc[q] += t;
                 tot += t;

@@ -145,10 +145,11 @@ __global__ __launch_bounds__(256) void prodsum_bwd_kernel(const LevelBwdArgs a) 
             const TwoSum ac = two_sum(xa[u], xc[u]);
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                // an all -inf row has out = -inf: its gradient is defined as zero (sum_bwd_kernel, and the masked_fill
-                // guard inside torch.logsumexp's backward).  The responsibilities of a sum node are normalised over its
-                // N*N inputs (the lanes of the group) instead of trusting the stored `out`, whose own rounding (half an ulp
-                // of ~560) would otherwise scale all of them alike.
+                // an all -inf row has out = -inf: its gradient is DEFINED as zero, for its inputs and its weights, here as
+                // in sum_bwd_kernel.  A convention of this project: autograd through torch.logsumexp yields NaN there, for
+                // the dead inputs and for every weight of the node (tests/test_ratspn_level_backward_host.py states both).
+                // The responsibilities of a sum node are normalised over its N*N inputs (the lanes of the group) instead of
+                // trusting the stored `out`, whose own rounding (half an ulp of ~560) would otherwise scale all of them alike.
                 const float e = (in[u] && o[u][s] > -INFINITY) ? expf(resp_arg(ac, lw[s], o[u][s])) : 0.f;
                 const float z = dpp_group_sum<NN>(e);
                 const float t = z > 0.f ? gg[u][s] * (e * __builtin_amdgcn_rcpf(z)) : 0.f;   // (hardware reciprocal, 1 ulp: the IEEE division is ten instructions)
