@@ -1,4 +1,5 @@
-// Top-down pass of a DGC-SPN in ONE launch: DgcSpn.sample (mode 1) and DgcSpn.sample_conditional (mode 2).
+// Top-down pass of a DGC-SPN in ONE launch: DgcSpn.sample (mode 1), DgcSpn.sample_conditional (mode 2) and
+// DgcSpn.mpe_completion (mode 3).
 //
 // reference: deeprob/spn/models/dgcspn.py raises NotImplementedError in `sample` and has no conditional sampler; the
 // circuit is the one its forward evaluates (SpatialGaussianLayer, SpatialProductLayer, SpatialSumLayer, SpatialRootLayer of
@@ -40,6 +41,15 @@
 //     Hout_{t-1} Wout_{t-1}), slots base_L + 2 ((c H + h) W + w), + 1 the two uniforms of leaf entry (c, h, w).  A row's
 //     output depends on (seed, row index, y) and its evidence only.
 //   Mode 1 (no evidence) takes every activation as log 1: act == null, every draw is by the bare weights, no bottom-up pass.
+//   Mode 3 (max-product completion) selects where mode 2 draws; arguments as in mode 2, `seed` is ignored and no uniform is
+//     formed.  At the root and at every active position of every sum layer, with mode 2's scores s(n) (the same fp32
+//     expressions, operand for operand) and their NaN-sticky maximum m: if m > -inf, the first n in index order with
+//     s(n) == m; otherwise (m is -inf or NaN) the first n in index order that maximises logw(n), a NaN weight never over a
+//     number -- the bare weights again.  Ties always go to the lowest index.  A node of more than 64 inputs: every lane
+//     keeps the first maximum of its strided indices n = lane, lane + 64, ..., the wave then takes the largest value and
+//     among equal values the smallest index.  Leaves: an observed entry is copied bit for bit, a NaN entry of a pixel
+//     reached with component k is loc[k, c, h, w] bit for bit (the mode of a Gaussian); `scale` is not read.  The result is
+//     the leaf modes of the induced tree chosen greedily from the sum-pass activations, as csrc/ratspn_topdown.hip's MPE.
 //
 // Shape of the kernel: one work-group of 256 threads per sample, grid-stride over samples.  The state between two levels is
 // the list of the active positions of a map with their channels, (channel << 16 | position) -- the chosen-channel map in
@@ -104,9 +114,71 @@ __device__ __forceinline__ int lane_inverse_cdf(int count, float u, WeightFn wei
     return count - 1;
 }
 
-// One node's draw among `count` inputs, by a wave (every lane returns the pick) or by one lane.
-template <bool POSTERIOR, typename ScoreFn, typename LogwFn>
+// First n in index order with value(n) == the NaN-sticky maximum of value, which is left in m; by one lane.  (A maximum of
+// -inf or NaN: the caller does not use the index.)
+template <typename ValueFn>
+__device__ __forceinline__ int lane_first_max(int count, float &m, ValueFn value) {
+    int at = 0;
+    m = -INFINITY;
+    for (int n = 0; n < count; ++n) {
+        const float v = value(n);
+        if (v > m) {
+            m = v;
+            at = n;
+        } else if (v != v) {
+            m = v;                                   // (once NaN, m stays NaN)
+        }
+    }
+    return at;
+}
+
+// The same by a wave: every lane keeps the first maximum of its strided indices, then a butterfly takes the largest value
+// and, among equal values, the smallest index.  Every lane ends with the same m and, when m is a number, the same index.
+template <typename ValueFn>
+__device__ __forceinline__ int wave_first_max(int count, int lane, float &m, ValueFn value) {
+    int at = 0x7fffffff;
+    m = -INFINITY;
+    for (int n = lane; n < count; n += 64) {
+        const float v = value(n);
+        if (v > m) {
+            m = v;
+            at = n;
+        } else if (v != v) {
+            m = v;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float t = __shfl_xor(m, o, 64);
+        const int ta = __shfl_xor(at, o, 64);
+        if (t > m || t != t || (t == m && ta < at)) {
+            m = t;
+            at = ta;
+        }
+    }
+    return at == 0x7fffffff ? 0 : at;                // (no value above -inf: index 0, as the lane's loop)
+}
+
+// the number a weight counts as in mode 3's fallback: a NaN weight is never picked over a number
+__device__ __forceinline__ float weight_or_least(float w) { return w != w ? -INFINITY : w; }
+
+// the uniform of a node or leaf draw; mode 3 draws nothing and forms none
+template <int MODE>
+__device__ __forceinline__ float draw_uniform(unsigned long long seed, unsigned long long ctr) {
+    return MODE == DPG_MODE_MPE ? 0.f : dp_device::counter_uniform(seed, ctr);
+}
+
+// One node's draw (mode 3: selection) among `count` inputs, by a wave (every lane returns the pick) or by one lane.
+template <int MODE, typename ScoreFn, typename LogwFn>
 __device__ __forceinline__ int wave_choose(int count, int lane, float u, ScoreFn score, LogwFn logw) {
+    constexpr bool POSTERIOR = MODE == DPG_MODE_POSTERIOR;
+    if (MODE == DPG_MODE_MPE) {
+        float m;
+        int at = wave_first_max(count, lane, m, score);
+        // (wave-uniform; -inf and NaN: the bare weights.  All of them -inf or NaN: the lowest index)
+        if (!(m > -INFINITY)) at = wave_first_max(count, lane, m, [&](int n) { return weight_or_least(logw(n)); });
+        return at;
+    }
     if (POSTERIOR) {
         float m = -INFINITY;
         for (int n = lane; n < count; n += 64) {
@@ -120,8 +192,15 @@ __device__ __forceinline__ int wave_choose(int count, int lane, float u, ScoreFn
     return wave_inverse_cdf(count, lane, u, [&](int n) { return expf(logw(n)); });
 }
 
-template <bool POSTERIOR, typename ScoreFn, typename LogwFn>
+template <int MODE, typename ScoreFn, typename LogwFn>
 __device__ __forceinline__ int lane_choose(int count, float u, ScoreFn score, LogwFn logw) {
+    constexpr bool POSTERIOR = MODE == DPG_MODE_POSTERIOR;
+    if (MODE == DPG_MODE_MPE) {
+        float m;
+        int at = lane_first_max(count, m, score);
+        if (!(m > -INFINITY)) at = lane_first_max(count, m, [&](int n) { return weight_or_least(logw(n)); });
+        return at;
+    }
     if (POSTERIOR) {
         float m = -INFINITY;
         for (int n = 0; n < count; ++n) {
@@ -133,9 +212,10 @@ __device__ __forceinline__ int lane_choose(int count, float u, ScoreFn score, Lo
     return lane_inverse_cdf(count, u, [&](int n) { return expf(logw(n)); });
 }
 
-// POSTERIOR = false: mode 1 (act is not read); true: mode 2
-template <bool POSTERIOR>
+// MODE: DPG_MODE_PRIOR (act is not read), DPG_MODE_POSTERIOR or DPG_MODE_MPE (the scores of mode 2, selected from)
+template <int MODE>
 __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownArgs a) {
+    constexpr bool POSTERIOR = MODE != DPG_MODE_PRIOR;
     extern __shared__ int td_lists[];               // [2][cap]
     __shared__ int td_count[DPG_MAX_LEVELS];        // entries of the list of map j (the input map of product level j)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -160,8 +240,8 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
             const int cls = a.y ? min(max((int)a.y[b], 0), a.classes - 1) : 0;
             const float *A = POSTERIOR ? a.act[L - 1] + b * ((int64_t)g.cin * g.hin * g.win) : nullptr;
             const float *lw = a.logw[L] + (int64_t)cls * count;
-            const int n = wave_choose<POSTERIOR>(
-                count, lane, dp_device::counter_uniform(a.seed, ctr0),
+            const int n = wave_choose<MODE>(
+                count, lane, draw_uniform<MODE>(a.seed, ctr0),
                 [&](int q) {
                     const int oc = q / hw, p = q - oc * hw, oh = p / g.wout;
                     return prod_value(g, A, oc, oh, p - oh * g.wout) + lw[q];
@@ -185,8 +265,8 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                 for (int e = wave; e < ncur; e += kWaves) {
                     const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
                     const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
-                    const int c = wave_choose<POSTERIOR>(
-                        count, lane, dp_device::counter_uniform(a.seed, ctr + (unsigned)p),
+                    const int c = wave_choose<MODE>(
+                        count, lane, draw_uniform<MODE>(a.seed, ctr + (unsigned)p),
                         [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
                         [&](int n) { return lw[(int64_t)n * hw]; });
                     if (lane == 0) activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
@@ -195,8 +275,8 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                 for (int e = tid; e < ncur; e += kThreads) {
                     const int pk = cur[e], p = pk & 0xffff, oh = p / g.wout, ow = p - oh * g.wout;
                     const float *lw = a.logw[t] + (int64_t)(pk >> 16) * count * hw + p;
-                    const int c = lane_choose<POSTERIOR>(
-                        count, dp_device::counter_uniform(a.seed, ctr + (unsigned)p),
+                    const int c = lane_choose<MODE>(
+                        count, draw_uniform<MODE>(a.seed, ctr + (unsigned)p),
                         [&](int n) { return prod_value(g, A, n, oh, ow) + lw[(int64_t)n * hw]; },
                         [&](int n) { return lw[(int64_t)n * hw]; });
                     activate(g, c, oh, ow, nxt, &td_count[t - 1], cap);
@@ -217,6 +297,10 @@ __global__ __launch_bounds__(kThreads) void dgcspn_topdown_kernel(const TopDownA
                 const float xv = x ? x[f] : NAN;
                 if (xv != xv) {
                     const int64_t po = (int64_t)k * CHW + f;
+                    if (MODE == DPG_MODE_MPE) {
+                        out[f] = a.loc[po];
+                        continue;
+                    }
                     const unsigned long long slot = ctr0 + a.base[L] + 2ull * (unsigned long long)f;
                     const float u1 = dp_device::counter_uniform(a.seed, slot), u2 = dp_device::counter_uniform(a.seed, slot + 1ull);
                     const float z = sqrtf(-2.f * logf(1.f - u1)) * cosf(6.28318530717958647692f * u2);
@@ -241,13 +325,13 @@ extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H,
                                   const int32_t *geom, int32_t classes, const float *x, const int64_t *y,
                                   const float *const *act, const float *const *logw, const float *loc, const float *scale,
                                   uint64_t seed, float *out, int32_t *choice, void *stream) {
-    DPG_REQUIRE(mode == DPG_MODE_PRIOR || mode == DPG_MODE_POSTERIOR, "dpg_dgcspn_topdown: mode %d", mode);
+    DPG_REQUIRE(mode == DPG_MODE_PRIOR || mode == DPG_MODE_POSTERIOR || mode == DPG_MODE_MPE, "dpg_dgcspn_topdown: mode %d", mode);
     DPG_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0 && K > 0 && classes > 0, "dpg_dgcspn_topdown: bad sizes");
     DPG_REQUIRE(logw != nullptr, "dpg_dgcspn_topdown: null table");
     DPG_REQUIRE((int64_t)C * H * W <= (1 << 28), "dpg_dgcspn_topdown: an image of more than 2^28 entries");
     TopDownArgs a{};
     a.B = B; a.C = C; a.H = H; a.W = W; a.K = K; a.L = n_levels; a.classes = classes;
-    a.x = mode == DPG_MODE_POSTERIOR ? x : nullptr;
+    a.x = mode != DPG_MODE_PRIOR ? x : nullptr;
     a.y = y; a.loc = loc; a.scale = scale; a.seed = seed; a.out = out; a.choice = choice;
     if (int rc = parse_geometry("dpg_dgcspn_topdown", n_levels, geom, K, H, W, a.lv)) return rc;
     int64_t cap = 4, slots = 1;
@@ -269,9 +353,9 @@ extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H,
     a.cap = (int)cap;
     if (B == 0) return DPG_OK;
     DPG_REQUIRE(loc && scale && out, "dpg_dgcspn_topdown: null pointer");
-    DPG_REQUIRE(mode == DPG_MODE_PRIOR || act, "dpg_dgcspn_topdown: mode 2 needs the bottom-up activations");
+    DPG_REQUIRE(mode == DPG_MODE_PRIOR || act, "dpg_dgcspn_topdown: modes 2 and 3 need the bottom-up activations");
     for (int t = 0; t < n_levels; ++t) {
-        a.act[t] = mode == DPG_MODE_POSTERIOR ? act[t] : nullptr;
+        a.act[t] = mode != DPG_MODE_PRIOR ? act[t] : nullptr;
         DPG_REQUIRE(mode == DPG_MODE_PRIOR || a.act[t], "dpg_dgcspn_topdown: activations of level %d missing", t);
     }
     for (int t = 1; t <= n_levels; ++t) {
@@ -280,11 +364,14 @@ extern "C" int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H,
     }
     const size_t lds = (size_t)2 * a.cap * sizeof(int);
     const unsigned grid = (unsigned)std::min<int64_t>(B, (int64_t)device_cus() * 8);
-    if (mode == DPG_MODE_POSTERIOR)
-        DPG_LAUNCH("dgcspn_topdown_kernel<true>", dgcspn_topdown_kernel<true>, dim3(grid), dim3(kThreads), lds,
+    if (mode == DPG_MODE_MPE)
+        DPG_LAUNCH("dgcspn_topdown_kernel<mpe>", dgcspn_topdown_kernel<DPG_MODE_MPE>, dim3(grid), dim3(kThreads), lds,
+                   (hipStream_t)stream, a);
+    else if (mode == DPG_MODE_POSTERIOR)
+        DPG_LAUNCH("dgcspn_topdown_kernel<posterior>", dgcspn_topdown_kernel<DPG_MODE_POSTERIOR>, dim3(grid), dim3(kThreads), lds,
                    (hipStream_t)stream, a);
     else
-        DPG_LAUNCH("dgcspn_topdown_kernel<false>", dgcspn_topdown_kernel<false>, dim3(grid), dim3(kThreads), lds,
+        DPG_LAUNCH("dgcspn_topdown_kernel<prior>", dgcspn_topdown_kernel<DPG_MODE_PRIOR>, dim3(grid), dim3(kThreads), lds,
                    (hipStream_t)stream, a);
     return DPG_OK;
 }

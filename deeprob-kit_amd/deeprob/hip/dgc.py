@@ -30,8 +30,9 @@ def product_geometry(layers):
 
 def dgcspn_topdown(mode: int, n_samples: int, in_features, geom, classes: int, x, y, acts, logws, loc: torch.Tensor,
                    scale: torch.Tensor, seed: int, want_choice: bool = False, labels_trusted: bool = False):
-    """``dpg_dgcspn_topdown``: DgcSpn.sample (mode 1) / DgcSpn.sample_conditional (mode 2) top-down in one launch.
-    ``geom``: :func:`product_geometry`; ``acts``: [leaf output, sum layer 1 output, ...] NCHW (mode 2); ``logws``: the
+    """``dpg_dgcspn_topdown``: DgcSpn.sample (mode 1) / DgcSpn.sample_conditional (mode 2) / DgcSpn.mpe_completion (mode 3,
+    which ignores ``seed``) top-down in one launch.
+    ``geom``: :func:`product_geometry`; ``acts``: [leaf output, sum layer 1 output, ...] NCHW (modes 2 and 3); ``logws``: the
     log-softmax weights of the sum layers 1 .. L-1, then of the root.  Returns ``[B, C, H, W]`` (and the ``[B, 1 + H W]``
     int32 choices when asked).  A label outside ``[0, classes)`` raises ``ValueError`` (``labels_trusted``: the caller drew
     them itself, no check and no read-back)."""
@@ -50,7 +51,9 @@ def dgcspn_topdown(mode: int, n_samples: int, in_features, geom, classes: int, x
         raise ValueError('dgcspn_topdown: %d weight tensors for %d levels' % (len(logws), L))
     act_arr = (ctypes.c_void_p * L)()
     xd = None
-    if mode == DPG_MODE_POSTERIOR:
+    if mode in (DPG_MODE_POSTERIOR, DPG_MODE_MPE):
+        if acts is None:
+            raise ValueError('dgcspn_topdown: mode %d needs the bottom-up activations' % mode)
         if len(acts) != L:
             raise ValueError('dgcspn_topdown: %d activation tensors for %d levels' % (len(acts), L))
         xd = dev(x, 'x', (B, C, H, W))

@@ -305,6 +305,52 @@ class DgcSpn(ProbabilisticModel):
                                   ops.draw_seed() if seed is None else int(seed), labels_trusted=drawn)
 
     @torch.no_grad()
+    def mpe_completion(self, x: torch.Tensor, y: Optional[torch.Tensor] = None, return_choice: bool = False):
+        """The NaN entries of ``x [B,C,H,W]`` filled with the leaf modes of the induced tree that is chosen greedily from the
+        sum-pass values; the observed entries are returned as they are.  The bottom-up pass of ``sample_conditional`` (the
+        leaf map and every sum layer's output under the evidence), then one top-down launch (mode 3 of
+        csrc/dgc/dgcspn_topdown.hip) that takes, at the root and at every reached sum node, the input with the largest
+        weight * value under the evidence -- the lowest index among equal ones, the largest weight where no input is
+        possible -- and at every reached pixel the ``loc`` of the chosen component.  This is the semantics of ``RatSpn.mpe``
+        and of the reference's top-down MPE of RAT-SPNs; it is not a global MAP of p(x_missing | x_observed), which a
+        max-product bottom-up pass would need.  The reference has no counterpart for DGC-SPNs.
+
+        Against the other completions: ``mpe`` is the reference's gradient form and returns posterior means (for several
+        classes, the classes' means added up); ``expectation`` returns the exact posterior mean, a blend of all components;
+        ``sample_conditional`` returns one random draw.  This one is deterministic and sharp: every filled pixel is one
+        component's location.
+
+        Without labels a model with several classes descends from the class with the largest root output for the row (the
+        first of equal ones; a row with a NaN root output, or with every root output ``-inf``, takes class 0); a model with
+        one root ignores ``y``; a label outside ``[0, out_classes)`` raises ``ValueError``.  A pixel outside every scope is
+        returned as given.  ``return_choice``: also the ``[B, 1 + H*W]`` int32 choices, the root's input index and then the
+        component per pixel (-1 for a pixel out of scope)."""
+        from deeprob import hip
+        from deeprob.hip import dgc, ops, ops_spatial
+        device = self._check_topdown('mpe_completion')
+        x = ops.require_device_f32(x, 'x')
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.in_features):
+            raise ValueError("expected inputs [B, {}], got {}".format(tuple(self.in_features), tuple(x.shape)))
+        if self.out_classes == 1 or x.shape[0] == 0:
+            y = None
+        elif y is not None:
+            # (a wrong label is reported before the bottom-up pass is spent on the batch)
+            y = hip.require_labels('mpe_completion', y, x.shape[0], self.out_classes, device)
+        acts = self._upward_for_sampling(x)
+        if self.out_classes > 1 and x.shape[0] > 0 and y is None:
+            top = ops_spatial.spatial_prodroot(acts[-1], self.layers[-1], self.root_layer.weight, self.root_layer._ws2)
+            if top is None:
+                top = self.root_layer(self.layers[-1](acts[-1]))
+            # the first maximum; a NaN output equals nothing, so such a row finds none and takes class 0
+            index = torch.arange(self.out_classes, device=top.device).expand_as(top)
+            first = torch.where(top == top.max(dim=1, keepdim=True).values, index, self.out_classes).min(dim=1).values
+            y = torch.where(first < self.out_classes, first, 0)
+        geom = dgc.product_geometry(self._product_layers())
+        return dgc.dgcspn_topdown(dgc.DPG_MODE_MPE, x.shape[0], self.in_features, geom, self.out_classes, x, y, acts,
+                                  self._topdown_logw(), self.base_layer.loc, self.base_layer.scale, 0,
+                                  want_choice=return_choice, labels_trusted=True)
+
+    @torch.no_grad()
     def posterior_moments(self, x: torch.Tensor, y: Optional[torch.Tensor] = None,
                           want_var: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """Exact ``(E[x | e, y], Var[x | e, y])`` of every NaN entry of ``x [B,C,H,W]`` given the image's observed entries

@@ -1,6 +1,6 @@
 /*
  * deeprob_dgc.h -- C ABI of libdeeprob_dgc.so (gfx950 / MI355X): the top-down pass of a DGC-SPN
- * (deeprob.spn.models.DgcSpn.sample / sample_conditional) in one launch.
+ * (deeprob.spn.models.DgcSpn.sample / sample_conditional / mpe_completion) in one launch.
  *
  * The reference raises in DgcSpn.sample (deeprob/spn/models/dgcspn.py) and has no conditional
  * sampler.  The pass is defined, statement for statement, at the top of
@@ -67,6 +67,7 @@ extern "C" {
 #define DPG_MAX_LEVELS 12   /* most product levels: ceil(log2(H)) + 1                              */
 #define DPG_MODE_PRIOR 1     /* every activation is log 1: the weights alone, `act` and `x` unused  */
 #define DPG_MODE_POSTERIOR 2 /* scores from the activations of a bottom-up pass under `x`           */
+#define DPG_MODE_MPE 3       /* mode 2's scores, selected from where mode 2 draws: max-product       */
 
 const char *dpg_last_error(void);
 int dpg_abi_version(void);
@@ -81,7 +82,18 @@ int dpg_abi_version(void);
  *      or NaN.
  * choice: optional [B, 1 + H * W] int32: the root's input index, then per pixel the leaf component
  *      drawn, -1 for a pixel out of scope.
- * A row's output depends on (seed, row index, y[row]) and the row's evidence only. */
+ * A row's output depends on (seed, row index, y[row]) and the row's evidence only.
+ *
+ * Mode 3 (DPG_MODE_MPE) takes the arguments of mode 2 (x may be NULL, act is required) and selects
+ * where mode 2 draws; `seed` is ignored and no uniform is formed.  At the root and at every active
+ * position of every sum layer, with mode 2's fp32 scores s(n) = prod_value(n) + logw(n),
+ * prod_value = ((v0 + v1) + v2) + v3, and their NaN-sticky maximum m: if m > -inf the first n in index
+ * order with s(n) == m; otherwise (m is -inf or NaN) the first n in index order that maximises
+ * logw(n), a NaN weight never over a number.  Ties always go to the lowest index.  A NaN entry of a
+ * pixel reached with component k is loc[k, c, h, w] bit for bit (the mode of a Gaussian; `scale` is
+ * not read); observed entries, pixels out of scope and `choice` are as in mode 2.  The result is the
+ * leaf modes of the induced tree chosen greedily from the sum-pass activations -- not a global MAP.
+ * A row's output depends on y[row] and the row's evidence only. */
 int dpg_dgcspn_topdown(int32_t mode, int64_t B, int32_t C, int32_t H, int32_t W, int32_t K, int32_t n_levels,
                        const int32_t *geom, int32_t classes, const float *x, const int64_t *y,
                        const float *const *act, const float *const *logw, const float *loc, const float *scale,
