@@ -14,10 +14,8 @@
 namespace {
 
 using dpc_detail::Leaf;
-using dpc_detail::leaf_gather;
 using dpc_detail::leaf_messages;
 using dpc_detail::leaf_pull;
-using dpc_detail::leaf_root;
 using dp_device::counter_uniform;
 
 typedef unsigned long long u64;
@@ -98,20 +96,12 @@ __global__ __launch_bounds__(kRowThreads) void query_kernel(const QueryArgs a) {
     const Leaf f = {D, nullptr, a.bfs, a.parent, a.child_off, a.child_idx, a.params};
 
     if (MODE == kLogLikelihood) {
-        double s = 0.0;
-        if (leaf_gather<false>(f, q, B, s)) {
-            a.out[r] = (float)s;
-            return;
-        }
+        a.out[r] = dpc_detail::tree_log_likelihood(f, q, B, t, B);
+        return;
     }
 
     // upward: t_j of every node but the root, children before parents
     leaf_messages<MODE == kMpe, false>(f, q, B, t);
-
-    if (MODE == kLogLikelihood) {
-        a.out[r] = leaf_root<false, false>(f, q, B, t);
-        return;
-    }
 
     // downward: parents before children.  Once j has its value, t_j is dead (only j's parent pulled it, and that came
     // first): slot 2 j keeps the value for j's children.
@@ -165,7 +155,7 @@ extern "C" {
 
 const char *dpc_last_error(void) { return dpc_detail::g_error; }
 
-int dpc_abi_version(void) { return 4; }
+int dpc_abi_version(void) { return 5; }
 
 int dpc_pack_bits(const float *x, int64_t n, int d, uint64_t *planes, void *stream) {
     DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pack_bits: d = %d is outside 1..%d", d, DPC_MAX_D);

@@ -177,14 +177,16 @@ __device__ __forceinline__ void leaf_pull(const Leaf &f, const float *t, int64_t
 // the upward pass of dpc_clt_log_likelihood (R = lse) or of dpc_clt_mpe (MAX: R = max) over the tree's columns, in two
 // parts: the messages t_j of every node but the root, children before parents, and the root's value, which is the log
 // likelihood (a query that only goes back down never asks for it).  COLS as in leaf_gather.
+// TB: the stride of the state t, where it is not the stride B of the codes (dpc_mix_log_likelihood gathers its rows
+// through an index: the codes keep the stride of the whole batch, the state has that of the rows evaluated).
 template <bool MAX, bool COLS = true>
-__device__ void leaf_messages(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+__device__ void leaf_messages(const Leaf &f, const uint8_t *q, int64_t B, float *t, int64_t TB) {
     for (int p = f.d - 1; p >= 1; --p) {
         const int j = f.bfs[p];
         const float *pj = f.params + j * 4;
         const int cj = q[(int64_t)(COLS ? f.col[j] : j) * B];
         float m0, m1;
-        leaf_pull(f, t, B, j, m0, m1);
+        leaf_pull(f, t, TB, j, m0, m1);
         float t0, t1;
         if (cj != DPC_MISSING) {
             const float m = cj ? m1 : m0;
@@ -197,26 +199,47 @@ __device__ void leaf_messages(const Leaf &f, const uint8_t *q, int64_t B, float 
             t0 = lse2(pj[0] + m0, pj[1] + m1);
             t1 = lse2(pj[2] + m0, pj[3] + m1);
         }
-        t[2 * (int64_t)j * B] = t0;
-        t[(2 * (int64_t)j + 1) * B] = t1;
+        t[2 * (int64_t)j * TB] = t0;
+        t[(2 * (int64_t)j + 1) * TB] = t1;
     }
 }
 
 template <bool MAX, bool COLS = true>
-__device__ __forceinline__ float leaf_root(const Leaf &f, const uint8_t *q, int64_t B, const float *t) {
+__device__ __forceinline__ void leaf_messages(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
+    leaf_messages<MAX, COLS>(f, q, B, t, B);
+}
+
+template <bool MAX, bool COLS = true>
+__device__ __forceinline__ float leaf_root(const Leaf &f, const uint8_t *q, int64_t B, const float *t, int64_t TB) {
     const int j = f.bfs[0];
     const float *pj = f.params + j * 4;
     const int cj = q[(int64_t)(COLS ? f.col[j] : j) * B];
     float m0, m1;
-    leaf_pull(f, t, B, j, m0, m1);
+    leaf_pull(f, t, TB, j, m0, m1);
     if (cj != DPC_MISSING) return pj[cj] + (cj ? m1 : m0);
     return MAX ? fmaxf(pj[0] + m0, pj[1] + m1) : lse2(pj[0] + m0, pj[1] + m1);
+}
+
+template <bool MAX, bool COLS = true>
+__device__ __forceinline__ float leaf_root(const Leaf &f, const uint8_t *q, int64_t B, const float *t) {
+    return leaf_root<MAX, COLS>(f, q, B, t, B);
 }
 
 template <bool MAX, bool COLS = true>
 __device__ __forceinline__ float leaf_upward(const Leaf &f, const uint8_t *q, int64_t B, float *t) {
     leaf_messages<MAX, COLS>(f, q, B, t);
     return leaf_root<MAX, COLS>(f, q, B, t);
+}
+
+// dpc_clt_log_likelihood for one row of a stand-alone tree, which dpc_mix_log_likelihood evaluates per component: the
+// gather path for a complete row, else the pulled upward pass with R = lse (state t of stride TB).  t may be null where
+// the caller has no state to give (dpc_mix_log_likelihood without `work`): a row with NaN then gets NaN and writes nothing.
+__device__ __forceinline__ float tree_log_likelihood(const Leaf &f, const uint8_t *q, int64_t B, float *t, int64_t TB) {
+    double s = 0.0;
+    if (leaf_gather<false>(f, q, B, s)) return (float)s;
+    if (!t) return NAN;
+    leaf_messages<false, false>(f, q, B, t, TB);
+    return leaf_root<false, false>(f, q, B, t, TB);
 }
 
 // the downward pass of the posterior marginals (dpc_mar_*), after leaf_messages<false>: in `bfs` order the normalised log

@@ -34,6 +34,18 @@ def _rows(x: torch.Tensor, name: str) -> torch.Tensor:
     return x
 
 
+def rows_on_device(x, name: str) -> torch.Tensor:
+    """``x`` as a float32 tensor on a HIP device, under the input rules of the models (``name``: what the model calls itself
+    in a message): numpy goes to the current device, a device tensor stays where it is, a CPU tensor or a missing library
+    raises ``HipError``."""
+    load_library()
+    if isinstance(x, torch.Tensor):
+        return hip.require_device_f32(x, 'data')
+    if not torch.cuda.is_available():
+        raise HipError("{} needs a HIP device (there is no CPU fallback)".format(name))
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.device('cuda', torch.cuda.current_device()))
+
+
 def run_on_device(model, name: str, op, x, *args):
     """``op(model._on_device(device), x on the device, *args)`` under the input rules of ``BinaryCLT`` and ``BinaryCNet``
     (``model``: one of them, ``name``: what it calls itself in a message): numpy in, numpy out through the current device;
@@ -182,3 +194,134 @@ def marginals(tree: DeviceTree, x: torch.Tensor) -> torch.Tensor:
     """``[B, D]`` float32: ``x`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)``, exact
     (``dpc_mar_clt``); NaN where the row's evidence has probability zero."""
     return _query(tree, x, 'marginals')
+
+
+# ---- mixtures of trees (the last section of the header) --------------------------------------------------------------------
+#: the ``dpc_abi_version()`` that has the ``dpc_mix_*`` entry points (``ABI_VERSION``, what the module needs to load, stays)
+MIX_ABI_VERSION = 5
+
+
+def _mix_library():
+    lib = load_library()
+    version = lib.dpc_abi_version()
+    if version < MIX_ABI_VERSION:
+        raise HipError("libdeeprob_clt.so at {} has ABI version {}, mixtures of trees need {} -- rebuild it with `make -C "
+                       "deeprob-kit_amd/csrc` (or __graft_entry__.build())".format(BINDING.lib_path, version, MIX_ABI_VERSION))
+    return lib
+
+
+class DeviceMixture:
+    """The tables of ``K`` trees over the same ``D`` positions, stacked as ``dpc_mix_log_likelihood`` takes them, and the
+    float32 log weights ``logw`` ``[K]``, on ``device`` (one host-to-device copy).  ``trees``: ``(bfs, parent, params)``
+    per component.  :meth:`update` replaces the parameters and the weights of the same structures in one copy."""
+
+    def __init__(self, trees, logw, device):
+        trees = [check_tree(*t) for t in trees]
+        k = len(trees)
+        if not 1 <= k <= DPC_MIX_MAX_K:
+            raise HipError("a mixture of {} components is outside 1..{} (DPC_MIX_MAX_K)".format(k, DPC_MIX_MAX_K))
+        d = len(trees[0][1])
+        if any(len(t[1]) != d for t in trees):
+            raise ValueError("the components of a mixture must have the same number of variables")
+        logw = np.ascontiguousarray(logw, np.float32)
+        if logw.shape != (k,):
+            raise ValueError("expected {} log weights, got {}".format(k, logw.shape))
+        csr = [children_csr(bfs, parent) for bfs, parent, _ in trees]
+        ints = np.concatenate([np.concatenate([np.asarray(t[0], np.int32) for t in trees]),
+                               np.concatenate([np.asarray(t[1], np.int32) for t in trees]),
+                               np.concatenate([off for off, _ in csr]), np.concatenate([idx for _, idx in csr])])
+        floats = np.concatenate([np.concatenate([t[2].reshape(-1) for t in trees]), logw])
+        buf = torch.from_numpy(np.concatenate([ints.view(np.uint8), floats.view(np.uint8)])).to(device)
+        self.k, self.d, self.device, self._buf = k, d, buf.device, buf
+        ints_d = buf[:4 * len(ints)].view(torch.int32)
+        self.bfs, self.parent = ints_d[:k * d], ints_d[k * d:2 * k * d]
+        self.child_off, self.child_idx = ints_d[2 * k * d:2 * k * d + k * (d + 1)], ints_d[2 * k * d + k * (d + 1):]
+        self._floats = buf[4 * len(ints):].view(torch.float32)
+        self.params, self.logw = self._floats[:4 * k * d], self._floats[4 * k * d:]
+
+    def update(self, params, logw):
+        """New ``params`` ``[K, D, 2, 2]`` and ``logw`` ``[K]`` for the same trees: one copy."""
+        floats = np.concatenate([np.ascontiguousarray(params, np.float32).reshape(-1), np.ascontiguousarray(logw, np.float32)])
+        if floats.shape != (self._floats.numel(),):
+            raise ValueError("expected params [{}, {}, 2, 2] and {} log weights".format(self.k, self.d, self.k))
+        self._floats.copy_(torch.from_numpy(floats), non_blocking=False)
+
+    def pointers(self):
+        return (self.bfs.data_ptr(), self.parent.data_ptr(), self.params.data_ptr(), self.child_off.data_ptr(),
+                self.child_idx.data_ptr() if self.d > 1 else None, self.logw.data_ptr())
+
+
+def _mix_batch(mix: DeviceMixture, codes: torch.Tensor, rows):
+    """``(b, nb, the pointer of rows or None)`` of a launch over ``codes`` ``[D, b]`` through the batch index ``rows``."""
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[0] != mix.d or not codes.is_contiguous():
+        raise ValueError("expected codes as [{}, B] uint8 (pack_query), got {} {}".format(mix.d, tuple(codes.shape), codes.dtype))
+    if codes.device != mix.device:
+        raise HipError("the codes live on '{}', the mixture on '{}'".format(codes.device, mix.device))
+    b = codes.shape[1]
+    if rows is None:
+        return b, b, None
+    if rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != codes.device or not rows.is_contiguous():
+        raise ValueError("expected rows as a contiguous int32 vector on '{}'".format(codes.device))
+    return b, rows.shape[0], rows.data_ptr()
+
+
+def mixture_codes_log_likelihood(mix: DeviceMixture, codes: torch.Tensor, rows=None, work: torch.Tensor = None,
+                                 complete: bool = False):
+    """``(ll [nb], comp_ll [nb, K], resp [nb, K])`` float32 of the rows ``rows`` (int32 on the device; None: all, in order)
+    of ``codes`` ``[D, b]`` from :func:`pack_query`: ONE ``dpc_mix_log_likelihood``.  ``work``: at least ``K * 2 * D * nb``
+    float32 of scratch to reuse, allocated when None.  ``complete``: the caller knows that no row holds NaN (EM has checked
+    it): no scratch is allocated or passed, and a row with NaN would get NaN."""
+    lib = _mix_library()
+    b, nb, rows_ptr = _mix_batch(mix, codes, rows)
+    dev = codes.device
+    work_ptr = None
+    if not complete:
+        need = mix.k * 2 * mix.d * nb
+        if work is None:
+            work = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+        assert work.dtype == torch.float32 and work.device == dev and work.numel() >= need and work.is_contiguous()
+        work_ptr = work.data_ptr()
+    comp_ll = torch.empty((nb, mix.k), dtype=torch.float32, device=dev)
+    ll = torch.empty(nb, dtype=torch.float32, device=dev)
+    resp = torch.empty((nb, mix.k), dtype=torch.float32, device=dev)
+    call(lib.dpc_mix_log_likelihood, codes.data_ptr(), b, mix.d, rows_ptr, nb, mix.k, *mix.pointers(), work_ptr,
+         comp_ll.data_ptr(), ll.data_ptr(), resp.data_ptr(), hip.stream_ptr(dev))
+    return ll, comp_ll, resp
+
+
+def mixture_log_likelihood(mix: DeviceMixture, x: torch.Tensor, rows=None, want_resp: bool = False):
+    """``ll`` ``[nb]`` float32, the log likelihood of the rows ``rows`` (None: all) of ``x`` ``[B, D]`` under the mixture,
+    NaN entries marginalised; with ``want_resp`` ``(ll, comp_ll [nb, K], resp [nb, K])``.  With a row index it is one
+    launch; without, a long batch is evaluated in pieces of ``WORK_FLOATS / (2 D K)`` rows."""
+    x = _rows(x, 'x')
+    if x.shape[1] != mix.d:
+        raise ValueError("expected inputs [B, {}], got {}".format(mix.d, tuple(x.shape)))
+    if x.device != mix.device:
+        raise HipError("x lives on '{}', the mixture on '{}'".format(x.device, mix.device))
+    if rows is not None:
+        out = mixture_codes_log_likelihood(mix, pack_query(x), rows)
+        return out if want_resp else out[0]
+    b = x.shape[0]
+    step = query_rows(mix.d * mix.k)
+    work = torch.empty(mix.k * 2 * mix.d * min(b, step), dtype=torch.float32, device=x.device)
+    pieces = [mixture_codes_log_likelihood(mix, pack_query(x[r0:r0 + step]), None, work) for r0 in range(0, b, step)]
+    out = pieces[0] if len(pieces) == 1 else tuple(torch.cat(p) for p in zip(*pieces))
+    return out if want_resp else out[0]
+
+
+def mixture_em_stats(mix: DeviceMixture, codes: torch.Tensor, rows, resp: torch.Tensor) -> torch.Tensor:
+    """``stats`` ``[K, 1 + 2 D]`` float64 (``dpc_mix_em_stats``): per component the sum of the responsibilities ``resp``
+    ``[nb, K]`` over the batch ``rows`` of ``codes``, their sum where ``x_j = 1`` and where ``x_j = x_parent(j) = 1``, in
+    the fixed order of the header."""
+    lib = _mix_library()
+    b, nb, rows_ptr = _mix_batch(mix, codes, rows)
+    dev = codes.device
+    if resp.dtype != torch.float32 or tuple(resp.shape) != (nb, mix.k) or resp.device != dev or not resp.is_contiguous():
+        raise ValueError("expected resp as [{}, {}] float32 on '{}'".format(nb, mix.k, dev))
+    width = 1 + 2 * mix.d
+    n_chunks = (nb + DPC_MIX_CHUNK - 1) // DPC_MIX_CHUNK
+    part = torch.empty((max(n_chunks, 1), mix.k, width), dtype=torch.float64, device=dev)
+    stats = torch.empty((mix.k, width), dtype=torch.float64, device=dev)
+    call(lib.dpc_mix_em_stats, codes.data_ptr(), b, mix.d, rows_ptr, nb, mix.k, resp.data_ptr(), mix.parent.data_ptr(),
+         part.data_ptr(), stats.data_ptr(), hip.stream_ptr(dev))
+    return stats

@@ -39,7 +39,8 @@ def expectation_maximization(
     ``verbose=False`` the loop never waits for the device.  Two calls with the same arguments give bitwise identical
     parameters.  Unlike the reference (which lets NaN flow into the parameters), data containing NaN is an error.
 
-    :param root: The SPN (as loaded by ``deeprob.spn.structure.io.load_spn_json``); updated in place.
+    :param root: The SPN (as loaded by ``deeprob.spn.structure.io.load_spn_json``); updated in place.  A
+                 ``deeprob.spn.structure.BinaryCLTMixture`` is handed to its own ``em`` with the same arguments.
     :param data: The data to use to learn the parameters ``[n_samples, >= n_features]`` (numpy, evaluated on the
                  current HIP device, or a tensor on a HIP device).
     :param num_iter: The number of iterations.
@@ -52,6 +53,10 @@ def expectation_maximization(
     :raises ValueError: If a parameter is out of domain, or the data contains NaN.
     :raises NotImplementedError: If the SPN has a Uniform leaf (as the reference); nothing is modified then.
     """
+    from deeprob.spn.structure.cltmix import BinaryCLTMixture
+    if isinstance(root, BinaryCLTMixture):      # a mixture of Chow-Liu trees trains itself, with the CPTs of a tree tied
+        return root.em(data, num_iter=num_iter, batch_perc=batch_perc, step_size=step_size, random_init=random_init,
+                       random_state=random_state, verbose=verbose)
     if num_iter <= 0:
         raise ValueError("The number of iterations must be positive")
     if batch_perc <= 0.0 or batch_perc >= 1.0:

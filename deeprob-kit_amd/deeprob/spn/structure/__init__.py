@@ -1,0 +1,1 @@
+from .cltmix import BinaryCLTMixture

@@ -16,8 +16,10 @@ it only fixes the order of float32 additions.  ``sample`` draws from a counter-b
 ``FlatSpn`` has no multivariate leaf, so the class is never a node of a node-graph SPN here: ``learn_spn`` with
 ``learn_leaf=deeprob.spn.learning.leaf.learn_binary_clt`` (the function, by identity; the string ``'binary-clt'`` still
 raises) fits one tree per multivariate leaf task from counts taken on the learner's own data layout (``fit_counts``) and
-hangs its ``to_pc_nodes()`` expansion into the circuit.  The reference's ``em_init`` / ``em_step`` (tied CPTs) are not
-built: EM on such a circuit updates the expansion's sum weights freely.
+hangs its ``to_pc_nodes()`` expansion into the circuit; EM on such a circuit updates the expansion's sum weights freely.
+The reference's ``em_init`` / ``em_step`` keep the CPTs of a tree tied: ``em_step`` takes the weighted counts of its rows
+from one ``dpc_mix_em_stats`` launch and applies the reference's float32 update (:func:`em_update`) on the host;
+``deeprob.spn.structure.cltmix.BinaryCLTMixture`` trains a mixture of trees with them.
 """
 from typing import List, Optional, Union
 
@@ -41,6 +43,38 @@ def _post_order(root):
             stack.append((node, True))
             stack.extend((c, False) for c in node.get_children())
     return out
+
+
+def em_update(params: np.ndarray, tree: np.ndarray, root: int, stats: np.ndarray, step_size: float) -> np.ndarray:
+    """The tied-CPT EM update of one tree (cltree.py:131-155) in float32 and in the reference's order, as a pure function:
+    the new log CPTs ``[D, 2, 2]`` from the current ``params``, the predecessors ``tree``, the position ``root`` and the
+    tree's row ``stats`` ``[1 + 2 D]`` of ``dpc_mix_em_stats`` (the sum of the responsibilities, their sums where
+    ``x_j = 1`` and where ``x_j = x_parent(j) = 1``), which stand where the reference sums ``stats * data`` itself."""
+    f32 = np.float32
+    params, tree, stats = np.asarray(params, f32), np.asarray(tree), np.asarray(stats)
+    d = len(tree)
+    smooth = f32(np.finfo(np.float16).eps)          # 2^-10: the reference smooths the weighted counts this lightly
+    mass = f32(stats[0])                            # the batch's responsibility for this tree
+    on = stats[1:1 + d].astype(f32)                 # ... where x_j = 1
+    on_both = stats[1 + d:1 + 2 * d].astype(f32)    # ... where x_j = 1 and x_parent(j) = 1
+
+    # P(x_j = 1) and its complement, column 1 first
+    p_on = (on + f32(2) * smooth) / (mass + f32(4) * smooth)
+    marginal = np.stack([f32(1) - p_on, p_on], axis=1)
+
+    # fresh[j, l, 1] = P(x_j = 1 | x_parent(j) = l): the count of (x_j = 1, x_parent = l) over the parent's smoothed mass;
+    # the entry of the root's row is indexed with -1 and overwritten below
+    count = np.stack([on - on_both, on_both], axis=1)
+    fresh = np.empty((d, 2, 2), f32)
+    fresh[:, :, 1] = (count + smooth) / (mass * marginal[tree] + f32(4) * smooth)
+    fresh[:, :, 0] = f32(1) - fresh[:, :, 1]
+    fresh[root] = marginal[root]                    # both rows of the root hold its marginal
+
+    # a step of step_size from the current tables towards the fresh ones, in probability space, rows summing to 1 again
+    blend = f32(1.0 - step_size) * np.exp(params) + f32(step_size) * fresh
+    blend /= blend.sum(axis=2, keepdims=True)
+    with np.errstate(divide='ignore'):
+        return np.log(blend)
 
 
 class BinaryCLT(Leaf):
@@ -151,6 +185,34 @@ class BinaryCLT(Leaf):
             self.bfs, self.tree = maximum_spanning_tree(self.root, compute_mutual_information(priors, joints))
         with np.errstate(divide='ignore'):      # (alpha = 0 can leave a zero probability)
             self.params = np.log(self.compute_clt_parameters(self.bfs, self.tree, priors, joints))
+
+    def em_init(self, random_state: np.random.RandomState):
+        """Random CPTs for EM (cltree.py:117-125): ``rand(len(scope), 2)``, the two rows of the root made equal."""
+        if self.tree is None:
+            raise ValueError("The CLT's structure must be already initialized")
+        p_on = random_state.rand(len(self.scope), 2)          # P(x_j = 1 | parent value l), one draw per (j, l)
+        p_on[self.root, 0] = p_on[self.root, 1]
+        self.params = np.log(np.stack([1.0 - p_on, p_on], axis=2).astype(np.float32))
+
+    def em_step(self, stats, data, step_size: float):
+        """One batch EM step with tied CPTs (cltree.py:127-155).  ``stats`` ``[B]``: the responsibility of the tree for
+        every row of ``data`` ``[B, len(scope)]`` (complete 0 / 1 rows; both numpy or both tensors on one HIP device).  The
+        weighted counts are one ``dpc_mix_em_stats`` launch with one component, the update is :func:`em_update`."""
+        if self.tree is None:
+            raise ValueError("The CLT's structure must be already initialized")
+        if self.params is None:
+            raise ValueError("The CLT's structure and parameters must be already initialized")
+        import torch
+        from deeprob.hip import clt
+        if len(data.shape) != 2 or data.shape[1] != len(self.scope) or tuple(stats.shape) not in ((data.shape[0],), (data.shape[0], 1)):
+            raise ValueError("expected data [B, {}] and stats [B], got {} and {}".format(len(self.scope), tuple(data.shape),
+                                                                                      tuple(stats.shape)))
+        x, resp = clt.rows_on_device(data, 'BinaryCLT'), clt.rows_on_device(stats, 'BinaryCLT').reshape(-1, 1)
+        if bool(torch.isnan(x).any()):
+            raise ValueError("The data contains NaN: EM needs complete rows")
+        mix = clt.DeviceMixture([(self.bfs, self.tree, self.params)], [0.0], x.device)
+        row = clt.mixture_em_stats(mix, clt.pack_query(x), None, resp).cpu().numpy()[0]
+        self.params = em_update(self.params, self.tree, self.root, row, step_size)
 
     # ---- queries -----------------------------------------------------------------------------------------------------
     def _on_device(self, device):

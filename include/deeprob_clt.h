@@ -328,6 +328,47 @@ int dpc_xpc_partition(const uint64_t *planes, int64_t n_words, int64_t n, int d,
                       const int32_t *child_of_code, const int32_t *out_off, int n_tasks, int n_chunks, int32_t *rows_out,
                       void *stream);
 
+/* ---- Mixtures of Chow-Liu trees (deeprob.spn.structure.cltmix.BinaryCLTMixture): likelihoods, responsibilities and
+ * the sufficient statistics of tied-CPT batch EM (reference spn/structure/cltree.py:117-155, node.py:91-111), for all
+ * n_comp components in one call.  ABI version 5.
+ *
+ * The n_comp trees are over the same d positions and are STACKED: bfs[n_comp][d], parent[n_comp][d],
+ * params[n_comp][d][2][2], child_off[n_comp][d + 1], child_idx[n_comp][d - 1], each slice the tables of one tree as
+ * above (trusted).  codes: [d, b] from dpc_pack_query.  rows: [nb] int32 or null: position i of the batch is row rows[i]
+ * of `codes` (null: nb = b must hold and position i is row i).  A row index outside 0 .. b-1 reads nothing: the
+ * likelihood outputs of that position are NaN, and it adds nothing to the statistics. */
+#define DPC_MIX_MAX_K 64    /* the largest number of components                                                    */
+#define DPC_MIX_CHUNK 1024  /* batch positions per work-group of dpc_mix_em_stats, and per chunk sum of its order  */
+
+/* comp_ll[i][k] = the value dpc_clt_log_likelihood gives tree k on that row, bit for bit (the same device function:
+ * the float64 gather for a complete row, the pulled upward pass for a row with NaN).  Then, in float32,
+ *   a_k = logw[k] + comp_ll[i][k];  M = max over k;  L = logf(sum over k INCREASING FROM 0.0f of expf(a_k - M));
+ *   ll[i] = M + L,  -inf when M = -inf;
+ *   resp[i][k] = expf((a_k - M) - L), which is expf(a_k - ll[i]) without the rounding of M + L (half an ulp of |ll|
+ *                would otherwise be a relative error of every responsibility);  0 when ll[i] = -inf (the row has no
+ *                responsibility).
+ * comp_ll, resp: [nb, n_comp] float32; ll: [nb] float32; logw: [n_comp] float32 (-inf allowed).
+ * work: [n_comp * 2 * d * nb] float32 scratch: the state of the upward pass of component k at position i.  Only a row with
+ * NaN touches it.  work may be NULL when the caller knows that every row is complete (EM checks it on the host): a row
+ * with NaN then gets NaN in comp_ll, ll and resp, and nothing is read or written through work. */
+int dpc_mix_log_likelihood(const uint8_t *codes, int64_t b, int d, const int32_t *rows, int64_t nb, int n_comp,
+                           const int32_t *bfs, const int32_t *parent, const float *params, const int32_t *child_off,
+                           const int32_t *child_idx, const float *logw, float *work, float *comp_ll, float *ll,
+                           float *resp, void *stream);
+
+/* stats[k][0] = sum over i of g_ik;  stats[k][1 + j] = sum of g_ik x_ij;  stats[k][1 + d + j] = sum of
+ * g_ik x_ij x_i,parent[k][j] (0.0 at the root, and where parent[k][j] is outside 0 .. d-1), with g_ik = (double)resp[i][k]
+ * and x = 1 where the code is 1, else 0 (DPC_MISSING counts as 0).  Every term is g_ik or 0.0, exact.  Order of every
+ * float64 sum: the batch is cut into chunks of DPC_MIX_CHUNK positions; in a chunk, partial l (l < 256) takes the
+ * positions l, l + 256, ... of the chunk in order, starting from 0.0; the chunk sum adds the 256 partials in order of
+ * l, starting from partial 0; stats adds the chunk sums in increasing chunk order, starting from chunk 0.  The grid
+ * has no part in it: a second call gives the same bits.
+ * resp: [nb, n_comp] float32; parent: [n_comp, d] int32; stats: [n_comp, 1 + 2 d] float64;
+ * part: [n_chunks, n_comp, 1 + 2 d] float64 scratch (the chunk sums), n_chunks = (nb + DPC_MIX_CHUNK - 1) / DPC_MIX_CHUNK.
+ * nb = 0 gives stats = 0. */
+int dpc_mix_em_stats(const uint8_t *codes, int64_t b, int d, const int32_t *rows, int64_t nb, int n_comp,
+                     const float *resp, const int32_t *parent, double *part, double *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
