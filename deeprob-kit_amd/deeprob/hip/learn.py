@@ -268,6 +268,19 @@ def column_moments(data: DeviceData, row_index, item_col, item_row_off, item_n) 
     return moments
 
 
+def _sorted_items(data: DeviceData, row_index, t, n_items: int, total: int) -> torch.Tensor:
+    """The values of all items of the tables ``t`` (``col``, ``off``, ``n``, ``out``), item major, each item's in
+    non-decreasing order: gathered and sorted on the device with ``torch.sort`` (by value, then stably by item); no row
+    is sorted on the host."""
+    item_of = torch.repeat_interleave(torch.arange(n_items, device=data.device), t['n'].long(), output_size=total)
+    pos = torch.arange(total, device=data.device) - t['out'][item_of]
+    rows = row_index[t['off'][item_of] + pos].long()
+    values = data.x[t['col'][item_of].long() * data.n_rows + rows]
+    by_value, order = torch.sort(values, stable=True)
+    _, by_item = torch.sort(item_of[order], stable=True)
+    return by_value[by_item].contiguous()
+
+
 def ecdf_ranks(data: DeviceData, row_index, item_col, item_row_off, item_n):
     """``(ranks, out_off)``: the int32 "max" ranks of every item, item i at ``ranks[out_off[i] : out_off[i] + item_n[i]]``
     in segment order (``dpl_ecdf_ranks``).  The values of all items are gathered and sorted on the device with
@@ -279,13 +292,7 @@ def ecdf_ranks(data: DeviceData, row_index, item_col, item_row_off, item_n):
     total = int(out_off[-1])
     block_item, block_row0 = _row_blocks(item_n)
     t = _items(data.device, item_col, item_row_off, item_n, out=out_off[:-1].copy(), bi=block_item, br=block_row0)
-    item_of = torch.repeat_interleave(torch.arange(n_items, device=data.device), t['n'].long(), output_size=total)
-    pos = torch.arange(total, device=data.device) - t['out'][item_of]
-    rows = row_index[t['off'][item_of] + pos].long()
-    values = data.x[t['col'][item_of].long() * data.n_rows + rows]
-    by_value, order = torch.sort(values, stable=True)
-    _, by_item = torch.sort(item_of[order], stable=True)
-    in_order = by_value[by_item].contiguous()
+    in_order = _sorted_items(data, row_index, t, n_items, total)
     ranks = torch.empty(total, dtype=torch.int32, device=data.device)
     call(lib.dpl_ecdf_ranks, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
          t['out'].data_ptr(), n_items, t['bi'].data_ptr(), t['br'].data_ptr(), len(block_item), in_order.data_ptr(),
@@ -356,3 +363,84 @@ def rdc_gram(ranks: torch.Tensor, tasks, k: int, w: np.ndarray, b: np.ndarray, r
         COUNTERS['kernels'] += 2
         partials.append(partial)
     return {'G': G, 'S': S, 'g_off': g_off[:-1], 'feat_off': feat_off[:-1], 'fs': fs, 'partials': partials}
+
+
+# ---- histograms of float columns (the header's last section) ---------------------------------------------------------------
+def order_statistics(data: DeviceData, row_index, item_col, item_row_off, item_n, positions) -> torch.Tensor:
+    """``[n_items, P]`` float32: for every item its values at the ``P`` positions ``positions[i]`` of its sorted order
+    (0 the minimum, ``n - 1`` the maximum), from the device sort of ``ecdf_ranks``.  One upload; the caller reads."""
+    assert data.is_float
+    n_items = len(item_col)
+    out_off = np.concatenate([[0], np.cumsum(np.asarray(item_n, np.int64))]).astype(np.int64)
+    at = np.asarray(positions, np.int64).reshape(n_items, -1) + out_off[:-1, None]
+    t = _items(data.device, item_col, item_row_off, item_n, out=out_off[:-1].copy(), at=at)
+    return _sorted_items(data, row_index, t, n_items, int(out_off[-1]))[t['at']]
+
+
+def check_bins(item_col, item_bins):
+    """ValueError, naming the column, for an item of more than ``DPL_HIST_MAX_BINS`` bins (or of none)."""
+    for col, bins in zip(item_col, item_bins):
+        if not 1 <= int(bins) <= CONSTANTS['DPL_HIST_MAX_BINS']:
+            raise ValueError("column {} has {} histogram bins, at most {} are built (a heavy tail or a tiny quartile range "
+                             "against the column's span)".format(int(col), int(bins), CONSTANTS['DPL_HIST_MAX_BINS']))
+
+
+def hist_codes(data: DeviceData, row_index, item_col, item_row_off, item_n, item_lo, item_hi, item_bins):
+    """``(codes, out_off)``: the uint16 bin of every row of every item under numpy's uniform bins ``(lo, hi, bins)``,
+    item i at ``codes[out_off[i] : out_off[i] + item_n[i]]`` in segment order (``dpl_hist_codes``).  ValueError before any
+    launch for a column over ``DPL_HIST_MAX_BINS``."""
+    assert data.is_float
+    check_bins(item_col, item_bins)
+    n_items = len(item_col)
+    out_off = np.concatenate([[0], np.cumsum(np.asarray(item_n, np.int64))]).astype(np.int64)
+    total = int(out_off[-1])
+    block_item, block_row0 = _row_blocks(item_n)
+    t = _items(data.device, item_col, item_row_off, item_n, out=out_off[:-1].copy(), lo=np.asarray(item_lo, np.float32),
+               hi=np.asarray(item_hi, np.float32), bins=np.asarray(item_bins, np.int32), bi=block_item, br=block_row0)
+    codes = torch.empty(total, dtype=torch.uint16, device=data.device)
+    call(load_library().dpl_hist_codes, *data.head(row_index), t['col'].data_ptr(), t['off'].data_ptr(), t['n'].data_ptr(),
+         t['out'].data_ptr(), t['lo'].data_ptr(), t['hi'].data_ptr(), t['bins'].data_ptr(), n_items, t['bi'].data_ptr(),
+         t['br'].data_ptr(), len(block_item), codes.data_ptr(), total, _stream(data.device))
+    COUNTERS['kernels'] += 1
+    return codes, out_off[:-1]
+
+
+def code_counts(codes: torch.Tensor, code_off, item_n, item_bins):
+    """``(counts, count_off)``: the int32 histogram of every item's codes, item i's ``item_bins[i]`` counts at
+    ``counts[count_off[i] ...]`` (``dpl_code_counts``)."""
+    assert codes.dtype == torch.uint16 and codes.is_contiguous()
+    check_bins(range(len(item_bins)), item_bins)
+    count_off = np.concatenate([[0], np.cumsum(np.asarray(item_bins, np.int64))]).astype(np.int64)
+    t = upload(codes.device, code_off=np.asarray(code_off, np.int64), n=np.asarray(item_n, np.int32),
+               bins=np.asarray(item_bins, np.int32), count_off=count_off[:-1].copy())
+    counts = torch.empty(int(count_off[-1]), dtype=torch.int32, device=codes.device)
+    call(load_library().dpl_code_counts, codes.data_ptr(), codes.numel(), t['code_off'].data_ptr(), t['n'].data_ptr(),
+         t['bins'].data_ptr(), t['count_off'].data_ptr(), len(item_bins), counts.data_ptr(), counts.numel(), _stream(codes.device))
+    COUNTERS['kernels'] += 1
+    return counts, count_off[:-1]
+
+
+def check_cells(col_a, col_b, bins_a, bins_b):
+    """ValueError, naming the two columns, for a pair whose joint table has more than ``DPL_HIST_MAX_CELLS`` cells."""
+    for ca, cb, ba, bb in zip(col_a, col_b, bins_a, bins_b):
+        if int(ba) * int(bb) > CONSTANTS['DPL_HIST_MAX_CELLS']:
+            raise ValueError("columns {} and {} have {} and {} histogram bins: a joint table of {} cells, at most {} are built"
+                             .format(int(ca), int(cb), int(ba), int(bb), int(ba) * int(bb), CONSTANTS['DPL_HIST_MAX_CELLS']))
+
+
+def pair_g_codes(codes: torch.Tensor, off_a, off_b, n, bins_a, bins_b, col_a=None, col_b=None) -> torch.Tensor:
+    """``[n_pairs]`` float64 G statistics of pairs of coded columns (``dpl_pair_g_codes``); ``col_a``, ``col_b`` name the
+    columns in the ValueError raised, before any launch, for a table over ``DPL_HIST_MAX_CELLS``."""
+    assert codes.dtype == torch.uint16 and codes.is_contiguous()
+    bins_a, bins_b = np.asarray(bins_a, np.int32), np.asarray(bins_b, np.int32)
+    check_bins(range(len(bins_a)) if col_a is None else col_a, bins_a)
+    check_bins(range(len(bins_b)) if col_b is None else col_b, bins_b)
+    check_cells(range(len(bins_a)) if col_a is None else col_a, range(len(bins_b)) if col_b is None else col_b, bins_a, bins_b)
+    t = upload(codes.device, oa=np.asarray(off_a, np.int64), ob=np.asarray(off_b, np.int64), n=np.asarray(n, np.int32),
+               ba=bins_a, bb=bins_b)
+    out = torch.empty(len(bins_a), dtype=torch.float64, device=codes.device)
+    call(load_library().dpl_pair_g_codes, codes.data_ptr(), codes.numel(), t['oa'].data_ptr(), t['ob'].data_ptr(),
+         t['n'].data_ptr(), t['ba'].data_ptr(), t['bb'].data_ptr(), len(bins_a), int((bins_a + bins_b).max()),
+         int((bins_a.astype(np.int64) * bins_b).max()), out.data_ptr(), _stream(codes.device))
+    COUNTERS['kernels'] += 1
+    return out

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from deeprob.hip import HipError, learn as L
-from deeprob.spn.learning.splitting import rdc as R
+from deeprob.spn.learning.splitting import rdc as R, hist as H, entropy as SE, gini as SG, gvs as SV
 from deeprob.spn.learning.leaf import learn_binary_clt, BERNOULLI_MESSAGE
 from deeprob.spn.structure.leaf import LeafType, Bernoulli, Categorical
 
@@ -35,7 +35,16 @@ LAUNCHES_PER_GENERATION = 14
 #: and the read of the counts ("Chow-Liu tree leaves in learn_spn")
 CLT_LAUNCHES_PER_GENERATION = 4
 
+#: the column-split functions of this package that ``split_cols`` takes, recognised by identity, and the split of each
+HIST_FUNCTIONS = ((SE.entropy_cols, H.ENTROPY), (SE.entropy_adaptive_cols, H.ENTROPY_ADAPTIVE), (SG.gini_cols, H.GINI),
+                  (SG.gini_adaptive_cols, H.GINI_ADAPTIVE), (SV.gvs_cols, 'gvs'), (SV.rgvs_cols, 'rgvs'))
+
 _last_info = {}
+
+
+def hist_split(split_cols):
+    """The split of one of ``HIST_FUNCTIONS``, None for anything else (a string included)."""
+    return next((split for fn, split in HIST_FUNCTIONS if fn is split_cols), None)
 
 
 def last_info() -> dict:
@@ -120,6 +129,7 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
         raise ValueError(BERNOULLI_MESSAGE)                                               # leaf.py:138-139
     _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
     rdc = split_cols is R.rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
+    hist = hist_split(split_cols)            # (likewise the entropy, Gini and G-test functions)
     if not rdc:
         kind.check_split_cols(split_cols)
     if clt:
@@ -130,6 +140,10 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
     rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
     if rdc:
         cols_kw = _kwargs(split_cols_kwargs, {'d': R.D_DEFAULT, 'k': R.K_DEFAULT, 's': R.S_DEFAULT}, 'rdc_cols')
+    elif hist is not None:
+        cols_kw = _kwargs(split_cols_kwargs, H.DEFAULTS[hist], split_cols.__name__)
+        if hist in H.MISSING_SIZE and cols_kw['size'] is None:
+            raise ValueError(H.MISSING_SIZE[hist])                                        # entropy.py:73-74, gini.py:75-76
     else:
         cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
     if kind.smoothed_leaves and leaf_kw['alpha'] < 0.0:
@@ -245,6 +259,47 @@ def component(adjacent, start):
     return seen
 
 
+def gvs_draws(random_state, nf, split_cols):
+    """The draws of gvs (gvs.py:30) or rgvs (gvs.py:76, then :30 on the subset, then :89) on ``nf`` columns: (columns
+    tested, start, coin)."""
+    k = int(max(np.sqrt(nf), 2))
+    if split_cols == 'gvs' or k == nf:
+        return np.arange(nf), random_state.randint(0, nf), None
+    perm = random_state.permutation(np.arange(nf))[:k]
+    start = random_state.randint(0, k)
+    return perm, start, random_state.rand()
+
+
+def pair_clusters(tasks, split_cols, cols_kw, g_all, dof_all):
+    """The clusters of every task from the statistics of the pairs a < b of its tested columns (``g_all``, with the
+    degrees of freedom ``dof_all`` of a G-test), in task order."""
+    out, g_pos = [], 0
+    for t in tasks:
+        (sub, start, coin), nf = t.draw, len(t.scope)
+        k = len(sub)
+        ia, ib = np.triu_indices(k, 1)
+        g, dof = g_all[g_pos:g_pos + len(ia)], dof_all[g_pos:g_pos + len(ia)]
+        g_pos += len(ia)
+        if split_cols == 'rdc':
+            dependent = g > cols_kw['d']                                              # rdc.py:43
+        else:
+            dependent = ~(g < 2.0 * dof * cols_kw['p'])                               # gvs.py:203-205, :42
+        adjacent = np.zeros((k, k), bool)
+        adjacent[ia, ib] = adjacent[ib, ia] = dependent
+        if split_cols == 'rdc':
+            clusters = R.components(adjacent)                                         # rdc.py:46-48
+        else:
+            part = np.zeros(k, np.int64)
+            part[list(component(adjacent, int(start)))] = 1
+            if coin is None:
+                clusters = part
+            else:
+                clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
+                clusters[sub] = part
+        out.append(clusters)
+    return out
+
+
 class DiscreteColumns:
     """What ``learn_spn`` asks of the kind of its columns, for ``Bernoulli`` / ``Categorical`` columns: the checks and the
     upload, the statistics of a generation's columns, the leaves, the column-split draws and clusters, the k-means batch."""
@@ -257,7 +312,8 @@ class DiscreteColumns:
 
     # ---- the checks of check_arguments that depend on the kind, in its order
     def check_split_cols(self, name):
-        _method(name, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
+        if hist_split(name) is None:
+            _method(name, KNOWN_COLS, BUILT_COLS, "Unknown split rows method called {}", 'split_cols')   # (sic: cols.py:76)
 
     def check_columns(self, rdc_kw):
         check_discrete(self.distributions, self.domains)
@@ -291,19 +347,29 @@ class DiscreteColumns:
         """The draws of a column split that is not 'random' (gvs.py:30, 76, 89; rdc.py:170-176): (columns tested, start,
         coin)."""
         nf = len(t.scope)
+        if split_cols in H.STAT_SPLITS:
+            return None                                 # (the entropy and Gini splits draw nothing)
         if split_cols == 'rdc':
             R.consume_draws(random_state, [self.ks[s] for s in t.scope], int(cols_kw['k']))
             return np.arange(nf), None, None
-        k = int(max(np.sqrt(nf), 2))
-        if split_cols == 'gvs' or k == nf:
-            return np.arange(nf), random_state.randint(0, nf), None
-        perm = random_state.permutation(np.arange(nf))[:k]
-        start = random_state.randint(0, k)
-        return perm, start, random_state.rand()
+        return gvs_draws(random_state, nf, split_cols)
+
+    def gtest_values(self, row_index, tasks):
+        """``(g, dof)`` of the column pairs a < b of the tested columns of every task, in task order: one launch, one
+        read."""
+        return self.pair_values(row_index, tasks, L.pair_g)
 
     def split_cols_clusters(self, row_index, tasks, split_cols, cols_kw):
         """The column clusters of every gvs / rgvs / rdc task: the G statistics (or maximal correlations) of all their
-        column pairs in one launch, then per task the adjacency and its component (gvs.py:31-50) or components."""
+        column pairs in one launch, then per task the adjacency and its component (gvs.py:31-50) or components.  The
+        entropy and Gini splits come from the counts ``column_stats`` has read: no launch, no read, no upload."""
+        if split_cols in H.STAT_SPLITS:
+            return [H.stat_clusters(split_cols, cols_kw, [t.counts[i][:self.ks[s]] for i, s in enumerate(t.scope)], t.n, False)
+                    for t in tasks]
+        g_all, dof_all = self.pair_values(row_index, tasks, L.pair_maxcorr if split_cols == 'rdc' else L.pair_g)
+        return pair_clusters(tasks, split_cols, cols_kw, g_all, dof_all)
+
+    def pair_values(self, row_index, tasks, pair_stat):
         ks, ci, cj, off, n = np.asarray(self.ks), [], [], [], []
         for t in tasks:
             cols = np.asarray(t.scope)[t.draw[0]]
@@ -311,35 +377,8 @@ class DiscreteColumns:
             ci, cj = ci + list(cols[ia]), cj + list(cols[ib])
             off, n = off + [t.row_off] * len(ia), n + [t.n] * len(ia)
         ci, cj = np.asarray(ci, np.int64), np.asarray(cj, np.int64)
-        pair_stat = L.pair_maxcorr if split_cols == 'rdc' else L.pair_g
         g_all = L.read(pair_stat(self.data, row_index, ci, cj, off, n, ks[ci], ks[cj])) if len(ci) else np.zeros(0)
-        out, g_pos = [], 0
-        for t in tasks:
-            (sub, start, coin), nf = t.draw, len(t.scope)
-            k = len(sub)
-            ia, ib = np.triu_indices(k, 1)
-            g = g_all[g_pos:g_pos + len(ia)]
-            g_pos += len(ia)
-            if split_cols == 'rdc':
-                dependent = g > cols_kw['d']                                              # rdc.py:43
-            else:
-                k_of = ks[np.asarray(t.scope)[sub]]
-                dof = (k_of[ia] - 1) * (k_of[ib] - 1)
-                dependent = ~(g < 2.0 * dof * cols_kw['p'])                               # gvs.py:203-205, :42
-            adjacent = np.zeros((k, k), bool)
-            adjacent[ia, ib] = adjacent[ib, ia] = dependent
-            if split_cols == 'rdc':
-                clusters = R.components(adjacent)                                         # rdc.py:46-48
-            else:
-                part = np.zeros(k, np.int64)
-                part[list(component(adjacent, int(start)))] = 1
-                if coin is None:
-                    clusters = part
-                else:
-                    clusters = np.zeros(nf, np.int64) if coin < 0.5 else np.ones(nf, np.int64)
-                    clusters[sub] = part
-            out.append(clusters)
-        return out
+        return g_all, (ks[ci] - 1) * (ks[cj] - 1)
 
     def kmeans_batch(self, row_index, tasks, n_clusters):
         return L.KMeansBatch(self.data, row_index, [(t.row_off, t.n, t.scope, [self.ks[s] for s in t.scope], t.draw) for t in tasks],
@@ -386,10 +425,18 @@ def learn_spn(
     leaves, see below; ``split_rows`` in ``'kmeans'``, ``'random'``;
     ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``, or the function
     ``deeprob.spn.learning.splitting.rdc.rdc_cols`` itself (recognised by identity): the RDC split as the exact maximal
-    correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``.  Also built: all-continuous data, every distribution
+    correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``; or one of the functions ``entropy_cols``,
+    ``entropy_adaptive_cols``, ``gini_cols``, ``gini_adaptive_cols`` (``e``, ``alpha``; the adaptive two also ``size``,
+    which is required), ``gvs_cols``, ``rgvs_cols`` (``p``) of ``deeprob.spn.learning.splitting`` themselves (recognised by
+    identity): on discrete data the entropy and Gini splits come from the column counts a generation has read anyway,
+    and ``gvs_cols`` / ``rgvs_cols`` are ``'gvs'`` / ``'rgvs'``.  Also built: all-continuous data, every distribution
     ``Gaussian`` and every domain a tuple ``(lo, hi)`` (learnspn_cont.py): ``split_rows`` in ``'kmeans'``, ``'random'``,
-    ``split_cols`` ``'random'`` or the function ``rdc_cols`` (there a ridge-regularised score of its own, see
-    splitting/rdc.py), MLE Gaussian leaves; ``'gvs'`` / ``'rgvs'`` raise there (a G-test needs a table).  Every other
+    ``split_cols`` ``'random'``, the function ``rdc_cols`` (there a ridge-regularised score of its own, see
+    splitting/rdc.py) or one of the six functions above -- there on numpy's histograms of the float columns, ``'scott'``
+    bins for the entropy and Gini splits and ``'fd'`` bins for the G-test, binned and counted on the device; a column of
+    more than 1024 bins or a column pair of more than 12 288 cells raises ``ValueError`` --, MLE Gaussian leaves; the
+    STRINGS ``'gvs'`` / ``'rgvs'`` raise there (a G-test needs a table), and ``'ebvs'``, ``'ebvs_ae'``, ``'gbvs'``,
+    ``'gbvs_ag'``, ``'wrgvs'`` raise for both kinds.  Every other
     name the reference knows, every other callable, ``Uniform`` and mixed discrete / continuous data raise
     ``NotImplementedError`` before any device work -- so does the STRING ``'rdc'``, the default: pass
     ``split_cols=rdc_cols`` or ``split_cols='gvs'``.  ``'kmeans'`` is this project's own k-means, not
@@ -414,10 +461,13 @@ def learn_spn(
     :param domains: A list of domains (one for each feature), each ``list(range(K))`` (``(lo, hi)`` for ``Gaussian``).
     :param learn_leaf: The method to use to learn a distribution leaf node: 'mle' or the function ``learn_binary_clt``.
     :param split_rows: The rows splitting method: 'kmeans' or 'random'.
-    :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random' or the function ``rdc_cols``.
+    :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random', the function ``rdc_cols`` or one of the
+                       functions ``entropy_cols``, ``entropy_adaptive_cols``, ``gini_cols``, ``gini_adaptive_cols``,
+                       ``gvs_cols``, ``rgvs_cols``.
     :param learn_leaf_kwargs: The parameters of the learn leaf method (``alpha`` | ``to_pc``, ``alpha``, ``random_state``).
     :param split_rows_kwargs: The parameters of the rows splitting method (``n`` | ``a``, ``b``).
-    :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b`` | ``d``, ``k``, ``s``).
+    :param split_cols_kwargs: The parameters of the cols splitting method (``p`` | ``a``, ``b`` | ``d``, ``k``, ``s`` |
+                              ``e``, ``alpha`` | ``e``, ``alpha``, ``size``).
     :param min_rows_slice: The minimum number of samples required to split horizontally.
     :param min_cols_slice: The minimum number of features required to split vertically.
     :param random_state: The random state. It can be either None, a seed integer or a Numpy RandomState.
@@ -438,6 +488,8 @@ def learn_spn(
     random_state = check_random_state(random_state)
     if split_cols is R.rdc_cols:
         split_cols = 'rdc'
+    elif hist_split(split_cols) is not None:
+        split_cols = hist_split(split_cols)
     clt = learn_leaf is learn_binary_clt
     dev_data = kind.upload(data)
     device = dev_data.device

@@ -1,3 +1,7 @@
-"""The splitting methods of the reference (deeprob/spn/learning/splitting) that exist as functions on the HIP path.
-Only ``rdc_cols`` and ``rdc_scores`` are built; the other methods are reached through ``learn_spn``'s names."""
+"""The splitting methods of the reference (deeprob/spn/learning/splitting) that exist as functions on the HIP path: the RDC
+split (``rdc_cols``, ``rdc_scores``), the entropy and Gini splits and the G-test splits.  ``learn_spn`` takes each of the
+``*_cols`` functions as ``split_cols``, recognised by identity; the other methods are reached through its names."""
 from .rdc import rdc_cols, rdc_scores
+from .entropy import entropy_cols, entropy_adaptive_cols
+from .gini import gini_cols, gini_adaptive_cols
+from .gvs import gvs_cols, rgvs_cols, gtest

@@ -1,7 +1,7 @@
 /*
  * deeprob_learn.h -- C ABI of libdeeprob_learn.so (gfx950 / MI355X): the device side of LearnSPN
  * (deeprob.spn.learning.learnspn.learn_spn) for discrete data and, in its last section, for continuous
- * (all-Gaussian) data.
+ * (all-Gaussian) data, with the histograms of float columns (the entropy, Gini and G-test column splits there) at the end.
  *
  * The reference is Python on numpy (deeprob/spn/learning/learnspn.py:121-222); the statistics it
  * gathers per task -- column histograms (leaf.py:162, 263; learnspn.py:132), the joint histograms
@@ -274,6 +274,55 @@ int dpl_kmeansf_inertia(const float *xf, int64_t n_rows, int n_cols, const int32
                         const int32_t *task_n, const int64_t *task_cent_off, const int64_t *task_lab_off, int n_tasks,
                         int n_restarts, int n_clusters, const double *cent, const uint8_t *labels, int64_t n_lab,
                         double *inertia, int32_t *sizes, void *stream);
+
+/* ==== histograms of float columns (splitting/entropy.py, gini.py: np.histogram(col, 'scott'); gvs.py:184-190:
+ * np.histogram_bin_edges(col, 'fd') and np.histogram2d on them) ====================================================
+ * An ITEM is one column over one row segment, as above, with the three numbers of numpy's uniform bins: lo, hi
+ * (float32: the item's min and max, or min - 0.5 and max + 0.5 when they are equal) and bins >= 1 (the host derives it
+ * from the bin width in float64: deeprob/spn/learning/splitting/hist.py).  The EDGES are float32, what np.linspace
+ * gives for float32 ends:
+ *   step = fl32(fl32(hi - lo) / fl32(bins));  edge[i] = fl32(fl32(fl32(i) * step) + lo), i < bins;  edge[bins] = hi
+ * -- one multiply, then one add, never fused.  The BIN of a value x (lo <= x <= hi) is (the number of i <= bins with
+ * edge[i] <= x) - 1, and bins - 1 for x == hi: the largest b <= bins - 1 with edge[b] <= x.  That is the bin np.histogram
+ * and np.histogram2d count x in.  A multiply-and-truncate guess is only the starting point of the search; the edges
+ * decide.
+ * Caps: a column has at most DPL_HIST_MAX_BINS bins (a code is a uint16 and the count table of an item lives in LDS);
+ * a pair's joint table has at most DPL_HIST_MAX_CELLS cells: 48 KiB of int32 which, with the 1024 + 12 float64
+ * marginals a table of that size can have at most and the 256 partial sums, stays under the 64 KiB a work-group gets
+ * without asking for more, so two work-groups at the cap, and five at the 80 x 80 of 20 000 Gaussian rows, share the
+ * 160 KiB of a compute unit (one resident work-group per compute unit was avoided).  The package
+ * raises ValueError over a cap, naming the column, before any launch. */
+#define DPL_HIST_MAX_BINS 1024
+#define DPL_HIST_MAX_CELLS 12288
+
+/* Bin codes: codes[item_out_off[i] + r] = the bin of row r of item i's segment, item major like the ranks of
+ * dpl_ecdf_ranks.  Block b covers positions block_row0[b] .. + 256 of item block_item[b].  codes: [n_out] uint16,
+ * n_out = the sum of item_n, every element written (code < bins). */
+int dpl_hist_codes(const float *xf, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                   const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n,
+                   const int64_t *item_out_off, const float *item_lo, const float *item_hi, const int32_t *item_bins,
+                   int64_t n_items, const int32_t *block_item, const int32_t *block_row0, int64_t n_blocks,
+                   uint16_t *codes, int64_t n_out, void *stream);
+
+/* Counts of the codes: counts[item_count_off[i] + b] = the number of r < item_n[i] with codes[item_code_off[i] + r]
+ * == b, b < item_bins[i] <= DPL_HIST_MAX_BINS: exact int32 (LDS integer atomics), one work-group per item.  The
+ * caller lays the items' outputs out so that they tile [0, n_counts).  A code >= bins is not counted. */
+int dpl_code_counts(const uint16_t *codes, int64_t n_codes, const int64_t *item_code_off, const int32_t *item_n,
+                    const int32_t *item_bins, const int64_t *item_count_off, int64_t n_items, int32_t *counts,
+                    int64_t n_counts, void *stream);
+
+/* G statistic of two coded columns (gvs.py:190-197 on the table np.histogram2d gives): pair q has the codes of its two
+ * columns at codes[pair_off_a[q] ...] and codes[pair_off_b[q] ...], n = pair_n[q] of each, with ba = pair_bins_a[q]
+ * and bb = pair_bins_b[q] bins; ba * bb <= max_cells <= DPL_HIST_MAX_CELLS and ba + bb <= max_bins_sum, the largest
+ * of the launch (they size the LDS of every work-group; a pair over them gets NaN).  One work-group per pair: the joint
+ * counts c[a][b] in exact int32, then in float64, in this order of operations:
+ *   h[a][b] = c[a][b] + 2^-23;  m1[a] = h[a][0] + h[a][1] + ...;  m2[b] = h[0][b] + h[1][b] + ...;
+ *   t[a][b] = h * log(h / (m1[a] * m2[b] / n));  256 partial sums (partial l takes the cells l, l + 256, ... of the row
+ *   major table in order, from 0.0), added in order of l (the convention of dpl_column_moments);  g = 2 * that sum.
+ * Tables need not be square and are as a rule larger than the work-group.  g: [n_pairs] float64. */
+int dpl_pair_g_codes(const uint16_t *codes, int64_t n_codes, const int64_t *pair_off_a, const int64_t *pair_off_b,
+                     const int32_t *pair_n, const int32_t *pair_bins_a, const int32_t *pair_bins_b, int64_t n_pairs,
+                     int max_bins_sum, int max_cells, double *g, void *stream);
 
 #ifdef __cplusplus
 }
