@@ -23,10 +23,17 @@ void set_error(const char *fmt, ...);
 // of the kernel with this id (DPK_KERNEL_* in deeprob_hip.h), or nulls
 void profile_take(hipEvent_t *start, hipEvent_t *stop, int kernel_id = 1);
 // Per-DEVICE launch state (a process may drive several GPUs): the compute-unit count of the calling thread's current
-// device, and the raised dynamic-LDS limit of a kernel, set once per (kernel, device) -- hipFuncSetAttribute and the
-// CU count both belong to a device, not to the process.  ensure_dynamic_lds returns DPK_OK or DPK_ELAUNCH (error set).
+// device, and the raised dynamic-LDS limit of a kernel, remembered per (kernel, device) and raised again only when a launch
+// asks for more bytes -- a function attribute and the CU count both belong to a device, not to the process.
+// ensure_dynamic_lds returns DPK_OK or DPK_ELAUNCH (error set).
 int device_cus();
 int ensure_dynamic_lds(const void *kernel, int bytes);
+#ifdef DPK_TIMELINE
+// Measurement builds (make ../lib/libdeeprob_hip_timeline.so): the device buffer the kernels of one family stamp into, at
+// least `bytes` large, kept for the life of the process; its address, `grid` and, if given, `extra` are written to
+// /tmp/dpk_timeline<family>_ptr.txt for tools/timeline*.py (read back through dpk_debug_read).  Null if it cannot be had.
+unsigned long long *timeline_buffer(const char *family, size_t bytes, int grid, int extra = -1);
+#endif
 
 // Marginalised-evidence hint of the RAT-SPN forward kernels: a work-group that meets NaN evidence stores the launch
 // number in a host-mapped word; the host reads it without synchronising (a stale value only costs speed) and picks the
@@ -80,23 +87,49 @@ inline TablePlan plan_tables(uint32_t flags, const void *key, const FpSeg *segs,
         }                                  \
     } while (0)
 
-#define DPK_CHECK_LAUNCH(what)                                                      \
-    do {                                                                            \
-        hipError_t e__ = hipGetLastError();                                         \
-        if (e__ != hipSuccess) {                                                    \
-            dpk::set_error("%s: %s", (what), hipGetErrorString(e__));               \
-            return DPK_ELAUNCH;                                                     \
-        }                                                                           \
+// return the status of `expr` (a helper that launches) unless it is DPK_OK
+#define DPK_TRY(expr)                      \
+    do {                                   \
+        const int rc__ = (expr);           \
+        if (rc__ != DPK_OK) return rc__;   \
     } while (0)
 
-// A launch reports its own status: whatever an earlier runtime call on this thread (the caller's own included, e.g. a
-// failed hipEventElapsedTime) left in the last-error slot is dropped first, so DPK_CHECK_LAUNCH never blames a kernel
-// for it.
-#define DPK_LAUNCH(...)                    \
-    do {                                   \
-        (void)hipGetLastError();           \
-        hipLaunchKernelGGL(__VA_ARGS__);   \
+// The measurement bracket of a launch site: takes the events a caller asked for around the next launch of the kernel with
+// this id (dpk_profile_next_kernel[_of]; nulls otherwise) and records the first; stop() records the second, once.  A site
+// with one launch hands the bracket to DPK_LAUNCH_IN, which stops it; one that brackets several launches calls stop().
+struct Profile {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t st;
+    Profile(int kernel_id, hipStream_t stream) : st(stream) {
+        profile_take(&ev0, &ev1, kernel_id);
+        if (ev0) (void)hipEventRecord(ev0, st);
+    }
+    void stop() {
+        if (ev1) (void)hipEventRecord(ev1, st);
+        ev1 = nullptr;
+    }
+};
+struct NoProfile {
+    void stop() {}
+};
+
+// The one launch of this library: hipLaunchKernelGGL(...) inside the bracket `prof`.  A launch reports its own status:
+// whatever an earlier runtime call on this thread (the caller's own included, e.g. a failed hipEventElapsedTime) left in
+// the last-error slot is dropped first, so no kernel is blamed for it; then the launch, the stop of the bracket, and the
+// status.  A launch that fails ends the function there: DPK_ELAUNCH, "<what>: <hip error>" as the last error.
+#define DPK_LAUNCH_IN(prof, what, ...)                                      \
+    do {                                                                    \
+        (void)hipGetLastError();                                            \
+        hipLaunchKernelGGL(__VA_ARGS__);                                    \
+        (prof).stop();                                                      \
+        hipError_t e__ = hipGetLastError();                                 \
+        if (e__ != hipSuccess) {                                            \
+            dpk::set_error("%s: %s", (what), hipGetErrorString(e__));       \
+            return DPK_ELAUNCH;                                             \
+        }                                                                   \
     } while (0)
+// ... outside any bracket
+#define DPK_LAUNCH(what, ...) DPK_LAUNCH_IN(dpk::NoProfile(), what, __VA_ARGS__)
 
 constexpr int kWave = 64;           // CDNA wavefront
 constexpr int kCompactRec = 48;      // bytes of a compact block record: 8 means + 4 u16 row offsets + pad

@@ -563,13 +563,12 @@ extern "C" int dpk_coupling1d_forward(const float *x, int64_t B, int32_t D, cons
                 (long long)ws_bytes, (long long)w.bytes + 256);
     int *bad = (int *)((char *)ws + w.bytes);
     hipStream_t st = (hipStream_t)stream;
-    DPK_LAUNCH(coupling_index_kernel, dim3(1), dim3(64), 0, st, mask, inv_mask, D, w.K1p, w.N2p, w.kidx,
-                       w.nidx, bad);
+    DPK_LAUNCH("coupling_index_kernel", coupling_index_kernel, dim3(1), dim3(64), 0, st, mask, inv_mask, D, w.K1p,
+               w.N2p, w.kidx, w.nidx, bad);
     const int64_t n_pack = (int64_t)units * w.K1p + (int64_t)w.N2p * units + w.N2p;
-    DPK_LAUNCH(coupling_pack_kernel, dim3(cdiv(n_pack, 256) > 2048 ? 2048 : cdiv(n_pack, 256)), dim3(256),
-                       0, st, W1, W2, b2, w.kidx, w.nidx, D, units, w.K1p, w.N2p, affine, w.w1p, w.w2tp, w.w2sp,
-                       w.b2tp, w.b2sp);
-    DPK_CHECK_LAUNCH("coupling_pack_kernel");
+    DPK_LAUNCH("coupling_pack_kernel", coupling_pack_kernel, dim3(cdiv(n_pack, 256) > 2048 ? 2048 : cdiv(n_pack, 256)),
+               dim3(256), 0, st, W1, W2, b2, w.kidx, w.nidx, D, units, w.K1p, w.N2p, affine, w.w1p, w.w2tp, w.w2sp,
+               w.b2tp, w.b2sp);
     CouplingArgs a{};
     a.x = x; a.out = out; a.ldj = ldj; a.B = B; a.D = D; a.U = units; a.K1p = w.K1p; a.N2p = w.N2p;
     a.kidx = w.kidx; a.nidx = w.nidx; a.w1p = w.w1p; a.b1 = b1; a.w2tp = w.w2tp; a.w2sp = w.w2sp;
@@ -579,26 +578,10 @@ extern "C" int dpk_coupling1d_forward(const float *x, int64_t B, int32_t D, cons
     const bool alias_xs = units >= 64 && units <= 32 * kCWaves;   // as in the kernel
     const size_t lds = (hs_floats + kCWaves * kCM + (alias_xs ? 0 : xs_floats)) * sizeof(float);
     const int grid = cdiv(B, kCM);
-    if (affine) {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(coupling1d_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipEvent_t ev0, ev1;
-        profile_take(&ev0, &ev1, DPK_KERNEL_COUPLING1D);
-        if (ev0) (void)hipEventRecord(ev0, st);
-        DPK_LAUNCH(coupling1d_kernel<true>, dim3(grid), dim3(kCWaves * 64), lds, st, a);
-        if (ev1) (void)hipEventRecord(ev1, st);
-    } else {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(coupling1d_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipEvent_t ev0, ev1;
-        profile_take(&ev0, &ev1, DPK_KERNEL_COUPLING1D);
-        if (ev0) (void)hipEventRecord(ev0, st);
-        DPK_LAUNCH(coupling1d_kernel<false>, dim3(grid), dim3(kCWaves * 64), lds, st, a);
-        if (ev1) (void)hipEventRecord(ev1, st);
-    }
-    DPK_CHECK_LAUNCH("coupling1d_kernel");
+    auto *kern = affine ? coupling1d_kernel<true> : coupling1d_kernel<false>;
+    if (lds > 64 * 1024) DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), (int)lds));
+    Profile prof(DPK_KERNEL_COUPLING1D, st);
+    DPK_LAUNCH_IN(prof, "coupling1d_kernel", kern, dim3(grid), dim3(kCWaves * 64), lds, st, a);
     return DPK_OK;
 }
 
@@ -609,10 +592,9 @@ extern "C" int dpk_bn1d_fold(const float *weight, const float *bias, const float
     DPK_REQUIRE(weight && bias && running_var && running_mean && scale_out && shift_out && ldj_const, DPK_EINVAL,
                 "bn1d_fold: null pointer");
     DPK_REQUIRE(D > 0 && (scale_in == nullptr) == (shift_in == nullptr), DPK_EINVAL, "bn1d_fold: bad arguments");
-    DPK_LAUNCH(bn1d_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, weight, bias, running_var,
-                       running_mean, eps, D, inverse, scale_in, shift_in, scale_out, shift_out, ldj_const,
-                       accumulate);
-    DPK_CHECK_LAUNCH("bn1d_fold_kernel");
+    DPK_LAUNCH("bn1d_fold_kernel", bn1d_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, weight, bias,
+               running_var, running_mean, eps, D, inverse, scale_in, shift_in, scale_out, shift_out, ldj_const,
+               accumulate);
     return DPK_OK;
 }
 
@@ -687,8 +669,7 @@ extern "C" int dpk_bn1d_fold_many(int32_t n, const dpk_bn1d_fold_args *layers, f
         DPK_REQUIRE(!(ldj_total && q.accumulate), DPK_EINVAL, "bn1d_fold_many: ldj_total with an accumulating layer");
         a.L[l] = q;
     }
-    DPK_LAUNCH(bn1d_fold_many_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-    DPK_CHECK_LAUNCH("bn1d_fold_many_kernel");
+    DPK_LAUNCH("bn1d_fold_many_kernel", bn1d_fold_many_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
     return DPK_OK;
 }
 
@@ -700,9 +681,8 @@ extern "C" int dpk_affine1d_forward(const float *x, const float *scale, const fl
     const int64_t total = B * D;
     int grid = cdiv(total, 256);
     if (grid > 8192) grid = 8192;
-    DPK_LAUNCH(affine1d_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, scale, shift, total, D,
-                       out);
-    DPK_CHECK_LAUNCH("affine1d_kernel");
+    DPK_LAUNCH("affine1d_kernel", affine1d_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, scale, shift,
+               total, D, out);
     return DPK_OK;
 }
 
@@ -742,9 +722,8 @@ extern "C" int dpk_logit1d_forward(const float *x, int64_t B, int32_t D, float a
     DPK_REQUIRE(B >= 0 && D > 0 && alpha > 0.f && alpha < 1.f, DPK_EINVAL, "logit1d: bad arguments");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(x && out && ldj, DPK_EINVAL, "logit1d: null pointer");
-    DPK_LAUNCH(logit1d_kernel, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, x, B, D, alpha, ldj_const,
-                       inverse, out, ldj);
-    DPK_CHECK_LAUNCH("logit1d_kernel");
+    DPK_LAUNCH("logit1d_kernel", logit1d_kernel, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, x, B, D, alpha,
+               ldj_const, inverse, out, ldj);
     return DPK_OK;
 }
 
@@ -760,8 +739,7 @@ extern "C" int dpk_normal_base_logprob(const float *u, const float *scale_in, co
     // rows per wave: 8 once the grid covers the chip a few times over (the per-work-group parameter table amortised), 1 for
     // training batches (B = 512 was 16 work-groups walking 8 rows each: 15 us)
     const int rows = B >= 4 * kBaseRows * 4 * (int64_t)device_cus() ? kBaseRows : 1;
-    DPK_LAUNCH(normal_base_logprob_kernel, dim3(cdiv(B, 4 * rows)), dim3(256), lds, (hipStream_t)stream,
-                       u, scale_in, shift_in, loc, scale, ildj, ildj_const, B, D, out, rows);
-    DPK_CHECK_LAUNCH("normal_base_logprob_kernel");
+    DPK_LAUNCH("normal_base_logprob_kernel", normal_base_logprob_kernel, dim3(cdiv(B, 4 * rows)), dim3(256), lds,
+               (hipStream_t)stream, u, scale_in, shift_in, loc, scale, ildj, ildj_const, B, D, out, rows);
     return DPK_OK;
 }

@@ -169,12 +169,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmArgs g) {
     }
 }
 
-static void launch_gemm_kernel(const GemmArgs &g, dim3 grid, hipStream_t st) {
+static int launch_gemm_kernel(const GemmArgs &g, dim3 grid, hipStream_t st) {
     const bool ak = g.sak == 1, bn = g.sbn == 1;   // any other stride pair runs as the "slow axis" orientation
-    if (ak && bn) DPK_LAUNCH((gemm_f32_kernel<true, true>), grid, dim3(256), 0, st, g);
-    else if (ak) DPK_LAUNCH((gemm_f32_kernel<true, false>), grid, dim3(256), 0, st, g);
-    else if (bn) DPK_LAUNCH((gemm_f32_kernel<false, true>), grid, dim3(256), 0, st, g);
-    else DPK_LAUNCH((gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, g);
+    if (ak && bn) DPK_LAUNCH("gemm_f32_kernel", (gemm_f32_kernel<true, true>), grid, dim3(256), 0, st, g);
+    else if (ak) DPK_LAUNCH("gemm_f32_kernel", (gemm_f32_kernel<true, false>), grid, dim3(256), 0, st, g);
+    else if (bn) DPK_LAUNCH("gemm_f32_kernel", (gemm_f32_kernel<false, true>), grid, dim3(256), 0, st, g);
+    else DPK_LAUNCH("gemm_f32_kernel", (gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, g);
+    return DPK_OK;
 }
 
 // C = 0 in front of the fallback's atomicAdds
@@ -253,8 +254,8 @@ static bool gemm_pool_take(int64_t floats, int tiles, float **p, unsigned **t, h
     return true;
 }
 
-void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
-    if (g_in.M <= 0 || g_in.N <= 0) return;
+int launch_gemm(const GemmArgs &g_in, hipStream_t st) {
+    if (g_in.M <= 0 || g_in.N <= 0) return DPK_OK;
     GemmArgs g = g_in;
     const int tiles = cdiv(g.N, kGT) * cdiv(g.M, kGT);
     int ksplit = 1;
@@ -271,8 +272,7 @@ void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
     }
     if (g.ksplit > 1) {
         if (gemm_pool_take((int64_t)tiles * g.ksplit * 4096, tiles, &g.partials, &g.tickets, st)) {
-            launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT), g.ksplit), st);
-            return;
+            return launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT), g.ksplit), st);
         }
         g.partials = nullptr;
         g.tickets = nullptr;
@@ -283,19 +283,21 @@ void launch_gemm(const GemmArgs &g_in, hipStream_t st) {
                 // replayed right behind host-to-device copies -- tests/test_gemm_f32_gpu.py, the captured fallback)
                 const int64_t total = (int64_t)g.M * g.N;
                 const int64_t nb = (total + 255) / 256;
-                DPK_LAUNCH(gemm_zero_kernel, dim3((int)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st, g);
+                DPK_LAUNCH("gemm_zero_kernel", gemm_zero_kernel, dim3((int)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st,
+                           g);
             }
-            launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT), g.ksplit), st);
+            DPK_TRY(launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT), g.ksplit), st));
             if (g.bias || g.relu || g.gate) {
                 const int64_t total = (int64_t)g.M * g.N;
                 const int64_t nb = (total + 255) / 256;
-                DPK_LAUNCH(gemm_epilogue_kernel, dim3((int)(nb > 4096 ? 4096 : nb)), dim3(256), 0, st, g);
+                DPK_LAUNCH("gemm_epilogue_kernel", gemm_epilogue_kernel, dim3((int)(nb > 4096 ? 4096 : nb)), dim3(256),
+                           0, st, g);
             }
-            return;
+            return DPK_OK;
         }
     }
     g.ksplit = 1;
-    launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT)), st);
+    return launch_gemm_kernel(g, dim3(cdiv(g.N, kGT), cdiv(g.M, kGT)), st);
 }
 
 // Column reducers over the batch: a work-group of 1024 threads owns kRC = 16 adjacent columns, its 64 row groups
@@ -700,10 +702,10 @@ extern "C" int dpk_coupling1d_backward(const float *x, int64_t B, int32_t D, con
     const int zc = affine ? 2 * D : D;
     if (grad_act) DPK_REQUIRE(hipMemsetAsync(grad_act, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
     if (B == 0) {
-        if (grad_W1) (void)hipMemsetAsync(grad_W1, 0, (size_t)units * D * 4, st);
-        if (grad_b1) (void)hipMemsetAsync(grad_b1, 0, (size_t)units * 4, st);
-        if (grad_W2) (void)hipMemsetAsync(grad_W2, 0, (size_t)zc * units * 4, st);
-        if (grad_b2) (void)hipMemsetAsync(grad_b2, 0, (size_t)zc * 4, st);
+        if (grad_W1) DPK_REQUIRE(hipMemsetAsync(grad_W1, 0, (size_t)units * D * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        if (grad_b1) DPK_REQUIRE(hipMemsetAsync(grad_b1, 0, (size_t)units * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        if (grad_W2) DPK_REQUIRE(hipMemsetAsync(grad_W2, 0, (size_t)zc * units * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        if (grad_b2) DPK_REQUIRE(hipMemsetAsync(grad_b2, 0, (size_t)zc * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
         return DPK_OK;
     }
     DPK_REQUIRE(x && grad_x && (grad_u || grad_ildj), DPK_EINVAL, "coupling1d_backward: null pointer");
@@ -720,48 +722,49 @@ extern "C" int dpk_coupling1d_backward(const float *x, int64_t B, int32_t D, con
     g.A = x; g.sam = D; g.sak = 1; g.kscale = mask;
     g.Bm = W1; g.sbk = 1; g.sbn = D;
     g.C = H; g.ldc = units; g.M = (int)B; g.N = units; g.K = D; g.bias = b1; g.relu = 1;
-    launch_gemm(g, st);
+    DPK_TRY(launch_gemm(g, st));
     // Z = H W2^T + b2
     g = GemmArgs{};
     g.A = H; g.sam = units; g.sak = 1;
     g.Bm = W2; g.sbk = 1; g.sbn = units;
     g.C = Z; g.ldc = zc; g.M = (int)B; g.N = zc; g.K = units; g.bias = b2;
-    launch_gemm(g, st);
+    DPK_TRY(launch_gemm(g, st));
     // element-wise core: Z <- dZ, grad_x <- direct term
-    DPK_LAUNCH(coupling_bwd_elem_kernel, dim3(grid1d(B * 64, 256, 1024)), dim3(256), 0, st, x, Z, inv_mask, act_weight,
-                       grad_u, grad_ildj, B, D, affine, 0, grad_x, grad_act);
+    DPK_LAUNCH("coupling_bwd_elem_kernel", coupling_bwd_elem_kernel, dim3(grid1d(B * 64, 256, 1024)), dim3(256), 0, st,
+               x, Z, inv_mask, act_weight, grad_u, grad_ildj, B, D, affine, 0, grad_x, grad_act);
     // dW2 = dZ^T H, db2 = colsum(dZ)
     if (grad_W2) {
         g = GemmArgs{};
         g.A = Z; g.sam = 1; g.sak = zc;
         g.Bm = H; g.sbk = units; g.sbn = 1;
         g.C = grad_W2; g.ldc = units; g.M = zc; g.N = units; g.K = (int)B;
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
     }
-    if (grad_b2) DPK_LAUNCH(colsum_kernel, dim3(cdiv(zc, kRC)), dim3(kRThreads), 0, st, Z, B, zc, (int64_t)zc, grad_b2);
+    if (grad_b2) DPK_LAUNCH("colsum_kernel", colsum_kernel, dim3(cdiv(zc, kRC)), dim3(kRThreads), 0, st, Z, B, zc,
+        (int64_t)zc, grad_b2);
     // dH = (dZ W2) * [H > 0]
     g = GemmArgs{};
     g.A = Z; g.sam = zc; g.sak = 1;
     g.Bm = W2; g.sbk = units; g.sbn = 1;
     g.C = dH; g.ldc = units; g.M = (int)B; g.N = units; g.K = zc; g.gate = H; g.ldg = units;
-    launch_gemm(g, st);
+    DPK_TRY(launch_gemm(g, st));
     // dW1 = dH^T (mask * x), db1 = colsum(dH)
     if (grad_W1) {
         g = GemmArgs{};
         g.A = dH; g.sam = 1; g.sak = units;
         g.Bm = x; g.sbk = D; g.sbn = 1; g.nscale = mask;
         g.C = grad_W1; g.ldc = D; g.M = units; g.N = D; g.K = (int)B;
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
     }
     if (grad_b1)
-        DPK_LAUNCH(colsum_kernel, dim3(cdiv(units, kRC)), dim3(kRThreads), 0, st, dH, B, units, (int64_t)units, grad_b1);
+        DPK_LAUNCH("colsum_kernel", colsum_kernel, dim3(cdiv(units, kRC)), dim3(kRThreads), 0, st, dH, B, units,
+                   (int64_t)units, grad_b1);
     // grad_x += mask * (dH W1)
     g = GemmArgs{};
     g.A = dH; g.sam = units; g.sak = 1;
     g.Bm = W1; g.sbk = D; g.sbn = 1; g.nscale = mask;
     g.C = grad_x; g.ldc = D; g.M = (int)B; g.N = D; g.K = units; g.accumulate = 1;
-    launch_gemm(g, st);
-    DPK_CHECK_LAUNCH("coupling1d_backward");
+    DPK_TRY(launch_gemm(g, st));
     return DPK_OK;
 }
 
@@ -779,9 +782,8 @@ extern "C" int dpk_bn1d_train_forward(const float *x, int64_t B, int32_t D, cons
     hipStream_t st = (hipStream_t)stream;
     float *sc = (float *)ws, *sh = sc + D;
     DPK_REQUIRE(hipMemsetAsync(ildj_const, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
-    DPK_LAUNCH(bn1d_stats_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, B, D, weight, bias, momentum, eps,
-                       running_var, running_mean, save_mean, save_var, sc, sh, ildj_const);
-    DPK_CHECK_LAUNCH("bn1d_stats_kernel");
+    DPK_LAUNCH("bn1d_stats_kernel", bn1d_stats_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, B, D, weight,
+               bias, momentum, eps, running_var, running_mean, save_mean, save_var, sc, sh, ildj_const);
     return dpk_affine1d_forward(x, sc, sh, B, D, out, stream);
 }
 
@@ -797,13 +799,11 @@ extern "C" int dpk_bn1d_backward(const float *x, const float *grad_u, const floa
     DPK_REQUIRE(ws_bytes >= (int64_t)(2 * D + 64) * 4, DPK_EWORKSPACE, "bn1d_backward: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float *s1 = (float *)ws, *s2 = s1 + D, *sg = s2 + D;
-    if (grad_ildj) DPK_LAUNCH(vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ildj, B, sg);
-    DPK_LAUNCH(bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, grad_u, B, D, mean, var, eps, s1,
-                       s2);
-    DPK_LAUNCH(bn1d_bwd_apply_kernel, dim3(grid1d(B * D)), dim3(256), 0, st, x, grad_u,
-                       grad_ildj ? sg : nullptr, B, D, weight, mean, var, eps, s1, s2, train, grad_x, grad_weight,
-                       grad_bias);
-    DPK_CHECK_LAUNCH("bn1d_backward");
+    if (grad_ildj) DPK_LAUNCH("vecsum_kernel", vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ildj, B, sg);
+    DPK_LAUNCH("bn1d_bwd_reduce_kernel", bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, grad_u,
+               B, D, mean, var, eps, s1, s2);
+    DPK_LAUNCH("bn1d_backward", bn1d_bwd_apply_kernel, dim3(grid1d(B * D)), dim3(256), 0, st, x, grad_u,
+               grad_ildj ? sg : nullptr, B, D, weight, mean, var, eps, s1, s2, train, grad_x, grad_weight, grad_bias);
     return DPK_OK;
 }
 
@@ -811,9 +811,8 @@ extern "C" int dpk_bn1d_backward(const float *x, const float *grad_u, const floa
 // ---- batch-sharded BatchNormLayer1d (see the kernels above) ------------------------------------------------
 extern "C" int dpk_bn1d_local_moments(const float *x, int64_t B, int32_t D, float *moments, void *stream) {
     DPK_REQUIRE(B >= 0 && D > 0 && moments && (B == 0 || x), DPK_EINVAL, "bn1d_local_moments: bad arguments");
-    DPK_LAUNCH(bn1d_local_moments_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, (hipStream_t)stream, x, B, D,
-                       moments);
-    DPK_CHECK_LAUNCH("bn1d_local_moments_kernel");
+    DPK_LAUNCH("bn1d_local_moments_kernel", bn1d_local_moments_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0,
+               (hipStream_t)stream, x, B, D, moments);
     return DPK_OK;
 }
 
@@ -830,9 +829,8 @@ extern "C" int dpk_bn1d_sync_forward(const float *x, int64_t B, int32_t D, const
     hipStream_t st = (hipStream_t)stream;
     float *sc = (float *)ws, *sh = sc + D;
     DPK_REQUIRE(hipMemsetAsync(ildj_const, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
-    DPK_LAUNCH(bn1d_combine_kernel, dim3(cdiv(D, 1024)), dim3(1024), 0, st, gathered, world, D, weight, bias,
-                       momentum, eps, running_var, running_mean, save_mean, save_var, sc, sh, ildj_const);
-    DPK_CHECK_LAUNCH("bn1d_combine_kernel");
+    DPK_LAUNCH("bn1d_combine_kernel", bn1d_combine_kernel, dim3(cdiv(D, 1024)), dim3(1024), 0, st, gathered, world, D,
+               weight, bias, momentum, eps, running_var, running_mean, save_mean, save_var, sc, sh, ildj_const);
     if (B == 0) return DPK_OK;
     return dpk_affine1d_forward(x, sc, sh, B, D, out, stream);
 }
@@ -843,10 +841,10 @@ extern "C" int dpk_bn1d_backward_sums(const float *x, const float *grad_u, const
                 "bn1d_backward_sums: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (B == 0 || !grad_ildj) DPK_REQUIRE(hipMemsetAsync(sums + 2 * D, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
-    if (B > 0 && grad_ildj) DPK_LAUNCH(vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ildj, B, sums + 2 * D);
-    DPK_LAUNCH(bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, grad_u, B, D, mean, var, eps,
-                       sums, sums + D);
-    DPK_CHECK_LAUNCH("bn1d_backward_sums");
+    if (B > 0 && grad_ildj) DPK_LAUNCH("vecsum_kernel", vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ildj, B,
+        sums + 2 * D);
+    DPK_LAUNCH("bn1d_backward_sums", bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, x, grad_u, B,
+               D, mean, var, eps, sums, sums + D);
     return DPK_OK;
 }
 
@@ -858,9 +856,9 @@ extern "C" int dpk_bn1d_sync_backward(const float *x, const float *grad_u, int64
                     (B == 0 || (x && grad_u && grad_x)),
                 DPK_EINVAL, "bn1d_sync_backward: bad arguments");
     const int64_t work = B * D > D ? B * D : D;
-    DPK_LAUNCH(bn1d_sync_bwd_apply_kernel, dim3(grid1d(work)), dim3(256), 0, (hipStream_t)stream, x, grad_u, B,
-                       B_total, D, weight, mean, var, eps, sums_x, sums_p, grad_x, grad_weight, grad_bias);
-    DPK_CHECK_LAUNCH("bn1d_sync_bwd_apply_kernel");
+    DPK_LAUNCH("bn1d_sync_bwd_apply_kernel", bn1d_sync_bwd_apply_kernel, dim3(grid1d(work)), dim3(256), 0,
+               (hipStream_t)stream, x, grad_u, B, B_total, D, weight, mean, var, eps, sums_x, sums_p, grad_x,
+               grad_weight, grad_bias);
     return DPK_OK;
 }
 
@@ -891,13 +889,12 @@ extern "C" int dpk_bn1d_inverse_backward(const float *u, const float *grad_x, co
     float *s1 = (float *)ws, *s2 = s1 + D, *G = s2 + D, *ones = G + D, *zero = ones + D, *sg = zero + D;
     // column sums of g and g (u - bias): the reducer of the forward direction with mean := bias, 1 / sqrt(var + eps) := 1
     DPK_REQUIRE(hipMemsetAsync(zero, 0, (size_t)D * 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
-    DPK_LAUNCH(fill_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, ones, 1.0f, (int64_t)D);
-    if (grad_ldj) DPK_LAUNCH(vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ldj, B, sg);
-    DPK_LAUNCH(bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, u, grad_x, B, D, bias, ones, 0.f,
-                       s1, s2);
-    DPK_LAUNCH(bn1d_inverse_bwd_finish_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, weight, running_var, eps, D,
-                       s1, s2, grad_ldj ? sg : nullptr, G, grad_weight, grad_bias);
-    DPK_CHECK_LAUNCH("bn1d_inverse_backward");
+    DPK_LAUNCH("fill_kernel", fill_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, ones, 1.0f, (int64_t)D);
+    if (grad_ldj) DPK_LAUNCH("vecsum_kernel", vecsum_kernel, dim3(1), dim3(256), 0, st, grad_ldj, B, sg);
+    DPK_LAUNCH("bn1d_bwd_reduce_kernel", bn1d_bwd_reduce_kernel, dim3(cdiv(D, kRC)), dim3(kRThreads), 0, st, u, grad_x,
+               B, D, bias, ones, 0.f, s1, s2);
+    DPK_LAUNCH("bn1d_inverse_backward", bn1d_inverse_bwd_finish_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, weight,
+               running_var, eps, D, s1, s2, grad_ldj ? sg : nullptr, G, grad_weight, grad_bias);
     return dpk_affine1d_forward(grad_x, G, zero, B, D, grad_u, stream);
 }
 
@@ -907,9 +904,8 @@ extern "C" int dpk_normal_base_backward(const float *u, const float *loc, const 
     DPK_REQUIRE(B >= 0 && D > 0, DPK_EINVAL, "normal_base_backward: bad sizes");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(u && loc && scale && g && grad_u, DPK_EINVAL, "normal_base_backward: null pointer");
-    DPK_LAUNCH(normal_base_bwd_kernel, dim3(grid1d(B * D)), dim3(256), 0, (hipStream_t)stream, u, loc, scale, g,
-                       B, D, grad_u);
-    DPK_CHECK_LAUNCH("normal_base_bwd_kernel");
+    DPK_LAUNCH("normal_base_bwd_kernel", normal_base_bwd_kernel, dim3(grid1d(B * D)), dim3(256), 0, (hipStream_t)stream,
+               u, loc, scale, g, B, D, grad_u);
     return DPK_OK;
 }
 
@@ -959,8 +955,8 @@ static int mlp_check(int64_t B, int D, int n_hidden, const float *const *W, cons
 }
 
 // forward of the MLP into ws (H[i], Z)
-static void mlp_forward(const MlpWs &w, const float *x, int64_t B, int D, const float *mask, int n_hidden,
-                        const float *const *W, const float *const *b, const int32_t *widths, hipStream_t st) {
+static int mlp_forward(const MlpWs &w, const float *x, int64_t B, int D, const float *mask, int n_hidden,
+                       const float *const *W, const float *const *b, const int32_t *widths, hipStream_t st) {
     const float *in = x;
     int in_w = D;
     for (int i = 0; i <= n_hidden; ++i) {
@@ -969,10 +965,11 @@ static void mlp_forward(const MlpWs &w, const float *x, int64_t B, int D, const 
         g.Bm = W[i]; g.sbk = 1; g.sbn = in_w;
         g.C = (i < n_hidden) ? w.H[i] : w.Z; g.ldc = widths[i];
         g.M = (int)B; g.N = widths[i]; g.K = in_w; g.bias = b[i]; g.relu = (i < n_hidden);
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
         in = g.C;
         in_w = widths[i];
     }
+    return DPK_OK;
 }
 
 extern "C" int64_t dpk_coupling1d_mlp_workspace_bytes(int64_t B, int32_t n_hidden, const int32_t *widths,
@@ -996,10 +993,9 @@ extern "C" int dpk_coupling1d_mlp_forward(const float *x, int64_t B, int32_t D, 
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(x && out && ldj, DPK_EINVAL, "coupling1d_mlp_forward: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    mlp_forward(w, x, B, D, mask, n_hidden, W, b, widths, st);
-    DPK_LAUNCH(coupling_fwd_elem_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x, w.Z, inv_mask, act_weight, B, D,
-                       affine, inverse, out, ldj);
-    DPK_CHECK_LAUNCH("coupling1d_mlp_forward");
+    DPK_TRY(mlp_forward(w, x, B, D, mask, n_hidden, W, b, widths, st));
+    DPK_LAUNCH("coupling1d_mlp_forward", coupling_fwd_elem_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x, w.Z, inv_mask,
+               act_weight, B, D, affine, inverse, out, ldj);
     return DPK_OK;
 }
 
@@ -1022,16 +1018,16 @@ static int mlp_backward_dir(const float *x, int64_t B, int32_t D, const float *m
     if (B == 0) {
         int in_w = D;
         for (int i = 0; i <= n_hidden; ++i) {
-            if (grad_W && grad_W[i]) (void)hipMemsetAsync(grad_W[i], 0, (size_t)widths[i] * in_w * 4, st);
-            if (grad_b && grad_b[i]) (void)hipMemsetAsync(grad_b[i], 0, (size_t)widths[i] * 4, st);
+            if (grad_W && grad_W[i]) DPK_REQUIRE(hipMemsetAsync(grad_W[i], 0, (size_t)widths[i] * in_w * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+            if (grad_b && grad_b[i]) DPK_REQUIRE(hipMemsetAsync(grad_b[i], 0, (size_t)widths[i] * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
             in_w = widths[i];
         }
         return DPK_OK;
     }
     DPK_REQUIRE(x && grad_x && (grad_u || grad_ildj), DPK_EINVAL, "coupling1d_mlp_backward: null pointer");
-    if (!ws_holds_forward) mlp_forward(w, x, B, D, mask, n_hidden, W, b, widths, st);
-    DPK_LAUNCH(coupling_bwd_elem_kernel, dim3(grid1d(B * 64, 256, 1024)), dim3(256), 0, st, x, w.Z, inv_mask, act_weight,
-                       grad_u, grad_ildj, B, D, affine, inverse, grad_x, grad_act);
+    if (!ws_holds_forward) DPK_TRY(mlp_forward(w, x, B, D, mask, n_hidden, W, b, widths, st));
+    DPK_LAUNCH("coupling_bwd_elem_kernel", coupling_bwd_elem_kernel, dim3(grid1d(B * 64, 256, 1024)), dim3(256), 0, st,
+               x, w.Z, inv_mask, act_weight, grad_u, grad_ildj, B, D, affine, inverse, grad_x, grad_act);
     // back through the layers: dOut starts as dZ (in w.Z)
     float *dout = w.Z;
     float *spare[2] = {w.dA, w.dB};
@@ -1045,25 +1041,25 @@ static int mlp_backward_dir(const float *x, int64_t B, int32_t D, const float *m
             g.A = dout; g.sam = 1; g.sak = ow;
             g.Bm = in; g.sbk = in_w; g.sbn = 1; g.nscale = (i == 0) ? mask : nullptr;
             g.C = grad_W[i]; g.ldc = in_w; g.M = ow; g.N = in_w; g.K = (int)B;
-            launch_gemm(g, st);
+            DPK_TRY(launch_gemm(g, st));
         }
         if (grad_b && grad_b[i])
-            DPK_LAUNCH(colsum_kernel, dim3(cdiv(ow, kRC)), dim3(kRThreads), 0, st, dout, B, ow, (int64_t)ow, grad_b[i]);
+            DPK_LAUNCH("colsum_kernel", colsum_kernel, dim3(cdiv(ow, kRC)), dim3(kRThreads), 0, st, dout, B, ow,
+                       (int64_t)ow, grad_b[i]);
         g = GemmArgs{};
         g.A = dout; g.sam = ow; g.sak = 1;
         g.Bm = W[i]; g.sbk = in_w; g.sbn = 1;
         g.M = (int)B; g.N = in_w; g.K = ow;
         if (i == 0) {   // grad_x += mask * (dOut W0)
             g.C = grad_x; g.ldc = D; g.nscale = mask; g.accumulate = 1;
-            launch_gemm(g, st);
+            DPK_TRY(launch_gemm(g, st));
         } else {        // dIn = (dOut W_i) * [H_{i-1} > 0]
             float *dst = spare[i & 1];
             g.C = dst; g.ldc = in_w; g.gate = w.H[i - 1]; g.ldg = in_w;
-            launch_gemm(g, st);
+            DPK_TRY(launch_gemm(g, st));
             dout = dst;
         }
     }
-    DPK_CHECK_LAUNCH("coupling1d_mlp_backward");
     return DPK_OK;
 }
 

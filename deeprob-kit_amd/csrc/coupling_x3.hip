@@ -1347,9 +1347,7 @@ static int x3_launch(const X3Args &a, hipStream_t st) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
     const int cus = device_cus();
     const int grid = a.ntiles < cus ? a.ntiles : cus;
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_COUPLING1D);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DPK_KERNEL_COUPLING1D, st);
 #ifdef DPK_X3_TIMELINE
     X3Args at = a;
     at.dbg = nullptr;
@@ -1357,7 +1355,7 @@ static int x3_launch(const X3Args &a, hipStream_t st) {
         (void)hipMalloc(&at.dbg, 8 * 64 * 8 * 8);
         (void)hipMemset(at.dbg, 0, 8 * 64 * 8 * 8);
     }
-    DPK_LAUNCH(kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, at);
+    DPK_LAUNCH("coupling_x3_kernel", kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, at);
     if (at.dbg) {   // synchronous read-back: measurement builds only
         std::vector<long long> hb(8 * 64 * 8);
         (void)hipStreamSynchronize(st);
@@ -1375,11 +1373,10 @@ static int x3_launch(const X3Args &a, hipStream_t st) {
             fprintf(stderr, "\n");
         }
     }
+    prof.stop();   // (behind the read-back, as this variant always had it)
 #else
-    DPK_LAUNCH(kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
+    DPK_LAUNCH_IN(prof, "coupling_x3_kernel", kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
 #endif
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("coupling_x3_kernel");
     return DPK_OK;
 }
 
@@ -1403,9 +1400,7 @@ static int x1_launch(const X3Args &a_in, hipStream_t st) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
     const int cus = device_cus();
     const int grid = a.ntiles < cus ? a.ntiles : cus;
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_COUPLING1D);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DPK_KERNEL_COUPLING1D, st);
 #ifdef DPK_X3_TIMELINE
     if (getenv("DPK_X3_TIMELINE")) {
         (void)hipMalloc(&a.dbg, 8 * 64 * 8 * 8);
@@ -1413,8 +1408,10 @@ static int x1_launch(const X3Args &a_in, hipStream_t st) {
         if (atoi(getenv("DPK_X3_TIMELINE")) == 2) a.accumulate = 7;
     }
 #endif
-    DPK_LAUNCH(kern, dim3(grid), dim3(512), lds, st, a);
-#ifdef DPK_X3_TIMELINE
+#ifndef DPK_X3_TIMELINE
+    DPK_LAUNCH_IN(prof, "coupling_x1_kernel", kern, dim3(grid), dim3(512), lds, st, a);
+#else
+    DPK_LAUNCH("coupling_x1_kernel", kern, dim3(grid), dim3(512), lds, st, a);
     if (a.dbg) {   // synchronous read-back: measurement builds only
         std::vector<long long> hb(8 * 64 * 8);
         (void)hipStreamSynchronize(st);
@@ -1432,9 +1429,8 @@ static int x1_launch(const X3Args &a_in, hipStream_t st) {
             fprintf(stderr, "\n");
         }
     }
+    prof.stop();   // (behind the read-back)
 #endif
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("coupling_x1_kernel");
     return DPK_OK;
 }
 
@@ -1489,11 +1485,11 @@ static int x3_forward_common(const float *x, int64_t B, int32_t D, int32_t maske
         p.D = D; p.U = units; p.pm = masked_parity; p.affine = affine; p.g = g;
         p.w1t = w.w1t; p.w2t = w.w2t; p.b1f = w.b1f; p.scales = w.scales;
         p.gate = &w.check->gate;
-        DPK_LAUNCH(coupling_x3_check_kernel, dim3(kX3CheckBlocks), dim3(256), 0, st, p, w.check, verify ? 1 : 0);
+        DPK_LAUNCH("coupling_x3_check_kernel", coupling_x3_check_kernel, dim3(kX3CheckBlocks), dim3(256), 0, st, p,
+                   w.check, verify ? 1 : 0);
         const int64_t total = (int64_t)g.NCH1 * 2 * g.NU * 64 + (int64_t)g.NPT * (units / 16) * 2 * 64 + (int64_t)g.NPT * 32 +
                               units;
-        DPK_LAUNCH(coupling_x3_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, p);
-        DPK_CHECK_LAUNCH("coupling_x3_pack_kernel");
+        DPK_LAUNCH("coupling_x3_pack_kernel", coupling_x3_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, p);
     }
     X3Args a{};
     a.x = x; a.out = out; a.ldj = ldj; a.B = B; a.D = D; a.U = units; a.pm = masked_parity; a.inverse = inverse;
@@ -1502,9 +1498,8 @@ static int x3_forward_common(const float *x, int64_t B, int32_t D, int32_t maske
     a.in_scale = in_scale; a.in_shift = in_shift;
     const bool once = x1_shape_ok(D);
     if (base) {
-        DPK_LAUNCH(x3_base_prep_kernel, dim3(1), dim3(256), 0, st, base->out_scale, base->out_shift, base->loc, base->scale,
-                   base->ildj_const, D, w.base_ac);
-        DPK_CHECK_LAUNCH("x3_base_prep_kernel");
+        DPK_LAUNCH("x3_base_prep_kernel", x3_base_prep_kernel, dim3(1), dim3(256), 0, st, base->out_scale,
+                   base->out_shift, base->loc, base->scale, base->ildj_const, D, w.base_ac);
         a.base_ac = w.base_ac; a.ildj_in = base->ildj_in; a.ll_out = base->ll;
         if (once) switch (units / 32) {
             case 1: return affine ? x1_launch<true, 1, true>(a, st) : x1_launch<false, 1, true>(a, st);
@@ -1561,9 +1556,10 @@ extern "C" int dpk_coupling1d_pairs_tables(int32_t n, const dpk_pairs_tables_arg
         m.st[l] = w.check;
         m.verify[l] = verify ? 1 : 0;
     }
-    DPK_LAUNCH(coupling_x3_check_many_kernel, dim3(n * kX3CheckBlocks), dim3(256), 0, st, m);
-    DPK_LAUNCH(coupling_x3_pack_many_kernel, dim3(n * kX3PackBlocks), dim3(256), 0, st, m);
-    DPK_CHECK_LAUNCH("coupling_x3_pack_many_kernel");
+    DPK_LAUNCH("coupling_x3_check_many_kernel", coupling_x3_check_many_kernel, dim3(n * kX3CheckBlocks), dim3(256), 0,
+               st, m);
+    DPK_LAUNCH("coupling_x3_pack_many_kernel", coupling_x3_pack_many_kernel, dim3(n * kX3PackBlocks), dim3(256), 0, st,
+               m);
     return DPK_OK;
 }
 

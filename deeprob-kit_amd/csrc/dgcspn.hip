@@ -279,18 +279,20 @@ __global__ __launch_bounds__(256) void spatial_product_bwd_dw_kernel(const float
         gin[pl * HW + ip] = acc;
     }
 }
-static void launch_product_bwd(const float *g, int64_t B, const ProdGeom &q, float *gin, hipStream_t st) {
+static int launch_product_bwd(const float *g, int64_t B, const ProdGeom &q, float *gin, hipStream_t st) {
     if (q.depthwise && q.kh * q.kw <= 4) {
         const int64_t planes = B * q.C, cols = cdiv(q.H * q.W, 256);
         int64_t slices = cdiv(4096, cols);                      // about 16 k waves
         int64_t pslice = cdiv(planes, slices);
         if (pslice < 4) pslice = 4;
         slices = cdiv(planes, pslice);
-        DPK_LAUNCH(spatial_product_bwd_dw_kernel, dim3((unsigned)cols, (unsigned)slices), dim3(256), 0, st, g, planes, q,
-                   (int)pslice, gin);
+        DPK_LAUNCH("spatial_product_bwd_dw_kernel", spatial_product_bwd_dw_kernel,
+                   dim3((unsigned)cols, (unsigned)slices), dim3(256), 0, st, g, planes, q, (int)pslice, gin);
     } else {
-        DPK_LAUNCH(spatial_product_bwd_kernel, dim3(grid_cap(B * q.C * q.H * q.W, 256)), dim3(256), 0, st, g, B, q, gin);
+        DPK_LAUNCH("spatial_product_bwd_kernel", spatial_product_bwd_kernel, dim3(grid_cap(B * q.C * q.H * q.W, 256)),
+                   dim3(256), 0, st, g, B, q, gin);
     }
+    return DPK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1225,9 +1227,9 @@ static int spatial_gaussian_forward_impl(const float *x, const float *loc, const
             int64_t bslice = cdiv(B, slices);
             if (bslice < 8) bslice = 8;
             slices = cdiv(B, bslice);
-            DPK_LAUNCH(spatial_gaussian_fwd_fast4_kernel, dim3((unsigned)blocks, 1, (unsigned)slices), dim3(256),
-                       0, (hipStream_t)stream, x, loc, scale, B, K, C, HW, (int)bslice, out);
-            DPK_CHECK_LAUNCH("spatial_gaussian_fwd_fast4_kernel");
+            DPK_LAUNCH("spatial_gaussian_fwd_fast4_kernel", spatial_gaussian_fwd_fast4_kernel,
+                       dim3((unsigned)blocks, 1, (unsigned)slices), dim3(256), 0, (hipStream_t)stream, x, loc, scale, B,
+                       K, C, HW, (int)bslice, out);
             return DPK_OK;
         }
         const int64_t cols = cdiv(HW, 64), kb = cdiv(K, 4);
@@ -1235,14 +1237,13 @@ static int spatial_gaussian_forward_impl(const float *x, const float *loc, const
         int64_t bslice = cdiv(B, slices);
         if (bslice < 8) bslice = 8;
         slices = cdiv(B, bslice);
-        DPK_LAUNCH(spatial_gaussian_fwd_fast_kernel, dim3((unsigned)cols, (unsigned)kb, (unsigned)slices),
-                           dim3(256), 0, (hipStream_t)stream, x, loc, scale, B, K, C, HW, (int)bslice, out);
-        DPK_CHECK_LAUNCH("spatial_gaussian_fwd_fast_kernel");
+        DPK_LAUNCH("spatial_gaussian_fwd_fast_kernel", spatial_gaussian_fwd_fast_kernel,
+                   dim3((unsigned)cols, (unsigned)kb, (unsigned)slices), dim3(256), 0, (hipStream_t)stream, x, loc,
+                   scale, B, K, C, HW, (int)bslice, out);
         return DPK_OK;
     }
-    DPK_LAUNCH(spatial_gaussian_fwd_kernel, dim3(grid_cap(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       x, loc, scale, B, K, C, H * W, out, drop_p, seed);
-    DPK_CHECK_LAUNCH("spatial_gaussian_fwd_kernel");
+    DPK_LAUNCH("spatial_gaussian_fwd_kernel", spatial_gaussian_fwd_kernel, dim3(grid_cap(total, 256)), dim3(256), 0,
+               (hipStream_t)stream, x, loc, scale, B, K, C, H * W, out, drop_p, seed);
     return DPK_OK;
 }
 extern "C" int dpk_spatial_gaussian_forward(const float *x, const float *loc, const float *scale, int64_t B,
@@ -1269,14 +1270,14 @@ static int spatial_gaussian_backward_impl(const float *x, const float *g, const 
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(x && g, DPK_EINVAL, "spatial_gaussian_backward: null pointer");
     if (grad_x)
-        DPK_LAUNCH(spatial_gaussian_bwd_x_kernel, dim3(grid_cap(B * C * HW, 256)), dim3(256), 0, st, x, g,
-                           loc, scale, B, K, C, HW, grad_x, drop_p, seed);
+        DPK_LAUNCH("spatial_gaussian_bwd_x_kernel", spatial_gaussian_bwd_x_kernel, dim3(grid_cap(B * C * HW, 256)),
+                   dim3(256), 0, st, x, g, loc, scale, B, K, C, HW, grad_x, drop_p, seed);
     if (grad_loc || grad_scale) {
         const int bslice = 64;
-        DPK_LAUNCH(spatial_gaussian_bwd_p_kernel, dim3(cdiv((int64_t)K * C * HW, 256), cdiv(B, bslice)),
-                           dim3(256), 0, st, x, g, loc, scale, B, K, C, HW, bslice, grad_loc, grad_scale, drop_p, seed);
+        DPK_LAUNCH("spatial_gaussian_bwd", spatial_gaussian_bwd_p_kernel,
+                   dim3(cdiv((int64_t)K * C * HW, 256), cdiv(B, bslice)), dim3(256), 0, st, x, g, loc, scale, B, K, C,
+                   HW, bslice, grad_loc, grad_scale, drop_p, seed);
     }
-    DPK_CHECK_LAUNCH("spatial_gaussian_bwd");
     return DPK_OK;
 }
 extern "C" int dpk_spatial_gaussian_backward(const float *x, const float *g, const float *loc, const float *scale,
@@ -1317,9 +1318,8 @@ extern "C" int dpk_spatial_product_forward(const float *in, int64_t B, int32_t C
     if (rc) return rc;
     if (B <= 0) return B == 0 ? DPK_OK : DPK_EINVAL;
     DPK_REQUIRE(in && out, DPK_EINVAL, "spatial_product: null pointer");
-    DPK_LAUNCH(spatial_product_fwd_kernel, dim3(grid_cap(B * OC * OH * OW, 256)), dim3(256), 0,
-                       (hipStream_t)stream, in, B, q, out);
-    DPK_CHECK_LAUNCH("spatial_product_fwd_kernel");
+    DPK_LAUNCH("spatial_product_fwd_kernel", spatial_product_fwd_kernel, dim3(grid_cap(B * OC * OH * OW, 256)),
+               dim3(256), 0, (hipStream_t)stream, in, B, q, out);
     return DPK_OK;
 }
 
@@ -1332,9 +1332,7 @@ extern "C" int dpk_spatial_product_backward(const float *g, int64_t B, int32_t C
     if (rc) return rc;
     if (B <= 0) return B == 0 ? DPK_OK : DPK_EINVAL;
     DPK_REQUIRE(g && grad_in, DPK_EINVAL, "spatial_product_backward: null pointer");
-    launch_product_bwd(g, B, q, grad_in, (hipStream_t)stream);
-    DPK_CHECK_LAUNCH("spatial_product_bwd_kernel");
-    return DPK_OK;
+    return launch_product_bwd(g, B, q, grad_in, (hipStream_t)stream);
 }
 
 // workspace: W, LW, glw of [Cout, Cin, H, W]
@@ -1354,18 +1352,21 @@ extern "C" int dpk_spatial_sum_forward(const float *x, const float *weight, int6
     DPK_REQUIRE(x && out, DPK_EINVAL, "spatial_sum: null pointer");
     float *Wl = (float *)ws, *LW = (float *)((char *)ws + seg);
     hipStream_t st = (hipStream_t)stream;
-    DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0, st, weight,
-                       Cout, Cin, HW, Wl, LW);
+    DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0,
+               st, weight, Cout, Cin, HW, Wl, LW);
     const dim3 grid(grid_cap(B * HW, 256)), block(256);
     if (Cin <= 8)
-        DPK_LAUNCH(spatial_sum_fwd_kernel<8>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW, out);
+        DPK_LAUNCH("spatial_sum_fwd_kernel", spatial_sum_fwd_kernel<8>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW,
+                   out);
     else if (Cin <= 16)
-        DPK_LAUNCH(spatial_sum_fwd_kernel<16>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW, out);
+        DPK_LAUNCH("spatial_sum_fwd_kernel", spatial_sum_fwd_kernel<16>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout,
+                   HW, out);
     else if (Cin <= 32)
-        DPK_LAUNCH(spatial_sum_fwd_kernel<32>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW, out);
+        DPK_LAUNCH("spatial_sum_fwd_kernel", spatial_sum_fwd_kernel<32>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout,
+                   HW, out);
     else
-        DPK_LAUNCH(spatial_sum_fwd_kernel<0>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW, out);
-    DPK_CHECK_LAUNCH("spatial_sum_fwd_kernel");
+        DPK_LAUNCH("spatial_sum_fwd_kernel", spatial_sum_fwd_kernel<0>, grid, block, 0, st, x, Wl, LW, B, Cin, Cout, HW,
+                   out);
     return DPK_OK;
 }
 
@@ -1379,8 +1380,8 @@ extern "C" int dpk_spatial_sum_backward(const float *x, const float *weight, con
     DPK_REQUIRE(ws_bytes >= 3 * seg, DPK_EWORKSPACE, "spatial_sum_backward: workspace too small");
     float *Wl = (float *)ws, *LW = (float *)((char *)ws + seg), *glw = (float *)((char *)ws + 2 * seg);
     hipStream_t st = (hipStream_t)stream;
-    DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0, st, weight,
-                       Cout, Cin, HW, Wl, LW);
+    DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0,
+               st, weight, Cout, Cin, HW, Wl, LW);
     if (grad_weight)
         DPK_REQUIRE(hipMemsetAsync(glw, 0, (size_t)Cout * Cin * HW * 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
     if (B > 0) {
@@ -1392,19 +1393,19 @@ extern "C" int dpk_spatial_sum_backward(const float *x, const float *weight, con
             int64_t bslice = cdiv(B, slices);
             if (bslice < 8) bslice = 8;
             slices = cdiv(B, bslice);
-            DPK_LAUNCH(spatial_sum_bwd8_kernel<false>, dim3((unsigned)cols, (unsigned)cdiv(slices, 4), (unsigned)halves),
-                       dim3(64, 4), 0, st, x, Wl, LW, out, g, B, Cin, Cout, HW, (int)bslice, grad_x,
-                       grad_weight ? glw : nullptr, ProdGeom{});
+            DPK_LAUNCH("spatial_sum_bwd8_kernel", spatial_sum_bwd8_kernel<false>,
+                       dim3((unsigned)cols, (unsigned)cdiv(slices, 4), (unsigned)halves), dim3(64, 4), 0, st, x, Wl, LW,
+                       out, g, B, Cin, Cout, HW, (int)bslice, grad_x, grad_weight ? glw : nullptr, ProdGeom{});
         } else {
             const int bslice = 16;
-            DPK_LAUNCH(spatial_sum_bwd_kernel, dim3(cdiv((int64_t)Cin * HW, 256), cdiv(B, bslice)), dim3(256),
-                               0, st, x, LW, out, g, B, Cin, Cout, HW, bslice, grad_x, grad_weight ? glw : nullptr);
+            DPK_LAUNCH("spatial_sum_bwd_kernel", spatial_sum_bwd_kernel,
+                       dim3(cdiv((int64_t)Cin * HW, 256), cdiv(B, bslice)), dim3(256), 0, st, x, LW, out, g, B, Cin,
+                       Cout, HW, bslice, grad_x, grad_weight ? glw : nullptr);
         }
     }
     if (grad_weight)
-        DPK_LAUNCH(spatial_softmax_jacobian_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0, st,
-                           glw, Wl, Cout, Cin, HW, grad_weight);
-    DPK_CHECK_LAUNCH("spatial_sum_bwd_kernel");
+        DPK_LAUNCH("spatial_sum_bwd_kernel", spatial_softmax_jacobian_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)),
+                   dim3(256), 0, st, glw, Wl, Cout, Cin, HW, grad_weight);
     return DPK_OK;
 }
 
@@ -1431,8 +1432,8 @@ extern "C" int dpk_spatial_prodsum_backward(const float *in, int64_t B, int32_t 
     hipStream_t st = (hipStream_t)stream;
     // (DPK_FLAG_PARAMS_CACHED: the forward of this very node left its tables in the workspace)
     if (!(flags & DPK_FLAG_PARAMS_CACHED))
-        DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0, st, weight, Cout, C, HW,
-                   Wl, LW);
+        DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256),
+                   0, st, weight, Cout, C, HW, Wl, LW);
     if (grad_weight)
         DPK_REQUIRE(hipMemsetAsync(glw, 0, (size_t)Cout * C * HW * 4, st) == hipSuccess, DPK_ELAUNCH, "memset");
     if (B > 0) {
@@ -1442,15 +1443,14 @@ extern "C" int dpk_spatial_prodsum_backward(const float *in, int64_t B, int32_t 
         int64_t bslice = cdiv(B, slices);
         if (bslice < 8) bslice = 8;
         slices = cdiv(B, bslice);
-        DPK_LAUNCH(spatial_sum_bwd8_kernel<true>, dim3((unsigned)cols, (unsigned)cdiv(slices, 4), (unsigned)halves),
-                   dim3(64, 4), 0, st, in, Wl, LW, out, g, B, C, Cout, HW, (int)bslice, grad_in ? grad_prod : nullptr,
-                   grad_weight ? glw : nullptr, q);
-        if (grad_in) launch_product_bwd(grad_prod, B, q, grad_in, st);
+        DPK_LAUNCH("spatial_sum_bwd8_kernel", spatial_sum_bwd8_kernel<true>,
+                   dim3((unsigned)cols, (unsigned)cdiv(slices, 4), (unsigned)halves), dim3(64, 4), 0, st, in, Wl, LW,
+                   out, g, B, C, Cout, HW, (int)bslice, grad_in ? grad_prod : nullptr, grad_weight ? glw : nullptr, q);
+        if (grad_in) DPK_TRY(launch_product_bwd(grad_prod, B, q, grad_in, st));
     }
     if (grad_weight)
-        DPK_LAUNCH(spatial_softmax_jacobian_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)), dim3(256), 0, st, glw, Wl,
-                   Cout, C, HW, grad_weight);
-    DPK_CHECK_LAUNCH("spatial_prodsum_backward");
+        DPK_LAUNCH("spatial_prodsum_backward", spatial_softmax_jacobian_kernel, dim3(grid_cap((int64_t)Cout * HW, 256)),
+                   dim3(256), 0, st, glw, Wl, Cout, C, HW, grad_weight);
     return DPK_OK;
 }
 
@@ -1500,16 +1500,14 @@ extern "C" int dpk_spatial_prodsum_forward(const float *in, int64_t B, int32_t C
     // DPK_FLAG_PARAMS_VERIFY: believed so, checked on the device)
     // (rebuilding IS the check here: the softmax pass costs what a fingerprint of the same bytes would)
     if (!(flags & DPK_FLAG_PARAMS_CACHED))
-        DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)), dim3(256), 0, st, weight,
-                   Cout, C, OHW, Wl, LW);
+        DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)),
+                   dim3(256), 0, st, weight, Cout, C, OHW, Wl, LW);
     // large batches of the 8 -> 8 channel level: pixel-resident weights, taps staged through LDS (dgcspn_stream.hip)
     const bool in_pm = (flags & DPK_FLAG_IN_PIXEL_MAJOR) != 0, out_pm = (flags & DPK_FLAG_OUT_PIXEL_MAJOR) != 0;
     if (stream_prodsum_ok(q, Cout, B, in)) return stream_prodsum_forward(in, B, q, Wl, LW, out, st, in_pm, out_pm);
     DPK_REQUIRE(!in_pm && !out_pm, DPK_EUNSUPPORTED, "spatial_prodsum: pixel-major maps only on the streaming route (dpk_spatial_level_streams)");
     const int Bi = (int)B;
-    hipEvent_t pev0, pev1;
-    profile_take(&pev0, &pev1, DPK_KERNEL_SPATIAL_PRODSUM);
-    if (pev0) (void)hipEventRecord(pev0, st);
+    Profile prof(DPK_KERNEL_SPATIAL_PRODSUM, st);
     // Wide levels (C >= 16): a thread reads Cout x C weights of its pixel per NB samples -- 800 KB per work-group at
     // 32 -> 32 channels on a 14 x 14 map, 3.3 GB of L2 traffic per launch with one sample group per work-group (round-4
     // trace: 865 us).  There a work-group is 16 pixels x 16 groups of samples: the 16 groups read the same weights.
@@ -1527,19 +1525,22 @@ extern "C" int dpk_spatial_prodsum_forward(const float *in, int64_t B, int32_t C
                            (OH - 1) * sh + dh < H;
 #define DPK_WIDE(CIN, PR)                                                                                                  \
     do {                                                                                                                   \
-        if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_kernel<CIN, PR>), 64 * 1024)) return lrc; \
-        DPK_LAUNCH((spatial_prodsum_wide_kernel<CIN, PR>), wgrid, dim3(256), lds, st, in, Wl, LW, Bi, q, Cout, out, per_wg);   \
+        DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_kernel<CIN, PR>), 64 * 1024)); \
+        DPK_LAUNCH_IN(prof, "spatial_prodsum_wide_kernel", (spatial_prodsum_wide_kernel<CIN, PR>), wgrid, dim3(256), lds,  \
+                      st, in, Wl, LW, Bi, q, Cout, out, per_wg);                                                           \
     } while (0)
         // (the pooling level with an even output width: two pixels per thread, 16-byte tap loads -- rows 16-byte aligned)
         const bool pool2 = pairs && sh == 2 && sw == 2 && dh == 1 && (OW % 2) == 0 && (W % 4) == 0 && (OHW % 2) == 0 &&
                            (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
         if (pool2 && (C == 16 || C == 32)) {
             if (C == 16) {
-                if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_pool_kernel<16>), 64 * 1024)) return lrc;
-                DPK_LAUNCH((spatial_prodsum_wide_pool_kernel<16>), wgrid, dim3(256), lds, st, in, Wl, LW, Bi, q, Cout, out, per_wg);
+                DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_pool_kernel<16>), 64 * 1024));
+                DPK_LAUNCH_IN(prof, "spatial_prodsum_wide_kernel", (spatial_prodsum_wide_pool_kernel<16>), wgrid,
+                              dim3(256), lds, st, in, Wl, LW, Bi, q, Cout, out, per_wg);
             } else {
-                if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_pool_kernel<32>), 64 * 1024)) return lrc;
-                DPK_LAUNCH((spatial_prodsum_wide_pool_kernel<32>), wgrid, dim3(256), lds, st, in, Wl, LW, Bi, q, Cout, out, per_wg);
+                DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&spatial_prodsum_wide_pool_kernel<32>), 64 * 1024));
+                DPK_LAUNCH_IN(prof, "spatial_prodsum_wide_kernel", (spatial_prodsum_wide_pool_kernel<32>), wgrid,
+                              dim3(256), lds, st, in, Wl, LW, Bi, q, Cout, out, per_wg);
             }
         } else if (C == 16) {
             if (pairs) DPK_WIDE(16, true); else DPK_WIDE(16, false);
@@ -1547,8 +1548,6 @@ extern "C" int dpk_spatial_prodsum_forward(const float *in, int64_t B, int32_t C
             if (pairs) DPK_WIDE(32, true); else DPK_WIDE(32, false);
         }
 #undef DPK_WIDE
-        if (pev1) (void)hipEventRecord(pev1, st);
-        DPK_CHECK_LAUNCH("spatial_prodsum_wide_kernel");
         return DPK_OK;
     }
     int slots = 1, ptile = 256;
@@ -1560,8 +1559,8 @@ extern "C" int dpk_spatial_prodsum_forward(const float *in, int64_t B, int32_t C
         slots = 256 / OHW;
     }
 #define DPK_PRODSUM(CMAX, NB)                                                                                      \
-    DPK_LAUNCH((spatial_prodsum_fwd_kernel<CMAX, NB>), dim3(cdiv(OHW, ptile), cdiv(Bi, NB * slots)), dim3(256), 0, st, \
-                       in, Wl, LW, Bi, q, Cout, out, slots)
+    DPK_LAUNCH_IN(prof, "spatial_prodsum_fwd_kernel", (spatial_prodsum_fwd_kernel<CMAX, NB>),                      \
+                  dim3(cdiv(OHW, ptile), cdiv(Bi, NB * slots)), dim3(256), 0, st, in, Wl, LW, Bi, q, Cout, out, slots)
     if (C <= 4)
         DPK_PRODSUM(4, 4);
     else if (C <= 8)
@@ -1571,8 +1570,6 @@ extern "C" int dpk_spatial_prodsum_forward(const float *in, int64_t B, int32_t C
     else
         DPK_PRODSUM(32, 1);   // (NB = 2 / 4: 256 registers or scratch, one wave per SIMD in a latency chain over the outputs -- measured slower)
 #undef DPK_PRODSUM
-    if (pev1) (void)hipEventRecord(pev1, st);
-    DPK_CHECK_LAUNCH("spatial_prodsum_fwd_kernel");
     return DPK_OK;
 }
 
@@ -1755,7 +1752,8 @@ extern "C" int dpk_spatial_leaf_prodsum_forward(const float *x, const float *loc
         float *Wl = (float *)ws, *LW = (float *)((char *)ws + seg);
         hipStream_t st = (hipStream_t)stream;
         if (!(flags & DPK_FLAG_PARAMS_CACHED))
-            DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)), dim3(256), 0, st, weight, Cout, K, OHW, Wl, LW);
+            DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)),
+                       dim3(256), 0, st, weight, Cout, K, OHW, Wl, LW);
         return stream_leaf_prodsum_forward(x, loc, scale, Cx, B, q, Wl, LW, out, st, (flags & DPK_FLAG_OUT_PIXEL_MAJOR) != 0);
     }
     const bool ok = (K == 8 || K == 16 || K == 32) && (pool || K >= leaf_min_k) && Cout <= 32 && kh == 2 && kw == 2 &&
@@ -1771,19 +1769,19 @@ extern "C" int dpk_spatial_leaf_prodsum_forward(const float *x, const float *loc
     float *Wl = (float *)ws, *LW = (float *)((char *)ws + seg);
     hipStream_t st = (hipStream_t)stream;
     if (!(flags & DPK_FLAG_PARAMS_CACHED))
-        DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)), dim3(256), 0, st, weight, Cout, K, OHW, Wl, LW);
+        DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW, 256)),
+                   dim3(256), 0, st, weight, Cout, K, OHW, Wl, LW);
     const int Bi = (int)B;
     const int ptiles = cdiv(OHW, kWidePix);
     int per_wg = (int)std::max<int64_t>(32, cdiv((int64_t)Bi * ptiles, 4 * (int64_t)device_cus()));
     per_wg = (int)align_up(per_wg, 32);
     const dim3 wgrid(ptiles * (int)align_up(cdiv(Bi, per_wg), 8));   // (one-dimensional: wide_block_of)
-    hipEvent_t pev0, pev1;
-    profile_take(&pev0, &pev1, DPK_KERNEL_SPATIAL_PRODSUM);
-    if (pev0) (void)hipEventRecord(pev0, st);
+    Profile prof(DPK_KERNEL_SPATIAL_PRODSUM, st);
 #define DPK_LEAF_FUSED(KERN)                                                                                               \
     do {                                                                                                                   \
-        if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&KERN), 160 * 1024)) return lrc;                  \
-        DPK_LAUNCH((KERN), wgrid, dim3(256), lds, st, x, loc, scale, Cx, Wl, LW, Bi, q, Cout, out, per_wg);              \
+        DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&KERN), 160 * 1024));                                    \
+        DPK_LAUNCH_IN(prof, "spatial_leaf_pool_prodsum_kernel", (KERN), wgrid, dim3(256), lds, st, x, loc, scale, Cx, Wl,  \
+                      LW, Bi, q, Cout, out, per_wg);                                                                       \
     } while (0)
     if (pool && K == 16) DPK_LEAF_FUSED(spatial_leaf_pool_prodsum_kernel<16>);
     else if (pool) DPK_LEAF_FUSED(spatial_leaf_pool_prodsum_kernel<32>);
@@ -1791,8 +1789,6 @@ extern "C" int dpk_spatial_leaf_prodsum_forward(const float *x, const float *loc
     else if (K == 16) DPK_LEAF_FUSED(spatial_leaf_prodsum_kernel<16>);
     else DPK_LEAF_FUSED(spatial_leaf_prodsum_kernel<32>);
 #undef DPK_LEAF_FUSED
-    if (pev1) (void)hipEventRecord(pev1, st);
-    DPK_CHECK_LAUNCH("spatial_leaf_pool_prodsum_kernel");
     return DPK_OK;
 }
 
@@ -2005,9 +2001,10 @@ extern "C" int dpk_spatial_sumprodroot_forward(const float *in, int64_t B, int32
     float *Wl = (float *)ws, *LW = (float *)((char *)ws + seg), *LWr = (float *)((char *)ws + 2 * seg);
     hipStream_t st = (hipStream_t)stream;
     if (!(flags & DPK_FLAG_PARAMS_CACHED)) {   // (flags as in dpk_spatial_prodsum_forward: VERIFY = rebuild)
-        DPK_LAUNCH(spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW5, 256)), dim3(256), 0, st, sum_weight,
-                   Cout, C, OHW5, Wl, LW);
-        DPK_LAUNCH(rowwise_logsoftmax_kernel, dim3(K), dim3(256), 0, st, root_weight, K, Cout * OHW6, LWr);
+        DPK_LAUNCH("spatial_softmax_kernel", spatial_softmax_kernel, dim3(grid_cap((int64_t)Cout * OHW5, 256)),
+                   dim3(256), 0, st, sum_weight, Cout, C, OHW5, Wl, LW);
+        DPK_LAUNCH("rowwise_logsoftmax_kernel", rowwise_logsoftmax_kernel, dim3(K), dim3(256), 0, st, root_weight, K,
+                   Cout * OHW6, LWr);
     }
     {
         // streaming kernel when the workspace carries its per-wave partials (.._workspace_bytes_batch)
@@ -2021,13 +2018,9 @@ extern "C" int dpk_spatial_sumprodroot_forward(const float *in, int64_t B, int32
                 "spatial_sumprodroot: a pixel-major input only on the streaming route (dpk_spatial_level_streams)");
     constexpr int kNB = 2;
     const int threads = (int)align_up(OHW6, 64);
-    hipEvent_t pev0, pev1;
-    profile_take(&pev0, &pev1, DPK_KERNEL_SPATIAL_SUMPRODROOT);
-    if (pev0) (void)hipEventRecord(pev0, st);
-    DPK_LAUNCH((spatial_sumprodroot_fwd_kernel<8, kNB>), dim3(cdiv((int)B, kNB)), dim3(threads), 0, st, in, Wl,
-                       LW, (int)B, q5, Cout, q6, LWr, K, out);
-    if (pev1) (void)hipEventRecord(pev1, st);
-    DPK_CHECK_LAUNCH("spatial_sumprodroot_fwd_kernel");
+    Profile prof(DPK_KERNEL_SPATIAL_SUMPRODROOT, st);
+    DPK_LAUNCH_IN(prof, "spatial_sumprodroot_fwd_kernel", (spatial_sumprodroot_fwd_kernel<8, kNB>),
+                  dim3(cdiv((int)B, kNB)), dim3(threads), 0, st, in, Wl, LW, (int)B, q5, Cout, q6, LWr, K, out);
     return DPK_OK;
 }
 
@@ -2055,9 +2048,9 @@ extern "C" int dpk_spatial_prodroot_forward(const float *in, int64_t B, int32_t 
     DPK_REQUIRE(in && out, DPK_EINVAL, "spatial_prodroot: null pointer");
     hipStream_t st = (hipStream_t)stream;
     float *LW = (float *)ws;
-    DPK_LAUNCH(rowwise_logsoftmax_kernel, dim3(K), dim3(256), 0, st, weight, K, M, LW);
-    DPK_LAUNCH(spatial_prodroot_fwd_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, in, LW, B, q, K, out);
-    DPK_CHECK_LAUNCH("spatial_prodroot_fwd_kernel");
+    DPK_LAUNCH("rowwise_logsoftmax_kernel", rowwise_logsoftmax_kernel, dim3(K), dim3(256), 0, st, weight, K, M, LW);
+    DPK_LAUNCH("spatial_prodroot_fwd_kernel", spatial_prodroot_fwd_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, in, LW,
+               B, q, K, out);
     return DPK_OK;
 }
 
@@ -2088,7 +2081,7 @@ extern "C" int dpk_spatial_tables(int32_t n, const dpk_spatial_tables_args *leve
         }
     }
     a.blk0[n] = blocks;
-    DPK_LAUNCH(spatial_tables_many_kernel, dim3(blocks + (a.rw ? a.K : 0)), dim3(256), 0, (hipStream_t)stream, a);
-    DPK_CHECK_LAUNCH("spatial_tables_many_kernel");
+    DPK_LAUNCH("spatial_tables_many_kernel", spatial_tables_many_kernel, dim3(blocks + (a.rw ? a.K : 0)), dim3(256), 0,
+               (hipStream_t)stream, a);
     return DPK_OK;
 }

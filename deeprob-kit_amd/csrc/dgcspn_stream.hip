@@ -792,16 +792,12 @@ static int stream_launch(StreamArgs &a, const StreamPlan &pl, int64_t B, hipStre
                 MODE, a.q5.H, a.q5.W, a.q5.OH, a.q5.OW, pl.T, pl.cw, pl.nl, pl.nst, pl.CS, pl.stage_bytes,
                 pl.wg_per_cu, a.per_wg, a.slices, grid, pl.tile[0].nb,
                 pl.tile[0].nr[0] + pl.tile[0].nr[1] + pl.tile[0].nr[2] + pl.tile[0].nr[3]);
-    hipEvent_t pev0, pev1;
-    profile_take(&pev0, &pev1, kernel_id);
-    if (pev0) (void)hipEventRecord(pev0, st);
+    Profile prof(kernel_id, st);
     static const bool timeline = DPK_STREAM_TL && getenv("DPK_DGC_STREAM_TIMELINE") != nullptr;
     a.dbg = nullptr;
     if (timeline) (void)hipMalloc(&a.dbg, 16 * 16 * 8 * 8 + 64 + 4096 * 32);
     if (a.dbg) (void)hipMemset(a.dbg, 0, 16 * 16 * 8 * 8 + 64 + 4096 * 32);
-    DPK_LAUNCH(kern, dim3(grid), dim3((pl.cw + pl.nl) * 64), lds_bytes, st, a);
-    if (pev1) (void)hipEventRecord(pev1, st);
-    DPK_CHECK_LAUNCH("spatial_stream_kernel");
+    DPK_LAUNCH_IN(prof, "spatial_stream_kernel", kern, dim3(grid), dim3((pl.cw + pl.nl) * 64), lds_bytes, st, a);
     if (a.dbg) {   // measurement only: synchronous read-back of work-group 0's stamps
         std::vector<long long> h(16 * 16 * 8 + 8 + 4096 * 4);
         (void)hipStreamSynchronize(st);
@@ -904,9 +900,8 @@ int stream_sumprodroot_forward(const float *in, int64_t B, const ProdGeom &q5, c
     a.q6 = q6;
     int rc = stream_launch<1>(a, pl, B, st, DPK_KERNEL_SPATIAL_SUMPRODROOT, in_pm, false);
     if (rc) return rc;
-    DPK_LAUNCH(stream_root_combine_kernel, dim3(cdiv(B * K, 4)), dim3(256), 0, st, (const float *)partials, B,
-               pl.T * pl.cw, K, out);
-    DPK_CHECK_LAUNCH("stream_root_combine_kernel");
+    DPK_LAUNCH("stream_root_combine_kernel", stream_root_combine_kernel, dim3(cdiv(B * K, 4)), dim3(256), 0, st,
+               (const float *)partials, B, pl.T * pl.cw, K, out);
     return DPK_OK;
 }
 

@@ -415,9 +415,9 @@ extern "C" int dpk_flat_spn_topdown(float *x, int64_t B, int32_t D, const dpk_fl
     if (topdown_lds_fits(*c)) {
         const size_t lds = (size_t)topdown_lds_bytes(*c);
         if (mode == 0)
-            DPK_LAUNCH((flat_topdown_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
+            DPK_LAUNCH("flat_spn_topdown", (flat_topdown_kernel<true, false>), dim3(blocks), dim3(64), lds, st, a);
         else
-            DPK_LAUNCH((flat_topdown_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
+            DPK_LAUNCH("flat_spn_topdown", (flat_topdown_kernel<true, true>), dim3(blocks), dim3(64), lds, st, a);
     } else {
         const int64_t need = dpk_flat_spn_topdown_workspace_bytes(B, c);
         DPK_REQUIRE(ws && ws_bytes >= need, DPK_EWORKSPACE, "flat_spn_topdown: workspace %lld < %lld", (long long)ws_bytes,
@@ -429,11 +429,10 @@ extern "C" int dpk_flat_spn_topdown(float *x, int64_t B, int32_t D, const dpk_fl
         p += align_up((int64_t)c->n_sum * B, 256);
         a.reach = (u64 *)p;
         if (mode == 0)
-            DPK_LAUNCH((flat_topdown_kernel<false, false>), dim3(blocks), dim3(64), 0, st, a);
+            DPK_LAUNCH("flat_spn_topdown", (flat_topdown_kernel<false, false>), dim3(blocks), dim3(64), 0, st, a);
         else
-            DPK_LAUNCH((flat_topdown_kernel<false, true>), dim3(blocks), dim3(64), 0, st, a);
+            DPK_LAUNCH("flat_spn_topdown", (flat_topdown_kernel<false, true>), dim3(blocks), dim3(64), 0, st, a);
     }
-    DPK_CHECK_LAUNCH("flat_spn_topdown");
     return DPK_OK;
 }
 
@@ -442,8 +441,8 @@ extern "C" int dpk_flat_spn_backward(const float *lls, float *grads, int64_t B, 
     DPK_REQUIRE(B >= 0, DPK_EINVAL, "flat_spn_backward: bad sizes");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(lls && grads, DPK_EINVAL, "flat_spn_backward: null pointer");
-    DPK_LAUNCH(flat_backward_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, *c, lls, grads, B);
-    DPK_CHECK_LAUNCH("flat_spn_backward");
+    DPK_LAUNCH("flat_spn_backward", flat_backward_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream,
+               *c, lls, grads, B);
     return DPK_OK;
 }
 
@@ -471,9 +470,8 @@ extern "C" int dpk_flat_spn_em_step(const float *x, int64_t N, int32_t D, const 
     a.grads = (float *)(p + tab);
     a.utmp = (double *)(p + 2 * tab);
     hipStream_t st = (hipStream_t)stream;
-    DPK_LAUNCH(flat_em_tables_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, st, a);
-    DPK_CHECK_LAUNCH("flat_spn_em_step (tables)");
-    DPK_LAUNCH(flat_em_update_kernel, dim3((unsigned)c->n_nodes + 1), dim3(kUpdThreads), 0, st, a);
-    DPK_CHECK_LAUNCH("flat_spn_em_step (update)");
+    DPK_LAUNCH("flat_spn_em_step (tables)", flat_em_tables_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, st, a);
+    DPK_LAUNCH("flat_spn_em_step (update)", flat_em_update_kernel, dim3((unsigned)c->n_nodes + 1), dim3(kUpdThreads), 0,
+               st, a);
     return DPK_OK;
 }

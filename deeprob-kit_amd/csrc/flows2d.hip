@@ -646,13 +646,12 @@ int dpk_conv2d_prepare(const float *weight_v, const float *weight_g, int32_t Cou
     const bool bn = bn_weight != nullptr;
     DPK_REQUIRE(!bn || (bn_bias && bn_mean && bn_var && pre), DPK_EINVAL, "conv2d_prepare: incomplete BatchNorm2d");
     const int CoutPad = (int)align_up(Cout, kConvCO);
-    DPK_LAUNCH(conv2d_prepare_kernel, dim3(CoutPad + (bn ? 1 : 0)), dim3(256), 0, (hipStream_t)stream, weight_v, weight_g,
-               Cout, CoutPad, Cin, ks * ks, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, wpack, pre);
-    DPK_CHECK_LAUNCH("conv2d_prepare_kernel");
+    DPK_LAUNCH("conv2d_prepare_kernel", conv2d_prepare_kernel, dim3(CoutPad + (bn ? 1 : 0)), dim3(256), 0,
+               (hipStream_t)stream, weight_v, weight_g, Cout, CoutPad, Cin, ks * ks, bn_weight, bn_bias, bn_mean,
+               bn_var, bn_eps, wpack, pre);
     const int64_t nf = conv_frag_floats(Cout, Cin, ks);
-    DPK_LAUNCH(conv2d_frag_kernel, dim3((unsigned)cdiv(nf, 256)), dim3(256), 0, (hipStream_t)stream, wpack, Cout, CoutPad, Cin,
-               ks * ks, wpack + conv_valu_floats(Cout, Cin, ks), nf);
-    DPK_CHECK_LAUNCH("conv2d_frag_kernel");
+    DPK_LAUNCH("conv2d_frag_kernel", conv2d_frag_kernel, dim3((unsigned)cdiv(nf, 256)), dim3(256), 0,
+               (hipStream_t)stream, wpack, Cout, CoutPad, Cin, ks * ks, wpack + conv_valu_floats(Cout, Cin, ks), nf);
     return DPK_OK;
 }
 
@@ -702,7 +701,7 @@ int dpk_conv2d_forward(const float *in, int64_t in_bstride, int64_t B, int32_t C
             const dim3 lgrid((unsigned)cdiv(B, q.G), (unsigned)cdiv(Cout, 32));
             const int ntile = cdiv((int64_t)q.NP, 32);
 #define DPK_LDS_CASE(PRE_, NW_, TW_) \
-    DPK_LAUNCH((conv3x3_lds_kernel<PRE_, NW_, TW_>), lgrid, dim3(NW_ * 64), lds_bytes, st, a, wfrag, q)
+    DPK_LAUNCH("conv3x3_lds_kernel", (conv3x3_lds_kernel<PRE_, NW_, TW_>), lgrid, dim3(NW_ * 64), lds_bytes, st, a, wfrag, q)
             if (ntile <= 24) {
                 if (pre) DPK_LDS_CASE(true, 4, 6); else DPK_LDS_CASE(false, 4, 6);
             } else if (ntile <= 28) {   // (25 tiles on 5 waves x 5 tiles -- no padded tile -- measured 910 against 645 us:
@@ -712,7 +711,6 @@ int dpk_conv2d_forward(const float *in, int64_t in_bstride, int64_t B, int32_t C
                 if (pre) DPK_LDS_CASE(true, 4, 8); else DPK_LDS_CASE(false, 4, 8);
             }
 #undef DPK_LDS_CASE
-            DPK_CHECK_LAUNCH("conv3x3_lds_kernel");
             return DPK_OK;
         }
     }
@@ -721,16 +719,15 @@ int dpk_conv2d_forward(const float *in, int64_t in_bstride, int64_t B, int32_t C
         const int64_t slots = B * H * W;
         const dim3 mgrid((unsigned)cdiv(slots, 4 * 32 * kMfmaTiles), (unsigned)cdiv(Cout, 32));
         if (ks == 3) {
-            if (pre) DPK_LAUNCH((conv2d_mfma_kernel<3, true>), mgrid, blk, 0, st, a, wfrag);
-            else DPK_LAUNCH((conv2d_mfma_kernel<3, false>), mgrid, blk, 0, st, a, wfrag);
+            if (pre) DPK_LAUNCH("conv2d_mfma_kernel", (conv2d_mfma_kernel<3, true>), mgrid, blk, 0, st, a, wfrag);
+            else DPK_LAUNCH("conv2d_mfma_kernel", (conv2d_mfma_kernel<3, false>), mgrid, blk, 0, st, a, wfrag);
         } else {
-            if (pre) DPK_LAUNCH((conv2d_mfma_kernel<1, true>), mgrid, blk, 0, st, a, wfrag);
-            else DPK_LAUNCH((conv2d_mfma_kernel<1, false>), mgrid, blk, 0, st, a, wfrag);
+            if (pre) DPK_LAUNCH("conv2d_mfma_kernel", (conv2d_mfma_kernel<1, true>), mgrid, blk, 0, st, a, wfrag);
+            else DPK_LAUNCH("conv2d_mfma_kernel", (conv2d_mfma_kernel<1, false>), mgrid, blk, 0, st, a, wfrag);
         }
-        DPK_CHECK_LAUNCH("conv2d_mfma_kernel");
         return DPK_OK;
     }
-#define DPK_CONV_CASE(KS_, PRE_, MASK_) DPK_LAUNCH((conv2d_kernel<KS_, PRE_, MASK_>), grid, blk, 0, st, a)
+#define DPK_CONV_CASE(KS_, PRE_, MASK_) DPK_LAUNCH("conv2d_kernel", (conv2d_kernel<KS_, PRE_, MASK_>), grid, blk, 0, st, a)
     if (ks == 3) {
         if (pre && in_mask) DPK_CONV_CASE(3, true, true);
         else if (pre) DPK_CONV_CASE(3, true, false);
@@ -743,7 +740,6 @@ int dpk_conv2d_forward(const float *in, int64_t in_bstride, int64_t B, int32_t C
         else DPK_CONV_CASE(1, false, false);
     }
 #undef DPK_CONV_CASE
-    DPK_CHECK_LAUNCH("conv2d_kernel");
     return DPK_OK;
 }
 
@@ -755,9 +751,8 @@ int dpk_coupling2d_transform(const float *x, const float *z, const float *scale,
     DPK_REQUIRE((int64_t)C * H * W < INT32_MAX && B < INT32_MAX, DPK_EUNSUPPORTED, "coupling2d_transform: too large");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(x && z && out && ldj_out && (!affine || scale), DPK_EINVAL, "coupling2d_transform: null pointer");
-    DPK_LAUNCH(coupling2d_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, z, scale, inv_mask, C, H * W,
-               affine, reverse, inverse, ldj_in, out, ldj_out);
-    DPK_CHECK_LAUNCH("coupling2d_kernel");
+    DPK_LAUNCH("coupling2d_kernel", coupling2d_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, z,
+               scale, inv_mask, C, H * W, affine, reverse, inverse, ldj_in, out, ldj_out);
     return DPK_OK;
 }
 
@@ -768,9 +763,8 @@ int dpk_bn2d_bijector(const float *x, const float *weight, const float *bias, co
     DPK_REQUIRE((int64_t)C * H * W < INT32_MAX && B < INT32_MAX, DPK_EUNSUPPORTED, "bn2d_bijector: too large");
     if (B == 0) return DPK_OK;
     DPK_REQUIRE(x && weight && bias && mean && var && out && ldj_out, DPK_EINVAL, "bn2d_bijector: null pointer");
-    DPK_LAUNCH(bn2d_bijector_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x, weight, bias, mean, var,
-               eps, C, H * W, inverse, ldj_in, out, ldj_out);
-    DPK_CHECK_LAUNCH("bn2d_bijector_kernel");
+    DPK_LAUNCH("bn2d_bijector_kernel", bn2d_bijector_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x,
+               weight, bias, mean, var, eps, C, H * W, inverse, ldj_in, out, ldj_out);
     return DPK_OK;
 }
 
@@ -783,10 +777,8 @@ static int depth_perm(const float *full, int64_t B, int32_t C, int32_t H, int32_
     DPK_REQUIRE(full && table && part_a && (Ca == 4 * C || part_b), DPK_EINVAL, "%s: null pointer", who);
     const int64_t total = B * C * H * W;
     DPK_REQUIRE(total / 256 < INT32_MAX, DPK_EUNSUPPORTED, "%s: too large", who);
-    DPK_LAUNCH(space_to_depth_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
-               const_cast<float *>(full), total, C,
-               H, W, table, part_a, Ca, part_b, inverse);
-    DPK_CHECK_LAUNCH("space_to_depth_kernel");
+    DPK_LAUNCH("space_to_depth_kernel", space_to_depth_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
+               (hipStream_t)stream, const_cast<float *>(full), total, C, H, W, table, part_a, Ca, part_b, inverse);
     return DPK_OK;
 }
 

@@ -318,9 +318,8 @@ int dpk_channel_stats(const float *x, int64_t x_bstride, int64_t B, int32_t C, i
     DPK_REQUIRE(x_bstride >= (int64_t)C * H * W, DPK_EINVAL, "channel_stats: batch stride below C*H*W");
     const int64_t n_el = B * H * W;
     DPK_REQUIRE(n_el / kStatSpan < INT32_MAX, DPK_EUNSUPPORTED, "channel_stats: too large");
-    DPK_LAUNCH(channel_stats_kernel, dim3((unsigned)cdiv(n_el, kStatSpan), (unsigned)C), dim3(256), 0,
-               (hipStream_t)stream, x, x_bstride, n_el, H * W, C, sums, want_sq);
-    DPK_CHECK_LAUNCH("channel_stats_kernel");
+    DPK_LAUNCH("channel_stats_kernel", channel_stats_kernel, dim3((unsigned)cdiv(n_el, kStatSpan), (unsigned)C),
+               dim3(256), 0, (hipStream_t)stream, x, x_bstride, n_el, H * W, C, sums, want_sq);
     return DPK_OK;
 }
 
@@ -333,9 +332,9 @@ int dpk_channel_stats_backward(const float *x, int64_t x_bstride, int64_t B, int
     DPK_REQUIRE(x && mean && dmean && dvar && dx, DPK_EINVAL, "channel_stats_backward: null pointer");
     const int64_t total = B * C * H * W;
     DPK_REQUIRE(total / 256 < INT32_MAX, DPK_EUNSUPPORTED, "channel_stats_backward: too large");
-    DPK_LAUNCH(channel_stats_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x,
-               x_bstride, total, C, H * W, mean, dmean, dvar, 1.f / (float)(B * H * W), accumulate, dx);
-    DPK_CHECK_LAUNCH("channel_stats_bwd_kernel");
+    DPK_LAUNCH("channel_stats_bwd_kernel", channel_stats_bwd_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
+               (hipStream_t)stream, x, x_bstride, total, C, H * W, mean, dmean, dvar, 1.f / (float)(B * H * W),
+               accumulate, dx);
     return DPK_OK;
 }
 
@@ -344,9 +343,9 @@ int dpk_bn2d_fold_train(const double *sums, int64_t n, int32_t C, const float *g
     DPK_REQUIRE(C > 0 && n > 0, DPK_EINVAL, "bn2d_fold_train: bad sizes");
     DPK_REQUIRE(sums && gamma && beta && pre && stat && (!running_mean == !running_var), DPK_EINVAL,
                 "bn2d_fold_train: null pointer");
-    DPK_LAUNCH(bn2d_fold_train_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, sums, (double)n,
-               C, gamma, beta, eps, momentum, running_mean, running_var, pre, stat);
-    DPK_CHECK_LAUNCH("bn2d_fold_train_kernel");
+    DPK_LAUNCH("bn2d_fold_train_kernel", bn2d_fold_train_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0,
+               (hipStream_t)stream, sums, (double)n, C, gamma, beta, eps, momentum, running_mean, running_var, pre,
+               stat);
     return DPK_OK;
 }
 
@@ -354,9 +353,8 @@ int dpk_bn2d_fold_backward(const double *dab, int32_t C, const float *gamma, con
                            float *dbeta, float *dstat, void *stream) {
     DPK_REQUIRE(C > 0, DPK_EINVAL, "bn2d_fold_backward: bad sizes");
     DPK_REQUIRE(dab && gamma && stat && dgamma && dbeta && dstat, DPK_EINVAL, "bn2d_fold_backward: null pointer");
-    DPK_LAUNCH(bn2d_fold_bwd_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, dab, C, gamma, stat,
-               dgamma, dbeta, dstat);
-    DPK_CHECK_LAUNCH("bn2d_fold_bwd_kernel");
+    DPK_LAUNCH("bn2d_fold_bwd_kernel", bn2d_fold_bwd_kernel, dim3((unsigned)cdiv(C, 256)), dim3(256), 0,
+               (hipStream_t)stream, dab, C, gamma, stat, dgamma, dbeta, dstat);
     return DPK_OK;
 }
 
@@ -367,9 +365,8 @@ int dpk_channel_affine_forward(const float *x, int64_t B, int32_t C, int32_t H, 
     DPK_REQUIRE(x && ab && out, DPK_EINVAL, "channel_affine_forward: null pointer");
     const int64_t total = B * C * H * W;
     DPK_REQUIRE(total / 256 < INT32_MAX, DPK_EUNSUPPORTED, "channel_affine_forward: too large");
-    DPK_LAUNCH(channel_affine_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, x, total, C,
-               H * W, ab, out);
-    DPK_CHECK_LAUNCH("channel_affine_kernel");
+    DPK_LAUNCH("channel_affine_kernel", channel_affine_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0,
+               (hipStream_t)stream, x, total, C, H * W, ab, out);
     return DPK_OK;
 }
 
@@ -383,9 +380,9 @@ int dpk_channel_affine_backward(const float *x, int64_t x_bstride, const float *
     DPK_REQUIRE(x_bstride >= (int64_t)C * H * W, DPK_EINVAL, "channel_affine_backward: batch stride below C*H*W");
     const int64_t n_el = B * H * W;
     DPK_REQUIRE(n_el / kStatSpan < INT32_MAX, DPK_EUNSUPPORTED, "channel_affine_backward: too large");
-    DPK_LAUNCH(channel_affine_bwd_kernel, dim3((unsigned)cdiv(n_el, kStatSpan), (unsigned)C), dim3(256), 0,
-               (hipStream_t)stream, x, x_bstride, dy, n_el, H * W, C, ab, relu, mask, dx, ab ? dab : nullptr);
-    DPK_CHECK_LAUNCH("channel_affine_bwd_kernel");
+    DPK_LAUNCH("channel_affine_bwd_kernel", channel_affine_bwd_kernel,
+               dim3((unsigned)cdiv(n_el, kStatSpan), (unsigned)C), dim3(256), 0, (hipStream_t)stream, x, x_bstride, dy,
+               n_el, H * W, C, ab, relu, mask, dx, ab ? dab : nullptr);
     return DPK_OK;
 }
 
@@ -411,15 +408,14 @@ int dpk_conv2d_backward_weight(const float *in, int64_t in_bstride, const float 
     const int b_per_group = cdiv(B, split);
     const dim3 grid((unsigned)Cin, (unsigned)cdiv(Cout, cot), (unsigned)cdiv(B, b_per_group));
 #define DPK_BW_CASE(KS_, COT_)                                                                                      \
-    DPK_LAUNCH((conv2d_bwd_weight_kernel<KS_, COT_>), grid, dim3(256), 0, (hipStream_t)stream, in, in_bstride, dout, B, \
-               Cin, Cout, H, W, pre, in_mask, b_per_group, dw)
+    DPK_LAUNCH("conv2d_bwd_weight_kernel", (conv2d_bwd_weight_kernel<KS_, COT_>), grid, dim3(256), 0,              \
+               (hipStream_t)stream, in, in_bstride, dout, B, Cin, Cout, H, W, pre, in_mask, b_per_group, dw)
     if (ks == 3) {
         if (cot == 16) DPK_BW_CASE(3, 16); else DPK_BW_CASE(3, 8);
     } else {
         if (cot == 16) DPK_BW_CASE(1, 16); else DPK_BW_CASE(1, 8);
     }
 #undef DPK_BW_CASE
-    DPK_CHECK_LAUNCH("conv2d_bwd_weight_kernel");
     return DPK_OK;
 }
 
@@ -435,9 +431,8 @@ int dpk_coupling2d_transform_backward(const float *x, const float *z, const floa
     DPK_REQUIRE(x && z && dout && dx && dz && (!affine || (scale && dscale)), DPK_EINVAL,
                 "coupling2d_transform_backward: null pointer");
     const int Ch = inv_mask ? C : C / 2;
-    DPK_LAUNCH(coupling2d_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)Ch * sizeof(float), (hipStream_t)stream, x,
-               z, scale, inv_mask, C, H * W, affine, reverse, dout, dldj, dx, dz, dscale);
-    DPK_CHECK_LAUNCH("coupling2d_bwd_kernel");
+    DPK_LAUNCH("coupling2d_bwd_kernel", coupling2d_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)Ch * sizeof(float),
+               (hipStream_t)stream, x, z, scale, inv_mask, C, H * W, affine, reverse, dout, dldj, dx, dz, dscale);
     return DPK_OK;
 }
 

@@ -24,6 +24,6 @@ struct GemmArgs {
 
 // One product on `st`: K split over blockIdx.z (partial tiles summed in slice order) when the output tiles alone do not
 // fill the chip.  M <= 0 or N <= 0 launches nothing.
-void launch_gemm(const GemmArgs &g, hipStream_t st);
+int launch_gemm(const GemmArgs &g, hipStream_t st);
 
 }  // namespace dpk

@@ -189,12 +189,13 @@ static int chain_room(const char *who, const MafChain &c, int mode, int64_t ws_b
 }
 
 // masked weights of every layer, then H_l = act(H_{l-1} Wm_l^T + b_l), Z = H_L Wm^T + b (into zout when given)
-static void chain_forward(const MafChain &c, float *base, const float *x, int64_t B, int D, const float *const *W,
-                          const float *const *M, const float *const *b, int act, hipStream_t st, float *zout = nullptr) {
+static int chain_forward(const MafChain &c, float *base, const float *x, int64_t B, int D, const float *const *W,
+                         const float *const *M, const float *const *b, int act, hipStream_t st, float *zout = nullptr) {
     int in = D;
     for (int l = 0; l < c.n_lin; ++l) {
         const int64_t n = (int64_t)c.widths[l] * in;
-        DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W[l], M[l], n, base + c.wm_off[l]);
+        DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W[l], M[l], n,
+                   base + c.wm_off[l]);
         in = c.widths[l];
     }
     const float *A = x;
@@ -205,14 +206,16 @@ static void chain_forward(const MafChain &c, float *base, const float *x, int64_
         g.Bm = base + c.wm_off[l]; g.sbk = 1; g.sbn = in;
         g.C = (zout && l + 1 == c.n_lin) ? zout : base + c.h_off[l]; g.ldc = c.widths[l];
         g.M = (int)B; g.N = c.widths[l]; g.K = in; g.bias = b[l];
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
         if (l + 1 < c.n_lin) {
             const int64_t n = B * c.widths[l];
-            DPK_LAUNCH(maf_act_kernel, dim3(grid_for(n)), dim3(256), 0, st, base + c.h_off[l], n, act);
+            DPK_LAUNCH("maf_act_kernel", maf_act_kernel, dim3(grid_for(n)), dim3(256), 0, st, base + c.h_off[l], n,
+                       act);
         }
         A = base + c.h_off[l];
         in = c.widths[l];
     }
+    return DPK_OK;
 }
 
 // ---- fused density kernel --------------------------------------------------------------------------------------------
@@ -590,27 +593,33 @@ __global__ __launch_bounds__(kSThreads) void maf_sample_kernel(SamplePack p, con
 }
 
 template <int ACT>
-static void launch_sample(int UP, dim3 grid, hipStream_t st, const SamplePack &p, const float *u, int64_t B,
-                          const float *ws, const int *order, const float *aw, float *x, float *ldj) {
+static int launch_sample(Profile &prof, int UP, dim3 grid, hipStream_t st, const SamplePack &p, const float *u, int64_t B,
+                         const float *ws, const int *order, const float *aw, float *x, float *ldj) {
     switch (UP) {
-        case 32: DPK_LAUNCH((maf_sample_kernel<ACT, 32>), grid, dim3(kSThreads), 0, st, p, u, B, ws, order, aw, x, ldj); break;
-        case 64: DPK_LAUNCH((maf_sample_kernel<ACT, 64>), grid, dim3(kSThreads), 0, st, p, u, B, ws, order, aw, x, ldj); break;
-        case 96: DPK_LAUNCH((maf_sample_kernel<ACT, 96>), grid, dim3(kSThreads), 0, st, p, u, B, ws, order, aw, x, ldj); break;
-        default: DPK_LAUNCH((maf_sample_kernel<ACT, 128>), grid, dim3(kSThreads), 0, st, p, u, B, ws, order, aw, x, ldj); break;
+        case 32: DPK_LAUNCH_IN(prof, "maf_sample_kernel", (maf_sample_kernel<ACT, 32>), grid, dim3(kSThreads), 0, st, p,
+            u, B, ws, order, aw, x, ldj); break;
+        case 64: DPK_LAUNCH_IN(prof, "maf_sample_kernel", (maf_sample_kernel<ACT, 64>), grid, dim3(kSThreads), 0, st, p,
+            u, B, ws, order, aw, x, ldj); break;
+        case 96: DPK_LAUNCH_IN(prof, "maf_sample_kernel", (maf_sample_kernel<ACT, 96>), grid, dim3(kSThreads), 0, st, p,
+            u, B, ws, order, aw, x, ldj); break;
+        default: DPK_LAUNCH_IN(prof, "maf_sample_kernel", (maf_sample_kernel<ACT, 128>), grid, dim3(kSThreads), 0, st,
+            p, u, B, ws, order, aw, x, ldj); break;
     }
+    return DPK_OK;
 }
 
 template <int ACT>
-static int launch_density(int nht, const DensityPack &p, dim3 grid, int lds, hipStream_t st, const float *x, int64_t B,
+static int launch_density(Profile &prof, int nht, const DensityPack &p, dim3 grid, int lds, hipStream_t st, const float *x, int64_t B,
                           const float *ws, const int *iperm, const int *operm, const float *aw, const float *sc,
                           const float *sh, float *out, float *ildj, int accumulate) {
     const void *k = nht == 1 ? (const void *)maf_density_kernel<ACT, 1> : (const void *)maf_density_kernel<ACT, 2>;
-    const int rc = ensure_dynamic_lds(k, lds);
-    if (rc != DPK_OK) return rc;
+    DPK_TRY(ensure_dynamic_lds(k, lds));
     if (nht == 1)
-        DPK_LAUNCH((maf_density_kernel<ACT, 1>), grid, dim3(256), lds, st, p, x, B, ws, iperm, operm, aw, sc, sh, out, ildj, accumulate);
+        DPK_LAUNCH_IN(prof, "maf_density_kernel", (maf_density_kernel<ACT, 1>), grid, dim3(256), lds, st, p, x, B, ws,
+                      iperm, operm, aw, sc, sh, out, ildj, accumulate);
     else
-        DPK_LAUNCH((maf_density_kernel<ACT, 2>), grid, dim3(256), lds, st, p, x, B, ws, iperm, operm, aw, sc, sh, out, ildj, accumulate);
+        DPK_LAUNCH_IN(prof, "maf_density_kernel", (maf_density_kernel<ACT, 2>), grid, dim3(256), lds, st, p, x, B, ws,
+                      iperm, operm, aw, sc, sh, out, ildj, accumulate);
     return DPK_OK;
 }
 
@@ -696,12 +705,6 @@ __global__ __launch_bounds__(64) void maf_sample_deep_kernel(DeepArgs a, const f
     if (live) ldj[b] = acc;
 }
 
-static int launched(const char *who) {
-    const hipError_t e = hipGetLastError();
-    DPK_REQUIRE(e == hipSuccess, DPK_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
-    return DPK_OK;
-}
-
 }  // namespace dpk
 
 using namespace dpk;
@@ -725,8 +728,8 @@ extern "C" int dpk_maf_conditioner_forward(const float *x, int64_t B, int32_t D,
     if (B == 0) return DPK_OK;
     hipStream_t st = (hipStream_t)stream;
     float *base = (float *)ws;
-    chain_forward(c, base, x, B, D, W, M, b, activation, st, Z);
-    return launched("maf_conditioner_forward");
+    DPK_TRY(chain_forward(c, base, x, B, D, W, M, b, activation, st, Z));
+    return DPK_OK;
 }
 
 extern "C" int dpk_maf_density_chain(const float *x, int64_t B, int32_t D, int32_t n_hidden, const float *const *W,
@@ -741,10 +744,10 @@ extern "C" int dpk_maf_density_chain(const float *x, int64_t B, int32_t D, int32
     if (B == 0) return DPK_OK;
     hipStream_t st = (hipStream_t)stream;
     float *base = (float *)ws;
-    chain_forward(c, base, x, B, D, W, M, b, activation, st);
-    DPK_LAUNCH(maf_epilogue_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x, base + c.h_off[c.n_lin - 1], B, D, act_weight,
-               u, ildj);
-    return launched("maf_density_chain");
+    DPK_TRY(chain_forward(c, base, x, B, D, W, M, b, activation, st));
+    DPK_LAUNCH("maf_epilogue_kernel", maf_epilogue_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x,
+               base + c.h_off[c.n_lin - 1], B, D, act_weight, u, ildj);
+    return DPK_OK;
 }
 
 extern "C" int dpk_maf_density_chain_backward(const float *x, int64_t B, int32_t D, int32_t n_hidden,
@@ -765,27 +768,28 @@ extern "C" int dpk_maf_density_chain_backward(const float *x, int64_t B, int32_t
     if (B == 0) {
         int in = D;
         for (int l = 0; l < c.n_lin; ++l) {
-            if (grad_W[l]) (void)hipMemsetAsync(grad_W[l], 0, (size_t)c.widths[l] * in * 4, st);
-            if (grad_b[l]) (void)hipMemsetAsync(grad_b[l], 0, (size_t)c.widths[l] * 4, st);
+            if (grad_W[l]) DPK_REQUIRE(hipMemsetAsync(grad_W[l], 0, (size_t)c.widths[l] * in * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+            if (grad_b[l]) DPK_REQUIRE(hipMemsetAsync(grad_b[l], 0, (size_t)c.widths[l] * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
             in = c.widths[l];
         }
-        if (grad_act) (void)hipMemsetAsync(grad_act, 0, 4, st);
-        return launched("maf_density_chain_backward");
+        if (grad_act) DPK_REQUIRE(hipMemsetAsync(grad_act, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        return DPK_OK;
     }
-    if (!ws_holds_forward) chain_forward(c, base, x, B, D, W, M, b, activation, st);
+    if (!ws_holds_forward) DPK_TRY(chain_forward(c, base, x, B, D, W, M, b, activation, st));
     int64_t widest = 2 * (int64_t)D;
     for (int l = 0; l + 1 < c.n_lin; ++l) widest = c.widths[l] > widest ? c.widths[l] : widest;
     float *g0 = base + c.h_off[c.n_lin], *g1 = g0 + align_up(B * widest, 64), *pa = g1 + align_up(B * widest, 64);
     float *dOut = g0;
     if (grad_Z) {
         // gradient w.r.t. the conditioner output itself (the step loop's op): no epilogue, nothing direct into x
-        (void)hipMemcpyAsync(dOut, grad_Z, (size_t)B * 2 * D * 4, hipMemcpyDeviceToDevice, st);
-        (void)hipMemsetAsync(grad_x, 0, (size_t)B * D * 4, st);
-        if (grad_act) (void)hipMemsetAsync(grad_act, 0, 4, st);
+        DPK_REQUIRE(hipMemcpyAsync(dOut, grad_Z, (size_t)B * 2 * D * 4, hipMemcpyDeviceToDevice, st) == hipSuccess, DPK_ELAUNCH, "hipMemcpyAsync");
+        DPK_REQUIRE(hipMemsetAsync(grad_x, 0, (size_t)B * D * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        if (grad_act) DPK_REQUIRE(hipMemsetAsync(grad_act, 0, 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
     } else {
-        DPK_LAUNCH(maf_epilogue_bwd_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x, base + c.h_off[c.n_lin - 1], B, D,
-                   act_weight, grad_u, grad_ildj, grad_x, dOut, pa);
-        if (grad_act) DPK_LAUNCH(maf_colsum_kernel, dim3(1), dim3(256), 0, st, pa, B, 1, grad_act, 0);
+        DPK_LAUNCH("maf_epilogue_bwd_kernel", maf_epilogue_bwd_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, x,
+                   base + c.h_off[c.n_lin - 1], B, D, act_weight, grad_u, grad_ildj, grad_x, dOut, pa);
+        if (grad_act) DPK_LAUNCH("maf_colsum_kernel", maf_colsum_kernel, dim3(1), dim3(256), 0, st, pa, B, 1, grad_act,
+            0);
     }
     for (int l = c.n_lin - 1; l >= 0; --l) {
         const int out_w = c.widths[l], in_w = l ? c.widths[l - 1] : D;
@@ -796,25 +800,28 @@ extern "C" int dpk_maf_density_chain_backward(const float *x, int64_t B, int32_t
             g.A = dOut; g.sam = 1; g.sak = out_w;
             g.Bm = In; g.sbk = in_w; g.sbn = 1;
             g.C = grad_W[l]; g.ldc = in_w; g.M = out_w; g.N = in_w; g.K = (int)B;
-            launch_gemm(g, st);
+            DPK_TRY(launch_gemm(g, st));
             const int64_t n = (int64_t)out_w * in_w;
-            DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, grad_W[l], M[l], n, grad_W[l]);
+            DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, grad_W[l], M[l], n,
+                       grad_W[l]);
         }
-        if (grad_b[l]) DPK_LAUNCH(maf_colsum_kernel, dim3(cdiv(out_w, 64)), dim3(256), 0, st, dOut, B, out_w, grad_b[l], 0);
+        if (grad_b[l]) DPK_LAUNCH("maf_colsum_kernel", maf_colsum_kernel, dim3(cdiv(out_w, 64)), dim3(256), 0, st, dOut,
+            B, out_w, grad_b[l], 0);
         // dIn = dOut Wm (accumulated into grad_x for the first layer)
         float *dIn = l ? (dOut == g0 ? g1 : g0) : grad_x;
         GemmArgs g{};
         g.A = dOut; g.sam = out_w; g.sak = 1;
         g.Bm = base + c.wm_off[l]; g.sbk = in_w; g.sbn = 1;
         g.C = dIn; g.ldc = in_w; g.M = (int)B; g.N = in_w; g.K = out_w; g.accumulate = l == 0 ? 1 : 0;
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
         if (l) {
             const int64_t n = B * in_w;
-            DPK_LAUNCH(maf_act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, st, dIn, base + c.h_off[l - 1], n, activation);
+            DPK_LAUNCH("maf_act_bwd_kernel", maf_act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, st, dIn,
+                       base + c.h_off[l - 1], n, activation);
         }
         dOut = dIn;
     }
-    return launched("maf_density_chain_backward");
+    return DPK_OK;
 }
 
 extern "C" int64_t dpk_maf_density_workspace_bytes(int32_t D, int32_t units) {
@@ -842,27 +849,22 @@ extern "C" int dpk_maf_density_forward(const float *x, int64_t B, int32_t D, con
     hipStream_t st = (hipStream_t)stream;
     float *w = (float *)ws;
     const int64_t total = (int64_t)p.HT * 32 * p.KP + 2 * (int64_t)p.OT * 32 * p.UP + p.UP + 2 * p.OT * 32;
-    DPK_LAUNCH(maf_pack_density_kernel, dim3(grid_for(total)), dim3(256), 0, st, p, W1, M1, b1, W2, M2, b2, in_order,
+    DPK_LAUNCH("maf_pack_density_kernel", maf_pack_density_kernel, dim3(grid_for(total)), dim3(256), 0, st, p, W1, M1,
+               b1, W2, M2, b2, in_order, hidden_order, out_order, w);
+    DPK_LAUNCH("maf_klimit_kernel", maf_klimit_kernel, dim3(p.HT + p.OT), dim3(256), 0, st, p, M1, M2, in_order,
                hidden_order, out_order, w);
-    DPK_LAUNCH(maf_klimit_kernel, dim3(p.HT + p.OT), dim3(256), 0, st, p, M1, M2, in_order, hidden_order, out_order, w);
     const int nht = p.HT <= 4 ? 1 : 2;
     const int hs = p.UP + 1;
     const int lds = (64 * (hs > kFKc + 1 ? hs : kFKc + 1) + 256) * 4;
     dim3 grid(cdiv(B, kFRows));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_take(&e0, &e1, DPK_KERNEL_MAF_DENSITY);
-    if (e0) (void)hipEventRecord(e0, st);
-    int rc;
+    Profile prof(DPK_KERNEL_MAF_DENSITY, st);
     switch (activation) {
-        case kActRelu: rc = launch_density<kActRelu>(nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj); break;
-        case kActLeaky: rc = launch_density<kActLeaky>(nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj); break;
-        case kActSoftplus: rc = launch_density<kActSoftplus>(nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj); break;
-        case kActTanh: rc = launch_density<kActTanh>(nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj); break;
-        default: rc = launch_density<kActSigmoid>(nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj); break;
+        case kActRelu: return launch_density<kActRelu>(prof, nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj);
+        case kActLeaky: return launch_density<kActLeaky>(prof, nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj);
+        case kActSoftplus: return launch_density<kActSoftplus>(prof, nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj);
+        case kActTanh: return launch_density<kActTanh>(prof, nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj);
+        default: return launch_density<kActSigmoid>(prof, nht, p, grid, lds, st, x, B, w, in_order, out_order, act_weight, in_scale, in_shift, u, ildj, accumulate_ildj);
     }
-    if (rc) return rc;
-    if (e1) (void)hipEventRecord(e1, st);
-    return launched("maf_density_forward");
 }
 
 extern "C" int64_t dpk_maf_sample_workspace_bytes(int32_t D, int32_t units) {
@@ -887,21 +889,18 @@ extern "C" int dpk_maf_sample_forward(const float *u, int64_t B, int32_t D, cons
     hipStream_t st = (hipStream_t)stream;
     float *w = (float *)ws;
     const int64_t total = (int64_t)D * 3 * p.UP + 2 * (int64_t)D + p.UP;
-    DPK_LAUNCH(maf_pack_sample_kernel, dim3(grid_for(total)), dim3(256), 0, st, p, W1, M1, b1, W2, M2, b2, order, w);
-    DPK_LAUNCH(maf_sample_nz_kernel, dim3(cdiv(D, 4)), dim3(256), 0, st, p, w);
+    DPK_LAUNCH("maf_pack_sample_kernel", maf_pack_sample_kernel, dim3(grid_for(total)), dim3(256), 0, st, p, W1, M1, b1,
+               W2, M2, b2, order, w);
+    DPK_LAUNCH("maf_sample_nz_kernel", maf_sample_nz_kernel, dim3(cdiv(D, 4)), dim3(256), 0, st, p, w);
     dim3 grid(cdiv(B, kSThreads));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_take(&e0, &e1, DPK_KERNEL_MAF_SAMPLE);
-    if (e0) (void)hipEventRecord(e0, st);
+    Profile prof(DPK_KERNEL_MAF_SAMPLE, st);
     switch (activation) {
-        case kActRelu: launch_sample<kActRelu>(p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj); break;
-        case kActLeaky: launch_sample<kActLeaky>(p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj); break;
-        case kActSoftplus: launch_sample<kActSoftplus>(p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj); break;
-        case kActTanh: launch_sample<kActTanh>(p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj); break;
-        default: launch_sample<kActSigmoid>(p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj); break;
+        case kActRelu: return launch_sample<kActRelu>(prof, p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj);
+        case kActLeaky: return launch_sample<kActLeaky>(prof, p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj);
+        case kActSoftplus: return launch_sample<kActSoftplus>(prof, p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj);
+        case kActTanh: return launch_sample<kActTanh>(prof, p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj);
+        default: return launch_sample<kActSigmoid>(prof, p.UP, grid, st, p, u, B, w, order, act_weight, x, ldj);
     }
-    if (e1) (void)hipEventRecord(e1, st);
-    return launched("maf_sample_forward");
 }
 
 extern "C" int64_t dpk_masked_linear_workspace_bytes(int32_t in_features, int32_t out_features) {
@@ -920,13 +919,13 @@ extern "C" int dpk_masked_linear_forward(const float *x, int64_t B, int32_t in_f
     if (B == 0) return DPK_OK;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)in_features * out_features;
-    DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W, M, n, (float *)ws);
+    DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W, M, n, (float *)ws);
     GemmArgs g{};
     g.A = x; g.sam = in_features; g.sak = 1;
     g.Bm = (const float *)ws; g.sbk = 1; g.sbn = in_features;
     g.C = y; g.ldc = out_features; g.M = (int)B; g.N = out_features; g.K = in_features; g.bias = b;
-    launch_gemm(g, st);
-    return launched("masked_linear_forward");
+    DPK_TRY(launch_gemm(g, st));
+    return DPK_OK;
 }
 
 extern "C" int dpk_masked_linear_backward(const float *x, int64_t B, int32_t in_features, int32_t out_features,
@@ -940,28 +939,29 @@ extern "C" int dpk_masked_linear_backward(const float *x, int64_t B, int32_t in_
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)in_features * out_features;
     if (B == 0) {
-        if (grad_W) (void)hipMemsetAsync(grad_W, 0, (size_t)n * 4, st);
-        if (grad_b) (void)hipMemsetAsync(grad_b, 0, (size_t)out_features * 4, st);
-        return launched("masked_linear_backward");
+        if (grad_W) DPK_REQUIRE(hipMemsetAsync(grad_W, 0, (size_t)n * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        if (grad_b) DPK_REQUIRE(hipMemsetAsync(grad_b, 0, (size_t)out_features * 4, st) == hipSuccess, DPK_ELAUNCH, "hipMemsetAsync");
+        return DPK_OK;
     }
     if (grad_x) {
-        DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W, M, n, (float *)ws);
+        DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, W, M, n, (float *)ws);
         GemmArgs g{};
         g.A = grad_y; g.sam = out_features; g.sak = 1;
         g.Bm = (const float *)ws; g.sbk = in_features; g.sbn = 1;
         g.C = grad_x; g.ldc = in_features; g.M = (int)B; g.N = in_features; g.K = out_features;
-        launch_gemm(g, st);
+        DPK_TRY(launch_gemm(g, st));
     }
     if (grad_W) {
         GemmArgs g{};
         g.A = grad_y; g.sam = 1; g.sak = out_features;
         g.Bm = x; g.sbk = in_features; g.sbn = 1;
         g.C = grad_W; g.ldc = in_features; g.M = out_features; g.N = in_features; g.K = (int)B;
-        launch_gemm(g, st);
-        DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, grad_W, M, n, grad_W);
+        DPK_TRY(launch_gemm(g, st));
+        DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(n)), dim3(256), 0, st, grad_W, M, n, grad_W);
     }
-    if (grad_b) DPK_LAUNCH(maf_colsum_kernel, dim3(cdiv(out_features, 64)), dim3(256), 0, st, grad_y, B, out_features, grad_b, 0);
-    return launched("masked_linear_backward");
+    if (grad_b) DPK_LAUNCH("maf_colsum_kernel", maf_colsum_kernel, dim3(cdiv(out_features, 64)), dim3(256), 0, st,
+        grad_y, B, out_features, grad_b, 0);
+    return DPK_OK;
 }
 
 extern "C" int64_t dpk_maf_sample_deep_workspace_bytes(int32_t D, int32_t n_hidden, const int32_t *widths) {
@@ -1011,24 +1011,21 @@ extern "C" int dpk_maf_sample_deep_forward(const float *u, int64_t B, int32_t D,
         a.off[l] = a.total;
         a.total += widths[l];
         a.b[l] = b[l];
-        DPK_LAUNCH(maf_masked_transpose_kernel, dim3(grid_for(in * widths[l])), dim3(256), 0, st, W[l], M[l], widths[l],
-                   (int)in, w + o);
+        DPK_LAUNCH("maf_masked_transpose_kernel", maf_masked_transpose_kernel, dim3(grid_for(in * widths[l])),
+                   dim3(256), 0, st, W[l], M[l], widths[l], (int)in, w + o);
         a.Wc[l] = w + o;
         o += align_up(in * widths[l], 64);
         in = widths[l];
     }
     a.b[n_hidden] = b[n_hidden];
-    DPK_LAUNCH(maf_mul_kernel, dim3(grid_for(2 * (int64_t)D * in)), dim3(256), 0, st, W[n_hidden], M[n_hidden],
-               2 * (int64_t)D * in, w + o);
+    DPK_LAUNCH("maf_mul_kernel", maf_mul_kernel, dim3(grid_for(2 * (int64_t)D * in)), dim3(256), 0, st, W[n_hidden],
+               M[n_hidden], 2 * (int64_t)D * in, w + o);
     a.Wo = w + o;
     a.order = order; a.ev_ptr = event_ptr; a.ev = events; a.aw = act_weight;
     const int lds = a.total * 64 * 4;
-    int rc = ensure_dynamic_lds((const void *)maf_sample_deep_kernel, lds);
-    if (rc) return rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    profile_take(&e0, &e1, DPK_KERNEL_MAF_SAMPLE);
-    if (e0) (void)hipEventRecord(e0, st);
-    DPK_LAUNCH(maf_sample_deep_kernel, dim3(cdiv(B, 64)), dim3(64), lds, st, a, u, B, x, ldj);
-    if (e1) (void)hipEventRecord(e1, st);
-    return launched("maf_sample_deep_forward");
+    DPK_TRY(ensure_dynamic_lds((const void *)maf_sample_deep_kernel, lds));
+    Profile prof(DPK_KERNEL_MAF_SAMPLE, st);
+    DPK_LAUNCH_IN(prof, "maf_sample_deep_kernel", maf_sample_deep_kernel, dim3(cdiv(B, 64)), dim3(64), lds, st, a, u, B,
+                  x, ldj);
+    return DPK_OK;
 }

@@ -103,15 +103,14 @@ using namespace dpk;
 
 extern "C" int dpk_neg_mean_forward(const float *x, int64_t n, float *out, void *stream) {
     DPK_REQUIRE(x && out && n > 0, DPK_EINVAL, "neg_mean_forward: bad arguments");
-    DPK_LAUNCH(neg_mean_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, out);
-    DPK_CHECK_LAUNCH("neg_mean_kernel");
+    DPK_LAUNCH("neg_mean_kernel", neg_mean_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, out);
     return DPK_OK;
 }
 extern "C" int dpk_neg_mean_backward(const float *grad_out, int64_t n, float *grad_x, void *stream) {
     DPK_REQUIRE(grad_out && grad_x && n > 0, DPK_EINVAL, "neg_mean_backward: bad arguments");
     const int blocks = (int)std::min<int64_t>(1024, cdiv(n, 256));
-    DPK_LAUNCH(neg_mean_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grad_out, n, grad_x);
-    DPK_CHECK_LAUNCH("neg_mean_bwd_kernel");
+    DPK_LAUNCH("neg_mean_bwd_kernel", neg_mean_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grad_out, n,
+               grad_x);
     return DPK_OK;
 }
 
@@ -135,7 +134,6 @@ extern "C" int dpk_adam_step(int32_t n, const dpk_adam_tensor *tensors, float lr
     if (blocks == 0) return DPK_OK;
     a.n = n; a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.maximize = maximize;
     a.step = step; a.ticket = ticket;
-    DPK_LAUNCH(adam_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-    DPK_CHECK_LAUNCH("adam_step_kernel");
+    DPK_LAUNCH("adam_step_kernel", adam_step_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return DPK_OK;
 }

@@ -1368,9 +1368,8 @@ int prepare_leaf_structure(const RatWs &w, const int64_t *mask, const uint8_t *p
     if (flags & DPK_FLAG_STRUCT_CACHED) return DPK_OK;
     const size_t lds = (size_t)(2 * w.QB * d + w.QB * (w.NC + 1) + w.NC * w.QB + 1) * sizeof(int);
     DPK_REQUIRE(lds <= 64 * 1024, DPK_EUNSUPPORTED, "region dimension %d too large for the structure kernel", d);
-    DPK_LAUNCH(ratspn_struct_kernel, dim3(w.G), dim3(256), lds, st, mask, pad, R, d, w.NC, w.QB, w.SP,
-                       w.fl1, w.fl2, w.srcr, w.feat, w.nblk, w.segoff);
-    DPK_CHECK_LAUNCH("ratspn_struct_kernel");
+    DPK_LAUNCH("ratspn_struct_kernel", ratspn_struct_kernel, dim3(w.G), dim3(256), lds, st, mask, pad, R, d, w.NC, w.QB,
+               w.SP, w.fl1, w.fl2, w.srcr, w.feat, w.nblk, w.segoff);
     return DPK_OK;
 }
 
@@ -1404,9 +1403,8 @@ static int prepare_leaf_tables(int dist, const RatWs &w, const int64_t *mask, co
         }
     }
     const int grid = 2 * w.G * kPrepSlices + w.G + cdiv(rows, 4);   // block roles: see ratspn_prep_kernel
-    if (dist == 0) DPK_LAUNCH(ratspn_prep_kernel<0>, dim3(grid), dim3(256), 0, st, a);
-    else DPK_LAUNCH(ratspn_prep_kernel<1>, dim3(grid), dim3(256), 0, st, a);
-    DPK_CHECK_LAUNCH("ratspn_prep_kernel");
+    if (dist == 0) DPK_LAUNCH("ratspn_prep_kernel", ratspn_prep_kernel<0>, dim3(grid), dim3(256), 0, st, a);
+    else DPK_LAUNCH("ratspn_prep_kernel", ratspn_prep_kernel<1>, dim3(grid), dim3(256), 0, st, a);
     return DPK_OK;
 }
 
@@ -1425,34 +1423,18 @@ static int launch_leaf_gen(const LeafArgs &a, hipStream_t st) {
     size_t lds = G::BUF_BYTES + 64 + (size_t)kLeafWaves * 2 * a.tabcap;
     if (DEPTH > 0) lds += (size_t)(2 * a.C + kLeafWaves) * G::T * sizeof(float);
     auto kern = ratspn_leaf_kernel<DIST, QB, CB, SPL, DEPTH, S, GEN, XLDS>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e));
-            return DPK_ELAUNCH;
-        }
-    }
+    // (the size varies with the model: the limit is raised again only when a launch asks for more)
+    if (lds > 64 * 1024) DPK_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(kern), (int)lds));
 #ifdef DPK_TIMELINE
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, (size_t)4096 * kLeafWaves * 64 * 6 * 8);
-        const_cast<LeafArgs &>(a).dbg = dbg;
-        FILE *f = fopen("/tmp/dpk_timeline_ptr.txt", "w");
-        if (f) { fprintf(f, "%p %d %d\n", (void *)dbg, grid, a.NC); fclose(f); }
-    }
+    const_cast<LeafArgs &>(a).dbg = timeline_buffer("", (size_t)4096 * kLeafWaves * 64 * 6 * 8, grid, a.NC);
 #endif
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DEPTH > 0 ? DPK_KERNEL_RATSPN_FUSED : DPK_KERNEL_RATSPN_LEAF);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DEPTH > 0 ? DPK_KERNEL_RATSPN_FUSED : DPK_KERNEL_RATSPN_LEAF, st);
     int gy = 1;
     if (DEPTH == 0) {
         const int n_items = (a.R / QB) * (a.I / CB);
         gy = cdiv(n_items, kLeafWaves);
     }
-    DPK_LAUNCH(kern, dim3(grid, gy), dim3(kLeafWaves * 64), lds, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_leaf_kernel");
+    DPK_LAUNCH_IN(prof, "ratspn_leaf_kernel", kern, dim3(grid, gy), dim3(kLeafWaves * 64), lds, st, a);
     return DPK_OK;
 }
 

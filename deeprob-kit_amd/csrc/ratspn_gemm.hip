@@ -321,31 +321,18 @@ static int gemm_launch(const ring::GemmArgs &a, int reps, hipStream_t st, const 
             static const bool np0 = [] { const char *e = getenv("DPK_RING_VI_NP0"); return e && atoi(e) != 0; }();
             if (np0) pv.np = 0;
         }
-        hipEvent_t e0, e1;
-        profile_take(&e0, &e1, DPK_KERNEL_RATSPN_FUSED);
-        if (e0) (void)hipEventRecord(e0, st);
-        DPK_LAUNCH(kvi, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a, pv);
-        if (e1) (void)hipEventRecord(e1, st);
-        DPK_CHECK_LAUNCH("ratspn_gemm_kernel (self-checking)");
+        Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
+        DPK_LAUNCH_IN(prof, "ratspn_gemm_kernel (self-checking)", kvi, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st,
+                      a, pv);
         return DPK_OK;
     }
     auto kern = ring::ratspn_gemm_kernel<I, S, NT>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
 #ifdef DPK_TIMELINE
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, (size_t)1024 * kGemmWaves * 64 * 8 * 8);
-        const_cast<ring::GemmArgs &>(a).dbg = dbg;
-        FILE *f = fopen("/tmp/dpk_timeline_ptr.txt", "w");
-        if (f) { fprintf(f, "%p %d %d\n", (void *)dbg, grid, a.NCH); fclose(f); }
-    }
+    const_cast<ring::GemmArgs &>(a).dbg = timeline_buffer("", (size_t)1024 * kGemmWaves * 64 * 8 * 8, grid, a.NCH);
 #endif
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
-    DPK_LAUNCH(kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_gemm_kernel");
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
+    DPK_LAUNCH_IN(prof, "ratspn_gemm_kernel", kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
     return DPK_OK;
 }
 
@@ -446,10 +433,12 @@ int ratspn_gemm_forward(const RatWs &w, const float *x, int64_t B, int D, const 
         p.np = np;
     } else if (!(flags & DPK_FLAG_PARAMS_CACHED)) {
         p.mode = (flags & DPK_FLAG_PARAMS_VERIFY) ? kPrepVerify : kPrepBuild;
-        if (I == 2) DPK_LAUNCH(ratspn_gemm_prep_kernel<2>, dim3(np), dim3(kGemmPrepThreads), prep_lds, st, p);
-        else if (I == 4) DPK_LAUNCH(ratspn_gemm_prep_kernel<4>, dim3(np), dim3(kGemmPrepThreads), prep_lds, st, p);
-        else DPK_LAUNCH(ratspn_gemm_prep_kernel<8>, dim3(np), dim3(kGemmPrepThreads), prep_lds, st, p);
-        DPK_CHECK_LAUNCH("ratspn_gemm_prep_kernel");
+        if (I == 2) DPK_LAUNCH("ratspn_gemm_prep_kernel", ratspn_gemm_prep_kernel<2>, dim3(np), dim3(kGemmPrepThreads),
+            prep_lds, st, p);
+        else if (I == 4) DPK_LAUNCH("ratspn_gemm_prep_kernel", ratspn_gemm_prep_kernel<4>, dim3(np),
+            dim3(kGemmPrepThreads), prep_lds, st, p);
+        else DPK_LAUNCH("ratspn_gemm_prep_kernel", ratspn_gemm_prep_kernel<8>, dim3(np), dim3(kGemmPrepThreads),
+            prep_lds, st, p);
         p.np = 0;
     }
     if (wide || small || slice || marginal_ring) {

@@ -352,20 +352,10 @@ static int gemm_launch(const GemmArgs &a, int reps, hipStream_t st) {
     const int cus = device_cus();
     const int grid = a.ntiles < cus ? a.ntiles : cus;
 #ifdef DPK_TIMELINE
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, (size_t)1024 * kGemmWaves * 64 * 8 * 8);
-        const_cast<GemmArgs &>(a).dbg = dbg;
-        FILE *f = fopen("/tmp/dpk_timeline_ptr.txt", "w");
-        if (f) { fprintf(f, "%p %d %d\n", (void *)dbg, grid, a.NCH); fclose(f); }
-    }
+    const_cast<GemmArgs &>(a).dbg = timeline_buffer("", (size_t)1024 * kGemmWaves * 64 * 8 * 8, grid, a.NCH);
 #endif
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
-    DPK_LAUNCH(kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_gemm_marginal_kernel");
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
+    DPK_LAUNCH_IN(prof, "ratspn_gemm_marginal_kernel", kern, dim3(grid), dim3(2 * kGemmWaves * 64), lds, st, a);
     return DPK_OK;
 }
 

@@ -1028,9 +1028,7 @@ static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, int lane
     auto kern = ratspn_gemm_slice_kernel<I, S, NT>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
     const int cus = device_cus();
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
     // a work-group remembers the blocks it leaves to the exact evaluation in a 64-bit mask: at most 64 blocks per
     // work-group and launch, i.e. 524 288 samples per launch on 256 work-groups -- larger batches take several launches
     // (the caller keeps the in-launch table check to single-launch batches: gemm_slice_checks_inline)
@@ -1047,20 +1045,13 @@ static int gemm_slice_launch(const GemmArgs &a0, const GemmPrepArgs &p, int lane
         GemmPrepArgs pp = p;
         pp.readers = grid;
 #ifdef DPK_TIMELINE
-        {
-            static unsigned long long *dbg = nullptr;
-            if (!dbg) (void)hipMalloc(&dbg, (size_t)256 * 8 * 16 * 8 * 8);
-            a.dbg = dbg;
-            FILE *f = fopen("/tmp/dpk_timeline_slice_ptr.txt", "w");
-            if (f) { fprintf(f, "%p %d\n", (void *)dbg, grid); fclose(f); }
-        }
+        a.dbg = timeline_buffer("_slice", (size_t)256 * 8 * 16 * 8 * 8, grid);
 #endif
-        DPK_LAUNCH(kern, dim3(grid), dim3(kSliceThreads), lds, st, a, pp);
-        DPK_CHECK_LAUNCH("ratspn_gemm_slice_kernel");
+        DPK_LAUNCH("ratspn_gemm_slice_kernel", kern, dim3(grid), dim3(kSliceThreads), lds, st, a, pp);
         g_slice_last_grid.store(grid, std::memory_order_relaxed);
         g_slice_last_lanes.store(lanes, std::memory_order_relaxed);
     }
-    if (ev1) (void)hipEventRecord(ev1, st);
+    prof.stop();
     return DPK_OK;
 }
 

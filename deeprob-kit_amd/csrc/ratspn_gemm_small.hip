@@ -549,22 +549,13 @@ static int gemm_small_launch(const GemmArgs &a, const GemmPrepArgs &p, hipStream
     auto kern = ratspn_gemm_small_kernel<I, S, NT, MAXK>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
 #ifdef DPK_TIMELINE
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, (size_t)256 * kGemmSmallWaves * 16 * 8);
-        const_cast<GemmArgs &>(a).dbg = dbg;
-        FILE *f = fopen("/tmp/dpk_timeline_small_ptr.txt", "w");
-        if (f) { fprintf(f, "%p %d\n", (void *)dbg, cdiv(a.B, 32)); fclose(f); }
-    }
+    const_cast<GemmArgs &>(a).dbg = timeline_buffer("_small", (size_t)256 * kGemmSmallWaves * 16 * 8, cdiv(a.B, 32));
 #endif
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
     GemmPrepArgs pp = p;
     pp.readers = p.np + (int)cdiv(a.B, 32);
-    DPK_LAUNCH(kern, dim3(p.np + cdiv(a.B, 32)), dim3(kGemmSmallWaves * 64), lds, st, a, pp);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_gemm_small_kernel");
+    DPK_LAUNCH_IN(prof, "ratspn_gemm_small_kernel", kern, dim3(p.np + cdiv(a.B, 32)), dim3(kGemmSmallWaves * 64), lds,
+                  st, a, pp);
     return DPK_OK;
 }
 

@@ -1004,16 +1004,12 @@ static int gemm_wide_launch_nw(const GemmArgs &a, const GemmPrepArgs &p, hipStre
     if (p.np > 0 && gemm_prep_lds_bytes(a.D, kWideI, a.d) > lds) lds = gemm_prep_lds_bytes(a.D, kWideI, a.d);
     auto kern = ratspn_gemm_wide_kernel<S, MARG, EMIT, NW>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
     GemmPrepArgs pp = p;
     const int blocks = (int)cdiv(a.B, 32);
     const int model_wgs = NW == kWideWaves ? blocks : 2 * (int)align_up(blocks, 8);   // (NW = 4: whole groups of 16, see the kernel)
     pp.readers = p.np + (NW == kWideWaves ? blocks : 2 * blocks);
-    DPK_LAUNCH(kern, dim3(p.np + model_wgs), dim3(kWideWaves * 64), lds, st, a, pp);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_gemm_wide_kernel");
+    DPK_LAUNCH_IN(prof, "ratspn_gemm_wide_kernel", kern, dim3(p.np + model_wgs), dim3(kWideWaves * 64), lds, st, a, pp);
     return DPK_OK;
 }
 template <int S, bool MARG, bool EMIT = false>
@@ -1027,12 +1023,9 @@ static int gemm_wide_ring_launch(const GemmArgs &a, hipStream_t st) {
     const size_t lds = (size_t)kGemmStages * kGemmTile * 256 + sizeof(WideRingTail) + (size_t)kWideWaves * 2 * S * kWideI * kWideI * 4;
     auto kern = ratspn_gemm_wide_ring_kernel<S>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024)) return rc;
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_FUSED);
-    if (ev0) (void)hipEventRecord(ev0, st);
-    DPK_LAUNCH(kern, dim3(cdiv(a.B, kGemmTile)), dim3((kWideWaves + kGemmWaves) * 64), lds, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_gemm_wide_ring_kernel");
+    Profile prof(DPK_KERNEL_RATSPN_FUSED, st);
+    DPK_LAUNCH_IN(prof, "ratspn_gemm_wide_ring_kernel", kern, dim3(cdiv(a.B, kGemmTile)),
+                  dim3((kWideWaves + kGemmWaves) * 64), lds, st, a);
     return DPK_OK;
 }
 

@@ -82,12 +82,15 @@ __global__ __launch_bounds__(1024) void logsoftmax_jacobian_wide_kernel(const fl
     for (int i = threadIdx.x; i < n; i += blockDim.x)
         gW[(int64_t)row * n + i] = glw[(int64_t)row * n + i] - W[(int64_t)row * n + i] * s;
 }
-static void launch_softmax_rows(const float *weight, int rows, int n, float *W, float *LW, hipStream_t st,
-                                const unsigned *gate = nullptr) {
+static int launch_softmax_rows(const float *weight, int rows, int n, float *W, float *LW, hipStream_t st,
+                               const unsigned *gate = nullptr) {
     if (n >= 2048 && rows <= 1024)
-        DPK_LAUNCH(softmax_rows_wide_kernel, dim3(rows), dim3(1024), 0, st, weight, rows, n, W, LW, gate);
+        DPK_LAUNCH("softmax_rows_wide_kernel", softmax_rows_wide_kernel, dim3(rows), dim3(1024), 0, st, weight, rows, n,
+                   W, LW, gate);
     else
-        DPK_LAUNCH(softmax_rows_kernel2, dim3(cdiv(rows, 4)), dim3(256), 0, st, weight, rows, n, W, LW, gate);
+        DPK_LAUNCH("softmax_rows_kernel2", softmax_rows_kernel2, dim3(cdiv(rows, 4)), dim3(256), 0, st, weight, rows, n,
+                   W, LW, gate);
+    return DPK_OK;
 }
 
 // ------------------------------------------------------------------------------------
@@ -883,9 +886,8 @@ extern "C" int dpk_product_forward(const float *in, int64_t B, int32_t R, int32_
     DPK_REQUIRE(B >= 0 && R > 0 && (R % 2) == 0 && N > 0, DPK_EINVAL, "product_forward: bad sizes");
     const int64_t total = B * (R / 2) * N * N;
     if (total == 0) return DPK_OK;
-    DPK_LAUNCH(product_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in,
-                       total, R, N, out);
-    DPK_CHECK_LAUNCH("product_fwd_kernel");
+    DPK_LAUNCH("product_fwd_kernel", product_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+               in, total, R, N, out);
     return DPK_OK;
 }
 
@@ -895,9 +897,8 @@ extern "C" int dpk_product_backward(const float *g, int64_t B, int32_t R, int32_
     DPK_REQUIRE(B >= 0 && R > 0 && (R % 2) == 0 && N > 0, DPK_EINVAL, "product_backward: bad sizes");
     const int64_t total = B * R * N;
     if (total == 0) return DPK_OK;
-    DPK_LAUNCH(product_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, g,
-                       total, R, N, grad_in);
-    DPK_CHECK_LAUNCH("product_bwd_kernel");
+    DPK_LAUNCH("product_bwd_kernel", product_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+               g, total, R, N, grad_in);
     return DPK_OK;
 }
 
@@ -918,13 +919,12 @@ static int sum_forward_impl(const float *in, const float *weight, int64_t B, int
     if (B == 0) return DPK_OK;
     float *W = (float *)ws, *LW = (float *)((char *)ws + seg);
     hipStream_t st = (hipStream_t)stream;
-    launch_softmax_rows(weight, P * S, N, W, LW, st);
+    DPK_TRY(launch_softmax_rows(weight, P * S, N, W, LW, st));
     if (P == 1 && N >= 1024)
-        DPK_LAUNCH(root_wide_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, in, LW, B, N, S, out);
+        DPK_LAUNCH("sum_fwd_kernel", root_wide_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, in, LW, B, N, S, out);
     else
-        DPK_LAUNCH(sum_fwd_kernel, dim3(cdiv(B, 64), P), dim3(256), 0, st, in, as_const(W), as_const(LW), B,
-                           P, N, S, out);
-    DPK_CHECK_LAUNCH("sum_fwd_kernel");
+        DPK_LAUNCH("sum_fwd_kernel", sum_fwd_kernel, dim3(cdiv(B, 64), P), dim3(256), 0, st, in, as_const(W),
+                   as_const(LW), B, P, N, S, out);
     return DPK_OK;
 }
 
@@ -938,12 +938,12 @@ static int sum_backward_impl(const float *in, const float *weight, const float *
     float *W = (float *)ws, *LW = (float *)((char *)ws + seg), *glw = (float *)((char *)ws + 2 * seg);
     float *corr = (float *)((char *)ws + 3 * seg);
     hipStream_t st = (hipStream_t)stream;
-    launch_softmax_rows(weight, P * S, N, W, LW, st);
+    DPK_TRY(launch_softmax_rows(weight, P * S, N, W, LW, st));
     if (B > 0) {
         const int64_t rows = B * P * S;
         const int64_t blocks = N <= 32 ? (rows + 255) / 256 : (rows + 3) / 4;
-        DPK_LAUNCH(lse_residual_kernel, dim3((unsigned)std::min<int64_t>(blocks, 65535 * 4)), dim3(256), 0, st, in, LW, out, B, P, N,
-                   S, corr);
+        DPK_LAUNCH("lse_residual_kernel", lse_residual_kernel, dim3((unsigned)std::min<int64_t>(blocks, 65535 * 4)),
+                   dim3(256), 0, st, in, LW, out, B, P, N, S, corr);
     }
     if (grad_weight) {
         hipError_t e = hipMemsetAsync(glw, 0, (size_t)P * S * N * 4, st);
@@ -953,20 +953,20 @@ static int sum_backward_impl(const float *in, const float *weight, const float *
         const int cols = P * N;
         int tile = kBwdTile;   // (shorter sample slices while the grid would leave compute units idle)
         while (tile > 8 && cdiv(B, tile) * cdiv(cols, 64) < 2 * device_cus()) tile /= 2;
-        DPK_LAUNCH(sum_bwd_kernel, dim3(cdiv(B, tile), cdiv(cols, 64)), dim3(64 * kBwdWaves), 0, st, in, LW,
-                           out, g, B, P, N, S, grad_in, grad_weight ? glw : nullptr, tile, corr);
+        DPK_LAUNCH("sum_bwd_kernel", sum_bwd_kernel, dim3(cdiv(B, tile), cdiv(cols, 64)), dim3(64 * kBwdWaves), 0, st,
+                   in, LW, out, g, B, P, N, S, grad_in, grad_weight ? glw : nullptr, tile, corr);
     } else if (grad_in) {
         // nothing to write
     }
     if (grad_weight)
     {
         if (N >= 2048 && P * S <= 1024)
-            DPK_LAUNCH(logsoftmax_jacobian_wide_kernel, dim3(P * S), dim3(1024), 0, st, glw, W, P * S, N, grad_weight);
+            DPK_LAUNCH("sum_bwd_kernel", logsoftmax_jacobian_wide_kernel, dim3(P * S), dim3(1024), 0, st, glw, W, P * S,
+                       N, grad_weight);
         else
-            DPK_LAUNCH(logsoftmax_jacobian_kernel, dim3(cdiv(P * S, 4)), dim3(256), 0, st, glw, W, P * S, N,
-                       grad_weight);
+            DPK_LAUNCH("sum_bwd_kernel", logsoftmax_jacobian_kernel, dim3(cdiv(P * S, 4)), dim3(256), 0, st, glw, W,
+                       P * S, N, grad_weight);
     }
-    DPK_CHECK_LAUNCH("sum_bwd_kernel");
     return DPK_OK;
 }
 
@@ -1024,14 +1024,13 @@ static int leaf_backward_common(int dist, const float *x, const float *g, int64_
 #define DPK_LEAF_MOMENT(DIST, W1)                                                                                          \
     do {                                                                                                                   \
         if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&leaf_bwd_moment_kernel<DIST, W1>), 96 * 1024)) return lrc; \
-        DPK_LAUNCH((leaf_bwd_moment_kernel<DIST, W1>), mgrid, mblock, kLeafMomentLds, st, x, g, B, D, R, I, d, mask, pad_mask, p0, \
-                   p1, gp0, gp1);                                                                                          \
+        DPK_LAUNCH("leaf_bwd_moment_kernel", (leaf_bwd_moment_kernel<DIST, W1>), mgrid, mblock, kLeafMomentLds, st, x,     \
+                   g, B, D, R, I, d, mask, pad_mask, p0, p1, gp0, gp1);                                                    \
     } while (0)
         if (dist == 0 && gp1) DPK_LEAF_MOMENT(0, true);
         else if (dist == 0) DPK_LEAF_MOMENT(0, false);
         else DPK_LEAF_MOMENT(1, false);
 #undef DPK_LEAF_MOMENT
-        DPK_CHECK_LAUNCH("leaf_bwd_moment_kernel");
     } else if (B > 0 && (gp0 || gp1)) {
         const int cbk = (I % 4 == 0) ? 4 : ((I % 2 == 0) ? 2 : 1);
         // small batches: shorter sample slices so that the grid still covers the chip (more atomics per parameter)
@@ -1050,15 +1049,15 @@ static int leaf_backward_common(int dist, const float *x, const float *g, int64_
     do {                                                                                                         \
         if (staged && gp1) {                                                                                     \
             if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&leaf_bwd_param_lds_kernel<DIST, CBK, true>), 96 * 1024)) return lrc; \
-            DPK_LAUNCH((leaf_bwd_param_lds_kernel<DIST, CBK, true>), sgrid, block, stage_bytes, st, x, g, B, D, R, I, d, \
-                       w.SP, w.feat, w.srcr, p0, p1, gp0, gp1, tile, passes);                                    \
+            DPK_LAUNCH("leaf_bwd_param_kernel", (leaf_bwd_param_lds_kernel<DIST, CBK, true>), sgrid, block,      \
+                       stage_bytes, st, x, g, B, D, R, I, d, w.SP, w.feat, w.srcr, p0, p1, gp0, gp1, tile, passes); \
         } else if (staged) {                                                                                     \
             if (int lrc = ensure_dynamic_lds(reinterpret_cast<const void *>(&leaf_bwd_param_lds_kernel<DIST, CBK, false>), 96 * 1024)) return lrc; \
-            DPK_LAUNCH((leaf_bwd_param_lds_kernel<DIST, CBK, false>), sgrid, block, stage_bytes, st, x, g, B, D, R, I, d, \
-                       w.SP, w.feat, w.srcr, p0, p1, gp0, gp1, tile, passes);                                    \
+            DPK_LAUNCH("leaf_bwd_param_kernel", (leaf_bwd_param_lds_kernel<DIST, CBK, false>), sgrid, block,     \
+                       stage_bytes, st, x, g, B, D, R, I, d, w.SP, w.feat, w.srcr, p0, p1, gp0, gp1, tile, passes); \
         } else                                                                                                     \
-            DPK_LAUNCH((leaf_bwd_param_kernel<DIST, CBK>), grid, block, 0, st, x, g, B, D, R, I, d, w.SP, w.feat, \
-                       w.srcr, p0, p1, gp0, gp1, drop_p, seed, tile);                                            \
+            DPK_LAUNCH("leaf_bwd_param_kernel", (leaf_bwd_param_kernel<DIST, CBK>), grid, block, 0, st, x, g, B, D, R, \
+                       I, d, w.SP, w.feat, w.srcr, p0, p1, gp0, gp1, drop_p, seed, tile);                        \
     } while (0)
         if (dist == 0) {
             if (cbk == 4) DPK_LEAF_BWD(0, 4);
@@ -1070,7 +1069,6 @@ static int leaf_backward_common(int dist, const float *x, const float *g, int64_
             else DPK_LEAF_BWD(1, 1);
         }
 #undef DPK_LEAF_BWD
-        DPK_CHECK_LAUNCH("leaf_bwd_param_kernel");
     }
     if (gx && B > 0) {
         // regions per repetition = 2^depth = (D + pad) / d with pad < 2^depth <= D (RegionGraph: depth <= log2 D), i.e.
@@ -1086,11 +1084,10 @@ static int leaf_backward_common(int dist, const float *x, const float *g, int64_
                     "leaf_backward: inverse table does not fit");
         DPK_REQUIRE(hipMemsetAsync(inv, 0xff, (size_t)reps * D * 4, st) == hipSuccess, DPK_ELAUNCH,
                     "leaf_backward: memset");
-        DPK_LAUNCH(leaf_inverse_kernel, dim3(w.G), dim3(256), 0, st, w.feat, w.srcr, d, w.SP, D, per_rep,
-                           inv);
-        DPK_LAUNCH(gaussian_leaf_bwd_x_kernel, dim3(grid_for(B * D, 256)), dim3(256), 0, st, x, g, B, D,
-                           R, I, d, reps, inv, p0, p1, gx, drop_p, seed, dist);
-        DPK_CHECK_LAUNCH("gaussian_leaf_bwd_x_kernel");
+        DPK_LAUNCH("leaf_inverse_kernel", leaf_inverse_kernel, dim3(w.G), dim3(256), 0, st, w.feat, w.srcr, d, w.SP, D,
+                   per_rep, inv);
+        DPK_LAUNCH("gaussian_leaf_bwd_x_kernel", gaussian_leaf_bwd_x_kernel, dim3(grid_for(B * D, 256)), dim3(256), 0,
+                   st, x, g, B, D, R, I, d, reps, inv, p0, p1, gx, drop_p, seed, dist);
     }
     return DPK_OK;
 }
@@ -1170,12 +1167,11 @@ extern "C" int dpk_leaf_forward_dropout(int32_t dist, const float *x, int64_t B,
     DPK_REQUIRE(x && mask && p0 && out && (dist == 1 || p1), DPK_EINVAL, "leaf_forward_dropout: null pointer");
     const int64_t total = B * R * I;
     if (dist == 0)
-        DPK_LAUNCH(leaf_fwd_dropout_kernel<0>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                           x, B, D, mask, pad_mask, p0, p1, R, I, d, drop_p, seed, out);
+        DPK_LAUNCH("leaf_fwd_dropout_kernel", leaf_fwd_dropout_kernel<0>, dim3(grid_for(total, 256)), dim3(256), 0,
+                   (hipStream_t)stream, x, B, D, mask, pad_mask, p0, p1, R, I, d, drop_p, seed, out);
     else
-        DPK_LAUNCH(leaf_fwd_dropout_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                           x, B, D, mask, pad_mask, p0, p1, R, I, d, drop_p, seed, out);
-    DPK_CHECK_LAUNCH("leaf_fwd_dropout_kernel");
+        DPK_LAUNCH("leaf_fwd_dropout_kernel", leaf_fwd_dropout_kernel<1>, dim3(grid_for(total, 256)), dim3(256), 0,
+                   (hipStream_t)stream, x, B, D, mask, pad_mask, p0, p1, R, I, d, drop_p, seed, out);
     return DPK_OK;
 }
 
@@ -1202,9 +1198,8 @@ extern "C" int dpk_dropout_fill(const float *x, int64_t n, float drop_p, uint64_
     DPK_REQUIRE(n >= 0 && drop_p >= 0.f && drop_p < 1.f, DPK_EINVAL, "dropout_fill: bad arguments");
     if (n == 0) return DPK_OK;
     DPK_REQUIRE(x && out, DPK_EINVAL, "dropout_fill: null pointer");
-    DPK_LAUNCH(dropout_fill_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, n, drop_p,
-                       seed, fill, out);
-    DPK_CHECK_LAUNCH("dropout_fill_kernel");
+    DPK_LAUNCH("dropout_fill_kernel", dropout_fill_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
+               n, drop_p, seed, fill, out);
     return DPK_OK;
 }
 
@@ -1366,23 +1361,22 @@ static int prod_fused_common(bool root, const float *in, const float *weight, in
             return upper_mfma_forward(root, in, W, LW, B, R, N, S, out, (char *)ws + 2 * seg, true, st);
         }
     }
-    if (!cached) launch_softmax_rows(weight, rows, n, W, LW, st);
+    if (!cached) DPK_TRY(launch_softmax_rows(weight, rows, n, W, LW, st));
     const dim3 block(256);
 #define DPK_LAUNCH_PS(NMAX)                                                                                         \
     do {                                                                                                            \
         if (root)                                                                                                   \
-            DPK_LAUNCH(prodroot_fwd_kernel<NMAX>, dim3(cdiv(B, 64)), block, 0, st, in, as_const(W),         \
-                               as_const(LW), B, R, N, S, out);                                                      \
+            DPK_LAUNCH(who, prodroot_fwd_kernel<NMAX>, dim3(cdiv(B, 64)), block, 0, st, in, as_const(W),            \
+                       as_const(LW), B, R, N, S, out);                                                              \
         else                                                                                                        \
-            DPK_LAUNCH(prodsum_fwd_kernel<NMAX>, dim3(cdiv(B, 64), cdiv(P, 4)), block, 0, st, in,           \
-                               as_const(W), as_const(LW), B, R, N, S, out);                                         \
+            DPK_LAUNCH(who, prodsum_fwd_kernel<NMAX>, dim3(cdiv(B, 64), cdiv(P, 4)), block, 0, st, in, as_const(W), \
+                       as_const(LW), B, R, N, S, out);                                                              \
     } while (0)
     if (N <= 4) DPK_LAUNCH_PS(4);
     else if (N <= 8) DPK_LAUNCH_PS(8);
     else if (N <= 16) DPK_LAUNCH_PS(16);
     else DPK_LAUNCH_PS(32);
 #undef DPK_LAUNCH_PS
-    DPK_CHECK_LAUNCH(who);
     return DPK_OK;
 }
 

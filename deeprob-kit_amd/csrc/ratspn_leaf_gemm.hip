@@ -476,12 +476,8 @@ static int leaf_gemm_launch(const LeafGemmArgs &a, int NG, hipStream_t st) {
     const int cus = device_cus();
     const int per_group = cus / NG > 0 ? cus / NG : 1;
     const int gx = a.ntiles < per_group ? a.ntiles : per_group;
-    hipEvent_t ev0, ev1;
-    profile_take(&ev0, &ev1, DPK_KERNEL_RATSPN_LEAF);
-    if (ev0) (void)hipEventRecord(ev0, st);
-    DPK_LAUNCH(kern, dim3(gx, NG), dim3(2 * kGemmWaves * 64), lds, st, a);
-    if (ev1) (void)hipEventRecord(ev1, st);
-    DPK_CHECK_LAUNCH("ratspn_leaf_gemm_kernel");
+    Profile prof(DPK_KERNEL_RATSPN_LEAF, st);
+    DPK_LAUNCH_IN(prof, "ratspn_leaf_gemm_kernel", kern, dim3(gx, NG), dim3(2 * kGemmWaves * 64), lds, st, a);
     return DPK_OK;
 }
 
@@ -513,8 +509,8 @@ int ratspn_leaf_gemm_forward(void *ws, const float *x, int64_t B, int D, const i
         pa.mtab = mtab; pa.ctab = ctab; pa.bias = biasC; pa.bias_row = biasT; pa.elig = elig;
         const size_t lds = ((size_t)D + (size_t)I * d + (size_t)NCH * I) * 4 + (size_t)align_up(d, 4);
         DPK_REQUIRE(lds <= 60 * 1024, DPK_EUNSUPPORTED, "leaf_gemm: in_features=%d too large for the table kernel", D);
-        DPK_LAUNCH(ratspn_leaf_gemm_prep_kernel, dim3(R, kLeafPrepParts), dim3(256), lds, st, pa);
-        DPK_CHECK_LAUNCH("ratspn_leaf_gemm_prep_kernel");
+        DPK_LAUNCH("ratspn_leaf_gemm_prep_kernel", ratspn_leaf_gemm_prep_kernel, dim3(R, kLeafPrepParts), dim3(256),
+                   lds, st, pa);
     }
     LeafGemmArgs a{};
     {

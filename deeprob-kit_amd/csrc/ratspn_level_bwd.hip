@@ -454,9 +454,9 @@ template <int N>
 static int launch_sum_level(const LevelBwdArgs &a, int S, hipStream_t st) {
     const dim3 grid((unsigned)cdiv(a.B, a.tile), (unsigned)a.P);
     switch (S) {
-        case 2: DPK_LAUNCH((prodsum_bwd_kernel<N, 2>), grid, dim3(256), 0, st, a); return DPK_OK;
-        case 4: DPK_LAUNCH((prodsum_bwd_kernel<N, 4>), grid, dim3(256), 0, st, a); return DPK_OK;
-        case 8: DPK_LAUNCH((prodsum_bwd_kernel<N, 8>), grid, dim3(256), 0, st, a); return DPK_OK;
+        case 2: DPK_LAUNCH("prodsum_bwd_kernel", (prodsum_bwd_kernel<N, 2>), grid, dim3(256), 0, st, a); return DPK_OK;
+        case 4: DPK_LAUNCH("prodsum_bwd_kernel", (prodsum_bwd_kernel<N, 4>), grid, dim3(256), 0, st, a); return DPK_OK;
+        case 8: DPK_LAUNCH("prodsum_bwd_kernel", (prodsum_bwd_kernel<N, 8>), grid, dim3(256), 0, st, a); return DPK_OK;
     }
     return DPK_EUNSUPPORTED;
 }
@@ -504,29 +504,27 @@ extern "C" int dpk_prodsum_backward(const float *in, const float *weight, const 
             a.tile = 4 * passes;
             const int threads = (int)align_up(P * NN, 64);
             const dim3 grid((unsigned)cdiv(B, a.tile));
-            if (N == 2) DPK_LAUNCH((prodroot_bwd_kernel<2, 8>), grid, dim3(threads), 0, st, a);
-            else if (N == 4) DPK_LAUNCH((prodroot_bwd_kernel<4, 8>), grid, dim3(threads), 0, st, a);
-            else DPK_LAUNCH((prodroot_bwd_kernel<8, 8>), grid, dim3(threads), 0, st, a);
+            if (N == 2) DPK_LAUNCH("prodsum_bwd_kernel", (prodroot_bwd_kernel<2, 8>), grid, dim3(threads), 0, st, a);
+            else if (N == 4) DPK_LAUNCH("prodsum_bwd_kernel", (prodroot_bwd_kernel<4, 8>), grid, dim3(threads), 0, st,
+                a);
+            else DPK_LAUNCH("prodsum_bwd_kernel", (prodroot_bwd_kernel<8, 8>), grid, dim3(threads), 0, st, a);
         } else {
             // sample tiles: short while the grid would leave compute units idle (more atomics per weight)
             int tile = 256;
             while (tile > 8 && cdiv(B, tile) * P < 2 * device_cus()) tile /= 2;
             a.tile = tile;
-            int rc = DPK_OK;
             if (wide16) {
                 // (a work-group per partition walks its samples one at a time: tiles short enough to cover the chip)
                 int t16 = 64;
                 while (t16 > 4 && cdiv(B, t16) * P < 2 * device_cus()) t16 /= 2;   // (longer tiles, fewer atomics: 91 against 63 us -- the walk over the tile is serial)
                 a.tile = t16;
                 const dim3 grid16((unsigned)cdiv(B, t16), (unsigned)P);
-                if (S == 8) DPK_LAUNCH((prodsum16_bwd_kernel<8>), grid16, dim3(256), 0, st, a);
-                else DPK_LAUNCH((prodsum16_bwd_kernel<16>), grid16, dim3(256), 0, st, a);
+                if (S == 8) DPK_LAUNCH("prodsum_bwd_kernel", (prodsum16_bwd_kernel<8>), grid16, dim3(256), 0, st, a);
+                else DPK_LAUNCH("prodsum_bwd_kernel", (prodsum16_bwd_kernel<16>), grid16, dim3(256), 0, st, a);
             } else {
-                rc = N == 2 ? launch_sum_level<2>(a, S, st) : (N == 4 ? launch_sum_level<4>(a, S, st) : launch_sum_level<8>(a, S, st));
+                DPK_TRY(N == 2 ? launch_sum_level<2>(a, S, st) : (N == 4 ? launch_sum_level<4>(a, S, st) : launch_sum_level<8>(a, S, st)));
             }
-            if (rc) return rc;
         }
-        DPK_CHECK_LAUNCH("prodsum_bwd_kernel");
     }
     return DPK_OK;
 }

@@ -235,11 +235,11 @@ extern "C" int dpk_ratspn_topdown(int32_t mode, int32_t dist, int64_t B, int32_t
     const int64_t groups = (B + 3) / 4;
     const unsigned grid = (unsigned)std::min<int64_t>(groups, (int64_t)device_cus() * 16);
     if (mode == 2) {
-        DPK_LAUNCH(ratspn_topdown_kernel<true>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        DPK_CHECK_LAUNCH("ratspn_topdown_kernel<true>");
+        DPK_LAUNCH("ratspn_topdown_kernel<true>", ratspn_topdown_kernel<true>, dim3(grid), dim3(256), lds,
+                   (hipStream_t)stream, a);
     } else {
-        DPK_LAUNCH(ratspn_topdown_kernel<false>, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-        DPK_CHECK_LAUNCH("ratspn_topdown_kernel<false>");
+        DPK_LAUNCH("ratspn_topdown_kernel<false>", ratspn_topdown_kernel<false>, dim3(grid), dim3(256), lds,
+                   (hipStream_t)stream, a);
     }
     return DPK_OK;
 }

@@ -534,9 +534,8 @@ int upper_mfma_tables(bool root, const float *weight, float *W, float *LW, int R
     const int P = R / 2, tiles = root ? root_ct(N, S) : cdiv((int64_t)S * N, 32);
     const int rows = root ? S : P * S, n = root ? P * N * N : N * N;
     const int extra = (root && S * N < tiles * 32) ? 1 : 0;
-    DPK_LAUNCH(upper_tables_kernel, dim3(rows + extra), dim3(256), 0, st, weight, rows, n, W, LW, (uint16_t *)frag, P, N, S,
-               root ? 1 : 0, tiles);
-    DPK_CHECK_LAUNCH("upper_tables_kernel");
+    DPK_LAUNCH("upper_tables_kernel", upper_tables_kernel, dim3(rows + extra), dim3(256), 0, st, weight, rows, n, W, LW,
+               (uint16_t *)frag, P, N, S, root ? 1 : 0, tiles);
     return DPK_OK;
 }
 
@@ -553,8 +552,8 @@ static UpperTabJob upper_tab_job(bool root, const float *weight, float *W, float
 int upper_mfma_tables_pair(const float *w0, float *W0, float *LW0, int R0, int N0, int S0, void *frag0, const float *w1,
                            float *W1, float *LW1, int R1, int N1, int C, void *frag1, hipStream_t st) {
     const UpperTabJob j0 = upper_tab_job(false, w0, W0, LW0, R0, N0, S0, frag0), j1 = upper_tab_job(true, w1, W1, LW1, R1, N1, C, frag1);
-    DPK_LAUNCH(upper_tables_pair_kernel, dim3(j0.blocks + j1.blocks), dim3(256), 0, st, j0, j1);
-    DPK_CHECK_LAUNCH("upper_tables_pair_kernel");
+    DPK_LAUNCH("upper_tables_pair_kernel", upper_tables_pair_kernel, dim3(j0.blocks + j1.blocks), dim3(256), 0, st, j0,
+               j1);
     return DPK_OK;
 }
 
@@ -562,8 +561,8 @@ int upper_mfma_forward(bool root, const float *in, const float *W, const float *
                        float *out, void *frag, bool frag_cached, hipStream_t st, const unsigned *gate) {
     const int P = R / 2, tiles = root ? root_ct(N, S) : cdiv((int64_t)S * N, 32);
     if (!frag_cached)
-        DPK_LAUNCH(upper_pack_kernel, dim3(cdiv((int64_t)P * tiles * 64, 256)), dim3(256), 0, st, W, P, N, S,
-                       root ? 1 : 0, tiles, (uint16_t *)frag, gate);
+        DPK_LAUNCH("upper_pack_kernel", upper_pack_kernel, dim3(cdiv((int64_t)P * tiles * 64, 256)), dim3(256), 0, st,
+                   W, P, N, S, root ? 1 : 0, tiles, (uint16_t *)frag, gate);
     UpperArgs a{};
     a.in = in; a.frag = (const uint16_t *)frag; a.LW = LW; a.out = out; a.B = B; a.R = R; a.S = S; a.tiles = tiles;
     const int gx = cdiv(B, 128);
@@ -576,10 +575,10 @@ int upper_mfma_forward(bool root, const float *in, const float *W, const float *
         a.ppb = ppb;
         const dim3 grid(gx, cdiv(P, ppb));
         const size_t lds = (size_t)4 * 32 * (S + 1) * 4;
-        if (N == 16) DPK_LAUNCH(prodsum_mfma_kernel<16>, grid, dim3(256), lds, st, a);
-        else DPK_LAUNCH(prodsum_mfma_kernel<8>, grid, dim3(256), lds, st, a);
+        if (N == 16) DPK_LAUNCH("upper_mfma_forward", prodsum_mfma_kernel<16>, grid, dim3(256), lds, st, a);
+        else DPK_LAUNCH("upper_mfma_forward", prodsum_mfma_kernel<8>, grid, dim3(256), lds, st, a);
     } else {
-#define DPK_ROOT(NN, CTT) DPK_LAUNCH((prodroot_mfma_kernel<NN, CTT>), dim3(gx), dim3(256), 0, st, a)
+#define DPK_ROOT(NN, CTT) DPK_LAUNCH("upper_mfma_forward", (prodroot_mfma_kernel<NN, CTT>), dim3(gx), dim3(256), 0, st, a)
         if (N == 16) {
             if (tiles <= 1) DPK_ROOT(16, 1); else if (tiles <= 2) DPK_ROOT(16, 2); else if (tiles <= 4) DPK_ROOT(16, 4);
             else DPK_ROOT(16, 8);
@@ -589,7 +588,6 @@ int upper_mfma_forward(bool root, const float *in, const float *W, const float *
         }
 #undef DPK_ROOT
     }
-    DPK_CHECK_LAUNCH("upper_mfma_forward");
     return DPK_OK;
 }
 

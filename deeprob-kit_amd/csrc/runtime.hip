@@ -2,8 +2,8 @@
 #include "common.h"
 #include <stdarg.h>
 #include <string.h>
+#include <string>
 #include <mutex>
-#include <unordered_set>
 #include <unordered_map>
 #include <vector>
 
@@ -87,18 +87,19 @@ bool slow_hint_next(const void *ws_key, int **dev_word, int *launch_seq) {
 
 int ensure_dynamic_lds(const void *kernel, int bytes) {
     static std::mutex mu;
-    static std::unordered_set<uint64_t> done;
+    static std::unordered_map<uint64_t, int> raised;   // the bytes set per (kernel, device)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     const uint64_t key = (uint64_t)(uintptr_t)kernel * 64u + (uint64_t)(dev & 63);
     std::lock_guard<std::mutex> lock(mu);
-    if (done.count(key)) return DPK_OK;
+    const auto it = raised.find(key);
+    if (it != raised.end() && it->second >= bytes) return DPK_OK;
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) {
         set_error("hipFuncSetAttribute(max dynamic LDS = %d): %s", bytes, hipGetErrorString(e));
         return DPK_ELAUNCH;
     }
-    done.insert(key);
+    raised[key] = bytes;
     return DPK_OK;
 }
 
@@ -169,8 +170,7 @@ int gated_zero(void *p, int64_t bytes, const unsigned *gate, hipStream_t st) {
     if (bytes == 0) return DPK_OK;
     int grid = cdiv(bytes / 16, 256 * 4);
     if (grid > 2048) grid = 2048;
-    DPK_LAUNCH(gated_zero_kernel, dim3(grid), dim3(256), 0, st, (uint4 *)p, bytes / 16, gate);
-    DPK_CHECK_LAUNCH("gated_zero_kernel");
+    DPK_LAUNCH("gated_zero_kernel", gated_zero_kernel, dim3(grid), dim3(256), 0, st, (uint4 *)p, bytes / 16, gate);
     return DPK_OK;
 }
 
@@ -281,8 +281,11 @@ const unsigned *params_gate(const void *key, const FpSeg *segs, int nseg, bool v
     a.verify = verify ? 1 : 0;
     a.state = state;
     const int grid = total > 0 ? cdiv(total, kFpSpan) : 1;
-    DPK_LAUNCH(params_fingerprint_kernel, dim3(grid), dim3(256), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return nullptr;
+    const auto fingerprint = [&]() -> int {
+        DPK_LAUNCH("params_fingerprint_kernel", params_fingerprint_kernel, dim3(grid), dim3(256), 0, st, a);
+        return DPK_OK;
+    };
+    if (fingerprint() != DPK_OK) return nullptr;   // (no verdict to be had: the caller rebuilds unconditionally)
     return reinterpret_cast<const unsigned *>(state + 2) + 1;
 }
 
@@ -342,12 +345,33 @@ extern "C" int dpk_ll_accumulate(const float *ll, int64_t n, double *acc, void *
     if (n == 0) return DPK_OK;
     int grid = dpk::cdiv(n, 256 * 8);
     if (grid > 1024) grid = 1024;
-    DPK_LAUNCH(dpk::ll_accumulate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ll, n, acc);
-    DPK_CHECK_LAUNCH("ll_accumulate_kernel");
+    DPK_LAUNCH("ll_accumulate_kernel", dpk::ll_accumulate_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, ll, n,
+               acc);
     return DPK_OK;
 }
 
 #ifdef DPK_TIMELINE
+namespace dpk {
+unsigned long long *timeline_buffer(const char *family, size_t bytes, int grid, int extra) {
+    static std::mutex mu;
+    static std::unordered_map<std::string, std::pair<unsigned long long *, size_t>> bufs;
+    std::lock_guard<std::mutex> lock(mu);
+    auto &b = bufs[family];
+    if (b.second < bytes) {   // (first use, or a kernel of the family with more stamps: the old buffer may still be in use)
+        b.first = nullptr;
+        (void)hipMalloc(&b.first, bytes);
+        b.second = b.first ? bytes : 0;
+    }
+    char path[64];
+    snprintf(path, sizeof(path), "/tmp/dpk_timeline%s_ptr.txt", family);
+    if (FILE *f = fopen(path, "w")) {
+        if (extra >= 0) fprintf(f, "%p %d %d\n", (void *)b.first, grid, extra);
+        else fprintf(f, "%p %d\n", (void *)b.first, grid);
+        fclose(f);
+    }
+    return b.first;
+}
+}  // namespace dpk
 // measurement builds: copy the timeline buffer of the last forward launch to the host
 extern "C" int dpk_debug_read(void *dev, void *host, int64_t bytes) {
     return hipMemcpy(host, dev, (size_t)bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;

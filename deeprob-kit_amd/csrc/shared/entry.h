@@ -7,8 +7,9 @@
 //     #include "../shared/entry.h"
 //
 // so the error text is DP_ENTRY_NS::g_error, a symbol of that library alone: two libraries in one process never share it.
-// (libdeeprob_hip.so keeps its own dpk::set_error / DPK_REQUIRE / DPK_LAUNCH / device_cus() of common.h: they cache per
-// device and carry the profiling hook.)
+// (libdeeprob_hip.so keeps its own dpk::set_error / DPK_REQUIRE / DPK_LAUNCH / device_cus() of common.h: the same shape --
+// DPK_LAUNCH(what, ...) is DP_LAUNCH with dpk's error text -- but cached per device, and DPK_LAUNCH_IN carries the
+// profiling hook.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

@@ -220,3 +220,31 @@ def test_table_cache_protocol_without_a_device():
     finally:
         hip.prepare_release()
         hip.trust_version_counters(prev)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason='with a device the launches succeed')
+def test_failed_launch_names_the_first_kernel_without_a_device():
+    """With no device every launch fails cleanly, so an entry point that launches several kernels must stop at the first
+    and name it: a later launch must not erase (or take the blame for) the failure of an earlier one."""
+    import numpy as np
+    from deeprob import hip
+    lib = hip.load_library()
+    ptr = lambda a: a.ctypes.data
+    # depthwise 2 x 2 product + root layer: the rows' log-softmax runs before the fused kernel
+    C, H, W, OH, OW, K, B = 2, 2, 2, 1, 1, 3, 4
+    ws_bytes = lib.dpk_spatial_prodroot_workspace_bytes(C, OH, OW, K)
+    assert ws_bytes == 512
+    x, weight = np.zeros((B, C, H, W), np.float32), np.zeros((K, C * OH * OW), np.float32)
+    out, ws = np.zeros((B, K), np.float32), np.zeros(ws_bytes, np.uint8)
+    rc = lib.dpk_spatial_prodroot_forward(ptr(x), B, C, H, W, OH, OW, 2, 2, 1, 1, 1, 1, 0, 0, ptr(weight), K, ptr(out),
+                                          ptr(ws), ws_bytes, None)
+    assert rc == hip.DPK_ELAUNCH
+    assert lib.dpk_last_error().decode().startswith('rowwise_logsoftmax_kernel:'), lib.dpk_last_error()
+    # masked linear layer: the masked weights are formed before the product
+    n_in, n_out = 3, 2
+    ws_bytes = lib.dpk_masked_linear_workspace_bytes(n_in, n_out)
+    x, Wt, M = np.zeros((B, n_in), np.float32), np.zeros((n_out, n_in), np.float32), np.ones((n_out, n_in), np.float32)
+    b, y, ws = np.zeros(n_out, np.float32), np.zeros((B, n_out), np.float32), np.zeros(ws_bytes, np.uint8)
+    rc = lib.dpk_masked_linear_forward(ptr(x), B, n_in, n_out, ptr(Wt), ptr(M), ptr(b), ptr(y), ptr(ws), ws_bytes, None)
+    assert rc == hip.DPK_ELAUNCH
+    assert lib.dpk_last_error().decode().startswith('maf_mul_kernel:'), lib.dpk_last_error()
