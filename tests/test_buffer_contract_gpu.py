@@ -57,6 +57,9 @@ REPLAY = [
     ('test_ratspn_gpu', 'test_training_forward_single_launch_matches_layer_chain', dict(B={1, 37}, evidence='marginalised')),
     ('test_ratspn_gpu', 'test_folded_level_autograd_matches_layer_chain', {'#': {0, 2, 3, 5, 11}}),
     ('test_ratspn_gpu', 'test_unit_scale_fused_shapes_vs_oracle', {'#': {0, 4}}),
+    ('test_ratspn_gaussian_gpu', 'test_leaf_forward_vs_float64', dict(name={'pad2', 'wide16_d1'}, B={1, 33}, kind='nan')),
+    ('test_ratspn_gaussian_gpu', 'test_leaf_backward_vs_float64', dict(name={'ad4', 'odd3'}, B=300, kind='nan', sign='mixed',
+                                                                       x_grad=True)),
     ('test_dropout_gpu', 'test_ratspn_dropout_replayed_by_the_oracle', {}),
     ('test_dropout_gpu', 'test_dgcspn_dropout_replayed_by_the_oracle', {}),
     # ---- DGC-SPN ------------------------------------------------------------------------------------------------

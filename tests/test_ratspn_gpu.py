@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from oracle import ratspn_oracle as orc
+from tests.ratspn_gaussian_cases import ill_regime
 from tests.util import rel_err, grad_err, state_to_model, report_measured
 
 pytestmark = pytest.mark.gpu
@@ -1086,30 +1087,7 @@ def test_leaf_parameter_gradients_ill_conditioned(regime, B):
     from deeprob.spn.models import GaussianRatSpn
     gen = torch.Generator().manual_seed(B + len(regime))
     model = GaussianRatSpn(64, rg_depth=2, rg_repetitions=4, rg_batch=8, rg_sum=4, optimize_scale=True, random_state=3).eval()
-    I = model.base_layer.loc.shape[1]
-    with torch.no_grad():
-        if regime == 'mu_over_s_50':
-            centre = 5.0 + torch.randn(64, generator=gen)
-            x = centre + 0.1 * torch.randn(B, 64, generator=gen)
-            spread, scale = 0.05, 0.1
-        elif regime == 'uint8_range':
-            centre = 40.0 + 170.0 * torch.rand(64, generator=gen)
-            x = (centre + 3.0 * torch.randn(B, 64, generator=gen)).round().clamp(0, 255)
-            spread, scale = 2.0, 3.0
-        else:
-            centre = torch.zeros(64)
-            offs = torch.tensor([0.0, 60.0, 128.0, 200.0])
-            x = offs[torch.randint(0, 4, (B, 1), generator=gen)] + torch.randn(B, 64, generator=gen)    # (a sample = one cluster)
-            spread, scale = 0.5, 1.0
-        loc = torch.empty_like(model.base_layer.loc)
-        mask = model.base_layer.mask                      # [regions, positions] -> variable
-        for k in range(I):
-            base = centre[mask.clamp_min(0)]
-            if regime == 'clusters':
-                base = base + offs[k % 4]
-            loc[:, k] = base + spread * torch.randn(base.shape, generator=gen)
-        model.base_layer.loc.copy_(loc)
-        model.base_layer.scale.fill_(scale).mul_(1.0 + 0.2 * torch.rand(model.base_layer.scale.shape, generator=gen))
+    x = ill_regime(model.base_layer, regime, B, gen)      # (the regimes: tests/ratspn_gaussian_cases.py)
     ref = {}
     for dt in (torch.float64, torch.float32):
         sd = {k: (v.detach().to(dt).clone() if v.is_floating_point() else v.detach().clone()) for k, v in model.state_dict().items()}
