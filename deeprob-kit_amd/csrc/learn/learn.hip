@@ -358,7 +358,7 @@ bool kmeans_ok(int n_restarts, int n_clusters, int kmax, const char *who) {
 extern "C" {
 
 const char *dpl_last_error(void) { return dpl_detail::g_error; }
-int dpl_abi_version(void) { return 5; }
+int dpl_abi_version(void) { return 6; }
 
 int dpl_column_counts(const uint8_t *x, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
                       const int32_t *item_col, const int64_t *item_row_off, const int32_t *item_n, int64_t n_items,

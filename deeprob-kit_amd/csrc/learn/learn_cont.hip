@@ -1,7 +1,7 @@
 // libdeeprob_learn.so, continuous data: the statistics of LearnSPN on all-Gaussian data, segmented over the tasks of one
 // generation (include/deeprob_learn.h, last section).  Built with -ffp-contract=off like learn.hip: every float64
 // expression is evaluated operation by operation in the order the header states.
-#include "learn_common.h"
+#include "learn_gram.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "libdeeprob_learn is written for gfx950 (MI355X)"
@@ -12,6 +12,7 @@ namespace {
 using dpl_detail::common_ok;
 using dpl_detail::kMaxGrid;
 using dpl_detail::kThreads;
+using dpl_detail::kTile;
 using dpl_detail::set_error;
 using dpl_detail::sum_in_order;
 
@@ -64,15 +65,8 @@ __global__ __launch_bounds__(kThreads) void ecdf_ranks_kernel(
 }
 
 // ---- random-feature Gram matrices ------------------------------------------------------------------------------------
-constexpr int kTile = DPL_GRAM_TILE;      // features of a tile, and rows of phi held in LDS at a time
-static_assert(kTile == 32 && DPL_GRAM_PARTIAL == kTile * kTile + kTile && kThreads == 256, "2 x 2 products per thread");
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// kMfma: the products of a 32-row step run on v_mfma_f64_16x16x4_f64 -- wave v owns the 16 x 16 quarter (v >> 1, v & 1) of
-// the tile pair, A = phi_i^T and B = phi_j taken from LDS one f64 per lane (A: feature lane & 15, row lane >> 4 of the
-// 4-row block; B likewise), D: column lane & 15, row (lane >> 4) + 4 * register -- else on the VALU, 2 x 2 products per
-// thread.
+// The products of a step, on the matrix core or on the VALU, and the layout of a unit's partial sums are learn_gram.h's
+// (shared with dpl_gmm_mstats).
 template <bool kMfma>
 __global__ __launch_bounds__(kThreads) void rdc_gram_partial_kernel(
     const int32_t *__restrict__ ranks, const float *__restrict__ w, const float *__restrict__ b, int k,
@@ -88,11 +82,9 @@ __global__ __launch_bounds__(kThreads) void rdc_gram_partial_kernel(
     const float *wt = w + task_feat_off[t], *bt = b + task_feat_off[t];
     const bool same = i0 == j0;             // (block-uniform)
     const int sides = same ? 1 : 2;
-    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+    const int tid = threadIdx.x;
     const double(*pj)[kTile + 1] = same ? phi[0] : phi[1];
-    double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0, cs = 0.0;
-    double4_t acc = {0.0, 0.0, 0.0, 0.0};
-    const int wave = tid >> 6, lane = tid & 63, qi = (wave >> 1) * 16, qj = (wave & 1) * 16;
+    dpl_detail::GramTile<kMfma> tile;
     for (int rs = 0; rs < nr; rs += kTile) {        // (nr is block-uniform: every thread takes every trip)
         for (int e = tid; e < sides * kTile * kTile; e += kThreads) {
             const int side = e >> 10, rr = (e >> 5) & (kTile - 1), fl = e & (kTile - 1);
@@ -106,36 +98,10 @@ __global__ __launch_bounds__(kThreads) void rdc_gram_partial_kernel(
             phi[side][rr][fl] = val;
         }
         __syncthreads();
-        if constexpr (kMfma) {
-            for (int r4 = 0; r4 < kTile; r4 += 4) {
-                const int rr = r4 + (lane >> 4);
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(phi[0][rr][qi + (lane & 15)], pj[rr][qj + (lane & 15)], acc, 0, 0, 0);
-            }
-            if (tid < kTile)
-                for (int rr = 0; rr < kTile; ++rr) cs += phi[0][rr][tid];
-        } else {
-            for (int rr = 0; rr < kTile; ++rr) {
-                const double x0 = phi[0][rr][ti], x1 = phi[0][rr][ti + 16], y0 = pj[rr][tj], y1 = pj[rr][tj + 16];
-                a00 += x0 * y0;
-                a01 += x0 * y1;
-                a10 += x1 * y0;
-                a11 += x1 * y1;
-                if (tid < kTile) cs += phi[0][rr][tid];
-            }
-        }
+        tile.step(phi[0], pj);
         __syncthreads();
     }
-    double *out = partial + u * DPL_GRAM_PARTIAL;
-    if constexpr (kMfma) {
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) out[(qi + (lane >> 4) + 4 * reg) * kTile + qj + (lane & 15)] = acc[reg];
-    } else {
-        out[ti * kTile + tj] = a00;
-        out[ti * kTile + tj + 16] = a01;
-        out[(ti + 16) * kTile + tj] = a10;
-        out[(ti + 16) * kTile + tj + 16] = a11;
-    }
-    if (tid < kTile) out[kTile * kTile + tid] = cs;
+    tile.store(partial + u * DPL_GRAM_PARTIAL);
 }
 
 __global__ __launch_bounds__(kThreads) void rdc_gram_reduce_kernel(
@@ -148,8 +114,7 @@ __global__ __launch_bounds__(kThreads) void rdc_gram_reduce_kernel(
     const int t = unit_task[u0], i0 = unit_i0[u0], j0 = unit_j0[u0], F = task_f[t];
     double *g = G + task_g_off[t];
     for (int e = threadIdx.x; e < DPL_GRAM_PARTIAL; e += kThreads) {
-        double total = partial[u0 * DPL_GRAM_PARTIAL + e];
-        for (int c = 1; c < units; ++c) total += partial[(u0 + c) * DPL_GRAM_PARTIAL + e];
+        const double total = dpl_detail::group_total(partial, DPL_GRAM_PARTIAL, u0, units, e);
         if (e < kTile * kTile) {
             const int i = i0 + (e >> 5), j = j0 + (e & (kTile - 1));
             if (i < F && j < F) {

@@ -20,8 +20,10 @@ load_library, call, _read_header = BINDING.load, BINDING.call, BINDING.read_head
 hip.bound_module(__name__)         # LIB_PATH, HEADER_PATH, ABI_VERSION and _lib are views of BINDING
 
 
-#: kernel launches outside the Lloyd loop, kernel launches inside it, device-to-host reads, host-to-device uploads
-COUNTERS = {'kernels': 0, 'lloyd_kernels': 0, 'reads': 0, 'lloyd_reads': 0, 'uploads': 0}
+#: kernel launches outside the Lloyd loop, kernel launches inside it, device-to-host reads, host-to-device uploads; and the
+#: launches, reads and uploads of the EM loop of the Gaussian-mixture row split, counted apart (``GmmBatch``)
+COUNTERS = {'kernels': 0, 'lloyd_kernels': 0, 'reads': 0, 'lloyd_reads': 0, 'uploads': 0,
+            'gmm_kernels': 0, 'gmm_reads': 0, 'gmm_uploads': 0}
 
 
 def reset_counters():
@@ -29,20 +31,20 @@ def reset_counters():
         COUNTERS[k] = 0
 
 
-def read(t: torch.Tensor, lloyd: bool = False) -> np.ndarray:
+def read(t: torch.Tensor, lloyd: bool = False, gmm: bool = False) -> np.ndarray:
     """One device-to-host read (it waits for the stream)."""
-    COUNTERS['lloyd_reads' if lloyd else 'reads'] += 1
+    COUNTERS['gmm_reads' if gmm else 'lloyd_reads' if lloyd else 'reads'] += 1
     return t.cpu().numpy()
 
 
-def upload(device, **arrays):
-    """Host tables of one launch (int32, int64, uint8 or float32), packed into one int64-aligned buffer and copied in ONE
-    transfer: a dict of device views of the host arrays' types."""
-    COUNTERS['uploads'] += 1
+def upload(device, _counter='uploads', **arrays):
+    """Host tables of one launch (int32, int64, uint8, float32 or float64), packed into one int64-aligned buffer and copied
+    in ONE transfer: a dict of device views of the host arrays' types."""
+    COUNTERS[_counter] += 1
     parts, spans, o = [], {}, 0
     for name, a in arrays.items():
         a = np.ascontiguousarray(a)
-        if a.dtype not in (np.int32, np.int64, np.uint8, np.float32):
+        if a.dtype not in (np.int32, np.int64, np.uint8, np.float32, np.float64):
             raise TypeError('{}: {}'.format(name, a.dtype))
         raw = a.view(np.uint8).reshape(-1)
         pad = (-len(raw)) % 8
@@ -57,7 +59,7 @@ def upload(device, **arrays):
     for name, (o, n, dtype, shape) in spans.items():
         view = dev[o:o + n]
         out[name] = view.view({np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8,
-                               np.dtype(np.float32): torch.float32}[np.dtype(dtype)]).reshape(shape)
+                               np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64}[np.dtype(dtype)]).reshape(shape)
     out['_buffer'] = dev
     return out
 
@@ -254,6 +256,220 @@ class KMeansBatch:
              self.R, self.C, *kmax, cent.data_ptr(), labels.data_ptr(), self.n_lab, inertia.data_ptr(), sizes.data_ptr(), st)
         COUNTERS['kernels'] += 1
         return read(inertia), read(sizes), labels, iterations
+
+
+#: the Gaussian-mixture row split: scikit-learn's GaussianMixture(covariance_type='full', n_init=3) defaults
+GMM_N_INIT, GMM_TOL, GMM_REG_COVAR, GMM_MAX_ITER = 3, 1e-3, 1e-6, 100
+#: rows of one unit of ``dpl_gmm_mstats``, and the units whose partial sums fit in 256 MiB
+GMM_ROW_CHUNK = 1024
+GMM_MAX_UNITS = (256 << 20) // (8 * CONSTANTS['DPL_GMM_PARTIAL'])
+#: whether the products of ``dpl_gmm_mstats`` run on v_mfma_f64_16x16x4_f64 (else on the VALU): see DESIGN.md 14.5
+GMM_USE_MFMA = True
+
+
+def gmm_features(cols, ks):
+    """``(feat_col, feat_val)`` of a task's columns: a column with K <= 2 (or a float column, ``ks`` None) is one feature
+    (value -1: the column's value), a column with K > 2 is K indicator features (header, "Gaussian-mixture row splits")."""
+    fc, fv = [], []
+    for p, col in enumerate(cols):
+        k = 1 if ks is None else int(ks[p])
+        if k <= 2:
+            fc.append(int(col))
+            fv.append(-1)
+        else:
+            fc += [int(col)] * k
+            fv += list(range(k))
+    return fc, fv
+
+
+def gmm_m_step(stats: np.ndarray, pivot: np.ndarray, n: int) -> np.ndarray:
+    """The parameters ``[C, 1 + F + F * F]`` (``k_c``, ``mu_c``, ``L_c^-1``: the layout ``dpl_gmm_estep`` takes) from the
+    moments ``stats [C, 1 + F + F * F]`` about ``pivot [C, F]`` over ``n`` rows: the M-step of DESIGN.md 14.5 with the
+    covariance as ``M / N_c - (mu - p)(mu - p)^T + 1e-6 I`` from the LOWER triangle of ``M``.  ValueError when a covariance
+    has no Cholesky factor (scikit-learn's rule)."""
+    C, F = pivot.shape
+    out = np.zeros((C, 1 + F + F * F))
+    for c in range(C):
+        n_c = stats[c, 0] + 10.0 * np.finfo(np.float64).eps
+        d = stats[c, 1:1 + F] / n_c
+        low = np.tril(stats[c, 1 + F:].reshape(F, F))
+        sigma = (low + np.tril(low, -1).T) / n_c - np.outer(d, d)
+        sigma[np.diag_indices(F)] += GMM_REG_COVAR
+        try:
+            chol = np.linalg.cholesky(sigma)
+        except np.linalg.LinAlgError:
+            raise ValueError("Fitting the mixture model failed because some components have ill-defined empirical covariance "
+                             "(for instance caused by singleton or collapsed samples): use fewer components") from None
+        out[c, 0] = np.log(n_c / n) - 0.5 * F * np.log(2.0 * np.pi) - np.sum(np.log(np.diag(chol)))
+        out[c, 1:1 + F] = pivot[c] + d
+        out[c, 1 + F:] = np.tril(np.linalg.inv(chol)).reshape(-1)
+    return out
+
+
+class GmmBatch:
+    """The Gaussian-mixture EM of all row-splitting tasks of one generation, ``GMM_N_INIT`` initialisations each (header:
+    "Gaussian-mixture row splits"; the definition: DESIGN.md 14.5).  ``tasks`` as for :class:`KMeansBatch`, ``seeds`` an
+    ``[GMM_N_INIT, n_comp]`` array.  A PAIR is ``(task, initialisation)``.  ``launch`` is one E-step and / or one moments
+    pass over listed pairs; ``run`` is the whole loop."""
+
+    def __init__(self, data: DeviceData, row_index, tasks, n_comp: int, kmax: int = None):
+        self.data, self.row_index, self.tasks, self.C, self.T, self.R = data, row_index, tasks, int(n_comp), len(tasks), GMM_N_INIT
+        self.kmax = kmax
+        feat_off, fc, fv, lab_off, n_lab = [], [], [], [], 0
+        for row_off, n, cols, ks, _ in tasks:
+            c, v = gmm_features(cols, ks)
+            feat_off.append(len(fc))
+            fc, fv = fc + c, fv + v
+            lab_off.append(n_lab)
+            n_lab += int(n)
+        self.fs = [b - a for a, b in zip(feat_off, feat_off[1:] + [len(fc)])]
+        self.feat_off, self.feat_col, self.feat_val, self.lab_off, self.n_lab = feat_off, fc, fv, lab_off, n_lab
+        self.ns = [int(t[1]) for t in tasks]
+        self.tab = upload(data.device, 'gmm_uploads', row_off=np.asarray([t[0] for t in tasks], np.int64),
+                          n=np.asarray(self.ns, np.int32), lab_off=np.asarray(lab_off, np.int64),
+                          feat_off=np.asarray(feat_off, np.int32), f=np.asarray(self.fs, np.int32),
+                          feat_col=np.asarray(fc, np.int32), feat_val=np.asarray(fv, np.int32))
+        dev = data.device
+        self.resp = torch.empty((self.R, n_lab, self.C), dtype=torch.float64, device=dev)
+        self.labels = torch.empty((self.R, n_lab), dtype=torch.uint8, device=dev)
+        self.lse = torch.empty((self.R, n_lab), dtype=torch.float64, device=dev)
+
+    def per(self, t):
+        return 1 + self.fs[t] + self.fs[t] * self.fs[t]
+
+    def launch(self, e_pairs, m_pairs, par, row_chunk: int = GMM_ROW_CHUNK, max_units: int = GMM_MAX_UNITS, mfma: bool = None):
+        """One E-step over the pairs ``e_pairs`` and one moments pass over ``m_pairs`` (lists of ``(task, init)``; either
+        may be empty), under the parameters ``par[(task, init)]`` (``[C, 1 + F + F * F]``: the E-step reads all of it, the
+        moments pass its means as the pivot): ONE upload of parameters and tables.  Returns ``(out, stat_off, partials)``:
+        ``out`` one device float64 tensor holding the summed ``lse`` of ``e_pairs`` and then, for ``m_pairs[i]`` at
+        ``len(e_pairs) + stat_off[i]``, its ``[C, 1 + F + F * F]`` moments."""
+        lib, d, C = load_library(), self.data, self.C
+        listed = list(dict.fromkeys(list(e_pairs) + list(m_pairs)))
+        par_off, at = {}, 0
+        for a in listed:
+            par_off[a] = at
+            at += C * self.per(a[0])
+        flat = np.concatenate([np.asarray(par[a], np.float64).reshape(-1) for a in listed])
+        assert len(flat) == at
+        stat_off = np.concatenate([[0], np.cumsum([C * self.per(t) for t, _ in m_pairs])]).astype(np.int64)
+        block_pair, block_row0 = _row_blocks([self.ns[t] for t, _ in e_pairs])
+        groups = []                 # (pair position, component, i0, j0) of the moments pass, tile pairs i0 <= j0
+        for a, (t, _) in enumerate(m_pairs):
+            for c in range(C):
+                for i0 in range(0, self.fs[t], CONSTANTS['DPL_GRAM_TILE']):
+                    for j0 in range(i0, self.fs[t], CONSTANTS['DPL_GRAM_TILE']):
+                        groups.append((a, c, i0, j0))
+        calls, g = [], 0
+        while g < len(groups):
+            unit, group, n_units = {key: [] for key in ('pair', 'comp', 'i0', 'j0', 'row0', 'rows')}, {'unit0': [], 'units': []}, 0
+            while g < len(groups):
+                a, c, i0, j0 = groups[g]
+                n = self.ns[m_pairs[a][0]]
+                chunks = -(-n // row_chunk)
+                if chunks > max_units:
+                    raise HipError("gmm: a task of {} rows needs {} partial sums per tile, over the 256 MiB of one call"
+                                   .format(n, chunks))
+                if n_units + chunks > max_units:
+                    break
+                group['unit0'].append(n_units)
+                group['units'].append(chunks)
+                for k in range(chunks):
+                    for key, v in zip(('pair', 'comp', 'i0', 'j0', 'row0', 'rows'),
+                                      (a, c, i0, j0, k * row_chunk, min(row_chunk, n - k * row_chunk))):
+                        unit[key].append(v)
+                n_units += chunks
+                g += 1
+            calls.append((unit, group, n_units))
+        tables = dict(par=flat)
+        if e_pairs:
+            tables.update(e_task=np.asarray([t for t, _ in e_pairs], np.int32), e_init=np.asarray([i for _, i in e_pairs], np.int32),
+                          e_par=np.asarray([par_off[a] for a in e_pairs], np.int64), block_pair=block_pair, block_row0=block_row0)
+        if m_pairs:
+            tables.update(m_task=np.asarray([t for t, _ in m_pairs], np.int32), m_init=np.asarray([i for _, i in m_pairs], np.int32),
+                          m_par=np.asarray([par_off[a] for a in m_pairs], np.int64), m_stat=stat_off[:-1].copy())
+        for k, (unit, group, _) in enumerate(calls):
+            tables.update({'u{}_{}'.format(k, key): np.asarray(v, np.int32) for key, v in list(unit.items()) + list(group.items())})
+        up = upload(d.device, 'gmm_uploads', **tables)
+        p, q = {k: v.data_ptr() for k, v in self.tab.items()}, {k: v.data_ptr() for k, v in up.items()}
+        head = (d.x.data_ptr(), int(d.is_float)) + d.head(self.row_index)[1:]
+        task = (p['row_off'], p['n'], p['lab_off'], p['feat_off'], p['f'], p['feat_col'], p['feat_val'])
+        out = torch.empty(len(e_pairs) + int(stat_off[-1]), dtype=torch.float64, device=d.device)
+        st = _stream(d.device)
+        if e_pairs:
+            call(lib.dpl_gmm_estep, *head, *task, q['e_task'], q['e_init'], q['e_par'], len(e_pairs), q['block_pair'],
+                 q['block_row0'], len(block_pair), self.R, C, q['par'], self.resp.data_ptr(), self.labels.data_ptr(),
+                 self.lse.data_ptr(), self.n_lab, out.data_ptr(), st)
+            COUNTERS['gmm_kernels'] += 2
+        partials = []
+        for k, (unit, group, n_units) in enumerate(calls):
+            partial = torch.empty(n_units * CONSTANTS['DPL_GMM_PARTIAL'], dtype=torch.float64, device=d.device)
+            u = {key: q['u{}_{}'.format(k, key)] for key in list(unit) + list(group)}
+            call(lib.dpl_gmm_mstats, *head, *task, q['m_task'], q['m_init'], q['m_par'], q['m_stat'], len(m_pairs), u['pair'],
+                 u['comp'], u['i0'], u['j0'], u['row0'], u['rows'], n_units, u['unit0'], u['units'], len(group['units']), C,
+                 q['par'], self.resp.data_ptr(), self.n_lab, int(GMM_USE_MFMA if mfma is None else mfma), partial.data_ptr(),
+                 out.data_ptr() + 8 * len(e_pairs), st)
+            COUNTERS['gmm_kernels'] += 2
+            partials.append(partial)
+        return out, stat_off[:-1], partials
+
+    def pivots(self, cent: np.ndarray, km):
+        """``{(task, init): [C, F]}``: the k-means centroids as feature vectors."""
+        out = {}
+        for t, (_, _, cols, ks, _) in enumerate(self.tasks):
+            width = len(cols) * (km.kmax or 1)
+            for i in range(self.R):
+                cen = cent[km.cent_off[t] + i * self.C * width:][:self.C * width].reshape(self.C, len(cols), -1)
+                feats = []
+                for p in range(len(cols)):
+                    k = 1 if ks is None else int(ks[p])
+                    feats += [cen[:, p, 0 if ks is None else 1]] if k <= 2 else [cen[:, p, v] for v in range(k)]
+                out[(t, i)] = np.stack(feats, axis=1)
+        return out
+
+    def run(self):
+        """``(best [T] winning initialisation, lower [T, R] bounds, sizes [T, R, C] int64, labels [R, n_lab] device uint8,
+        EM iterations)``; ``self.host_labels`` is the host copy of the labels the sizes were counted from: the Lloyd initialisations, then the loop of DESIGN.md 14.5 with every pair advancing together and
+        a converged pair leaving the launch tables after the label pass under its final parameters."""
+        C, R = self.C, self.R
+        km = KMeansBatch(self.data, self.row_index, self.tasks, R, C, self.kmax)
+        _, _, km_labels, _ = km.run()
+        self.km_labels = km_labels
+        self.resp.zero_()
+        self.resp.scatter_(2, km_labels.long().unsqueeze(-1), 1.0)       # the hard labels as 0/1 responsibilities
+        pivot = self.pivots(read(km.cent, gmm=True), km)
+        pairs = [(t, i) for t in range(self.T) for i in range(R)]
+        # the pivot of the first moments pass is the centroid (only the means of `par` are read there)
+        par = {a: np.concatenate([np.zeros((C, 1)), pivot[a], np.zeros((C, self.fs[a[0]] ** 2))], axis=1) for a in pairs}
+        out, stat_off, _ = self.launch([], pairs, par)
+        host = read(out, gmm=True)
+        for k, a in enumerate(pairs):
+            stats = host[stat_off[k]:stat_off[k] + C * self.per(a[0])].reshape(C, -1)
+            par[a] = gmm_m_step(stats, pivot[a], self.ns[a[0]])
+        lower = {a: -np.inf for a in pairs}
+        active, final, iterations = list(pairs), [], 0
+        while active or final:
+            listed = active + final
+            out, stat_off, _ = self.launch(listed, active, par)
+            host = read(out, gmm=True)
+            final, still = [], []
+            iterations += 1 if active else 0
+            for k, a in enumerate(active):
+                t = a[0]
+                bound = host[k] / float(self.ns[t])
+                stats = host[len(listed) + stat_off[k]:][:C * self.per(t)].reshape(C, -1)
+                par[a] = gmm_m_step(stats, par[a][:, 1:1 + self.fs[t]], self.ns[t])
+                change = bound - lower[a]
+                lower[a] = bound
+                if abs(change) < GMM_TOL or iterations == GMM_MAX_ITER:
+                    final.append(a)
+                else:
+                    still.append(a)
+            active = still
+        bounds = np.array([[lower[(t, i)] for i in range(R)] for t in range(self.T)])
+        labels = self.host_labels = read(self.labels, gmm=True)
+        sizes = np.array([[np.bincount(labels[i, self.lab_off[t]:self.lab_off[t] + self.ns[t]], minlength=C)[:C]
+                           for i in range(R)] for t in range(self.T)], np.int64)
+        return np.argmax(bounds, axis=1), bounds, sizes, self.labels, iterations
 
 
 # ---- continuous data (the last section of the header) ---------------------------------------------------------------------

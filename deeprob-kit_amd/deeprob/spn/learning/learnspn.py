@@ -6,8 +6,9 @@ The reference pops one task at a time from a FIFO queue.  The queue is breadth f
 order; a generation is processed here as a whole: column statistics of all its tasks in one launch, the operations decided
 from them, the draws of the ``RandomState`` made on the host in queue order (they need only sizes known by then), the
 statistics of all column-splitting tasks, the co-occurrence counts of all Chow-Liu leaf tasks (``learn_leaf`` the function
-``leaf.learn_binary_clt``), the k-means of all row-splitting tasks together, and one partition launch that
-writes the next generation's row-index array.  The loop is written once; what depends on the kind of the columns --
+``leaf.learn_binary_clt``), the k-means -- or, with ``split_rows`` the function ``splitting.cluster.gmm``, the
+Gaussian-mixture EM (``hip.learn.GmmBatch``) -- of all row-splitting tasks together, and one partition
+launch that writes the next generation's row-index array.  The loop is written once; what depends on the kind of the columns --
 discrete (:class:`DiscreteColumns`, below) or Gaussian (``learnspn_cont.GaussianColumns``) -- is asked of a column-kind
 object.  See DESIGN.md, "LearnSPN on the device".
 """
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from deeprob.hip import HipError, learn as L
-from deeprob.spn.learning.splitting import rdc as R, hist as H, entropy as SE, gini as SG, gvs as SV
+from deeprob.spn.learning.splitting import rdc as R, hist as H, entropy as SE, gini as SG, gvs as SV, cluster as SC
 from deeprob.spn.learning.leaf import learn_binary_clt, BERNOULLI_MESSAGE
 from deeprob.spn.structure.leaf import LeafType, Bernoulli, Categorical
 
@@ -39,7 +40,15 @@ CLT_LAUNCHES_PER_GENERATION = 4
 HIST_FUNCTIONS = ((SE.entropy_cols, H.ENTROPY), (SE.entropy_adaptive_cols, H.ENTROPY_ADAPTIVE), (SG.gini_cols, H.GINI),
                   (SG.gini_adaptive_cols, H.GINI_ADAPTIVE), (SV.gvs_cols, 'gvs'), (SV.rgvs_cols, 'rgvs'))
 
+#: the row-split functions of this package that ``split_rows`` takes, recognised by identity, and the split of each
+ROWS_FUNCTIONS = ((SC.gmm, 'gmm'), (SC.kmeans, 'kmeans'))
+
 _last_info = {}
+
+
+def rows_split(split_rows):
+    """The split of one of ``ROWS_FUNCTIONS``, None for anything else (a string included)."""
+    return next((split for fn, split in ROWS_FUNCTIONS if fn is split_rows), None)
 
 
 def hist_split(split_cols):
@@ -50,7 +59,9 @@ def hist_split(split_cols):
 def last_info() -> dict:
     """What the last ``learn_spn`` recorded: ``generations``, ``tasks_per_generation``, ``kernels`` (launches of the learn
     library outside the Lloyd loop; ``torch.sort`` and the gathers in front of it are not counted), ``reads``, ``uploads``,
-    ``launches`` (the sum of the three), ``lloyd_launches`` and ``lloyd_iterations``; on discrete data also
+    ``launches`` (the sum of the three), ``lloyd_launches`` and ``lloyd_iterations``; ``gmm_kernels``, ``gmm_reads``,
+    ``gmm_uploads`` and ``gmm_iterations``: the launches, reads, uploads and iterations of the Gaussian-mixture EM, counted
+    apart (not part of ``launches``; all zero without ``split_rows=gmm``); on discrete data also
     ``launches_per_generation``, the bound DESIGN.md derives for ``launches`` there (``LAUNCHES_PER_GENERATION``, plus
     ``CLT_LAUNCHES_PER_GENERATION`` with Chow-Liu leaves); and ``clt_leaves``: one record per Chow-Liu leaf in queue order,
     with its ``scope``, ``root`` (a variable), ``tree``, ``params``, ``n`` and ``rows`` -- the leaf's slice of its
@@ -127,7 +138,9 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
         _method(learn_leaf, KNOWN_LEAF, BUILT_LEAF, "Unknown learn leaf method called {}", 'learn_leaf')
     elif any(d is not Bernoulli for d in distributions):
         raise ValueError(BERNOULLI_MESSAGE)                                               # leaf.py:138-139
-    _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
+    rows_fn = rows_split(split_rows)         # (this package's gmm / kmeans functions, by identity; the string 'gmm' is not built)
+    if rows_fn is None:
+        _method(split_rows, KNOWN_ROWS, BUILT_ROWS, "Unknown split rows method called {}", 'split_rows')
     rdc = split_cols is R.rdc_cols           # (this package's own function, by identity; the string 'rdc' is not built)
     hist = hist_split(split_cols)            # (likewise the entropy, Gini and G-test functions)
     if not rdc:
@@ -137,7 +150,8 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
         check_random_state(leaf_kw['random_state'])             # (the type; a RandomState is returned as it is, untouched)
     else:
         leaf_kw = _kwargs(learn_leaf_kwargs, {'alpha': 0.1}, 'learn_mle')
-    rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if split_rows == 'kmeans' else {'a': 2.0, 'b': 2.0}, split_rows)
+    clustered = rows_fn is not None or split_rows == 'kmeans'
+    rows_kw = _kwargs(split_rows_kwargs, {'n': 2} if clustered else {'a': 2.0, 'b': 2.0}, rows_fn or split_rows)
     if rdc:
         cols_kw = _kwargs(split_cols_kwargs, {'d': R.D_DEFAULT, 'k': R.K_DEFAULT, 's': R.S_DEFAULT}, 'rdc_cols')
     elif hist is not None:
@@ -148,8 +162,8 @@ def check_arguments(kind, data, distributions, domains, learn_leaf, split_rows, 
         cols_kw = _kwargs(split_cols_kwargs, {'a': 2.0, 'b': 2.0} if split_cols == 'random' else {'p': 5.0}, split_cols)
     if kind.smoothed_leaves and leaf_kw['alpha'] < 0.0:
         raise ValueError("The Laplace smoothing factor must be non-negative")
-    if split_rows == 'kmeans' and not 1 <= int(rows_kw['n']) <= L.DPL_MAX_CLUSTERS:
-        raise ValueError("k-means on the HIP path takes 1..{} clusters".format(L.DPL_MAX_CLUSTERS))
+    if clustered and not 1 <= int(rows_kw['n']) <= L.DPL_MAX_CLUSTERS:
+        raise ValueError("{} on the HIP path takes 1..{} clusters".format('gmm' if rows_fn == 'gmm' else 'k-means', L.DPL_MAX_CLUSTERS))
     kind.check_columns(cols_kw if rdc else None)
     return leaf_kw, rows_kw, cols_kw
 
@@ -384,6 +398,10 @@ class DiscreteColumns:
         return L.KMeansBatch(self.data, row_index, [(t.row_off, t.n, t.scope, [self.ks[s] for s in t.scope], t.draw) for t in tasks],
                              KMEANS_RESTARTS, n_clusters, self.kmax)
 
+    def gmm_batch(self, row_index, tasks, n_clusters):
+        return L.GmmBatch(self.data, row_index, [(t.row_off, t.n, t.scope, [self.ks[s] for s in t.scope], t.draw) for t in tasks],
+                          n_clusters, self.kmax)
+
     def clt_leaves(self, row_index, tasks, alpha):
         """The Chow-Liu leaf of every task (learning/leaf.py:149-150; ``t.draw`` is the position of its root): the
         co-occurrence counts of all of them from one launch and one read, then per task the host half of
@@ -422,7 +440,11 @@ def learn_spn(
     Built: discrete data with ``Bernoulli`` (domain ``[0, 1]``) and ``Categorical`` leaves, every domain
     ``list(range(K))`` with ``K <= 16``; ``learn_leaf='mle'``, or the function
     ``deeprob.spn.learning.leaf.learn_binary_clt`` itself (recognised by identity; all-``Bernoulli`` data): Chow-Liu tree
-    leaves, see below; ``split_rows`` in ``'kmeans'``, ``'random'``;
+    leaves, see below; ``split_rows`` in ``'kmeans'``, ``'random'``, or one of the functions ``gmm`` and ``kmeans`` of
+    ``deeprob.spn.learning.splitting.cluster`` themselves (recognised by identity; ``split_rows_kwargs`` ``{'n': 2}``,
+    1..8): ``gmm`` is the Gaussian-mixture split (full covariances, three initialisations, this project's definition:
+    DESIGN.md 14.5), for discrete and for all-``Gaussian`` columns, with every column split and leaf learner that
+    ``'kmeans'`` works with, and the function ``kmeans`` is the string ``'kmeans'``; the STRING ``'gmm'`` raises;
     ``split_cols`` in ``'gvs'``, ``'rgvs'``, ``'random'``, or the function
     ``deeprob.spn.learning.splitting.rdc.rdc_cols`` itself (recognised by identity): the RDC split as the exact maximal
     correlation, with ``split_cols_kwargs`` in ``d``, ``k``, ``s``; or one of the functions ``entropy_cols``,
@@ -460,7 +482,8 @@ def learn_spn(
     :param distributions: A list of distribution classes of ``deeprob.spn.structure.leaf`` (one for each feature).
     :param domains: A list of domains (one for each feature), each ``list(range(K))`` (``(lo, hi)`` for ``Gaussian``).
     :param learn_leaf: The method to use to learn a distribution leaf node: 'mle' or the function ``learn_binary_clt``.
-    :param split_rows: The rows splitting method: 'kmeans' or 'random'.
+    :param split_rows: The rows splitting method: 'kmeans', 'random', or the function ``gmm`` or ``kmeans`` of
+                       ``deeprob.spn.learning.splitting.cluster``.
     :param split_cols: The columns splitting method: 'gvs', 'rgvs', 'random', the function ``rdc_cols`` or one of the
                        functions ``entropy_cols``, ``entropy_adaptive_cols``, ``gini_cols``, ``gini_adaptive_cols``,
                        ``gvs_cols``, ``rgvs_cols``.
@@ -491,6 +514,7 @@ def learn_spn(
     elif hist_split(split_cols) is not None:
         split_cols = hist_split(split_cols)
     clt = learn_leaf is learn_binary_clt
+    split_rows = rows_split(split_rows) or split_rows      # ('gmm' is reached through the function only: the string has raised)
     dev_data = kind.upload(data)
     device = dev_data.device
     n_total, n_features = dev_data.n_rows, dev_data.n_cols
@@ -500,7 +524,7 @@ def learn_spn(
 
     tmp_node = new_node('Product', range(n_features))
     generation = [_Task(tmp_node, n_total, list(range(n_features)), is_first=True)]
-    tasks_per_generation, lloyd_iterations, clt_records = [], 0, []
+    tasks_per_generation, lloyd_iterations, gmm_iterations, clt_records = [], 0, 0, []
     while generation:
         tasks_per_generation.append(len(generation))
         # ---- column statistics of every task, the operation of every task (learnspn.py:130-147) ----------------------
@@ -529,7 +553,8 @@ def learn_spn(
                 c = int(rows_kw['n'])
                 if t.n < c:
                     raise ValueError("n_samples={} should be >= n_clusters={}".format(t.n, c))
-                t.draw = np.stack([random_state.choice(t.n, c, replace=False) for _ in range(KMEANS_RESTARTS)])
+                t.draw = np.stack([random_state.choice(t.n, c, replace=False)
+                                   for _ in range(L.GMM_N_INIT if split_rows == 'gmm' else KMEANS_RESTARTS)])
             elif t.op == 'cols' and split_cols == 'random':
                 p = random_state.beta(cols_kw['a'], cols_kw['b'])
                 t.draw = random_state.binomial(1, p, size=len(t.scope))
@@ -550,9 +575,15 @@ def learn_spn(
                 clt_records.append({'scope': list(t.scope), 'root': leaf.scope[leaf.root], 'tree': leaf.tree, 'params': leaf.params,
                                     'n': t.n, 'rows': row_index[t.row_off:t.row_off + t.n]})
         # ---- k-means of every row-splitting task ----------------------------------------------------------------------
-        km_tasks = [t for t in generation if t.op == 'rows' and split_rows == 'kmeans']
+        km_tasks = [t for t in generation if t.op == 'rows' and split_rows in ('kmeans', 'gmm')]
         km_labels, km_result = None, {}
-        if km_tasks:
+        if km_tasks and split_rows == 'gmm':
+            batch = kind.gmm_batch(row_index, km_tasks, int(rows_kw['n']))
+            best, _, sizes, km_labels, iters = batch.run()     # the largest bound, the first one on a tie
+            gmm_iterations += iters
+            for i, t in enumerate(km_tasks):
+                km_result[id(t)] = (int(best[i]) * batch.n_lab + batch.lab_off[i], sizes[i, int(best[i])])
+        elif km_tasks:
             batch = kind.kmeans_batch(row_index, km_tasks, int(rows_kw['n']))
             inertia, sizes, km_labels, iters = batch.run()
             lloyd_iterations += iters
@@ -627,7 +658,9 @@ def learn_spn(
     _last_info.update(generations=len(tasks_per_generation), launches=c['kernels'] + c['reads'] + c['uploads'],
                       kernels=c['kernels'], reads=c['reads'], uploads=c['uploads'],
                       lloyd_launches=c['lloyd_kernels'] + c['lloyd_reads'], lloyd_iterations=lloyd_iterations,
-                      tasks_per_generation=tasks_per_generation, clt_leaves=clt_records)
+                      tasks_per_generation=tasks_per_generation, clt_leaves=clt_records,
+                      gmm_kernels=c['gmm_kernels'], gmm_reads=c['gmm_reads'], gmm_uploads=c['gmm_uploads'],
+                      gmm_iterations=gmm_iterations)
     if kind.launches_per_generation is not None:
         _last_info['launches_per_generation'] = kind.launches_per_generation + (CLT_LAUNCHES_PER_GENERATION if clt else 0)
     return to_flat(tmp_node['children'][0])

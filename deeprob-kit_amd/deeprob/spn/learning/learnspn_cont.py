@@ -176,3 +176,6 @@ class GaussianColumns:
     def kmeans_batch(self, row_index, tasks, n_clusters):
         return L.KMeansBatch(self.data, row_index, [(t.row_off, t.n, t.scope, None, t.draw) for t in tasks], KMEANS_RESTARTS,
                              n_clusters)
+
+    def gmm_batch(self, row_index, tasks, n_clusters):
+        return L.GmmBatch(self.data, row_index, [(t.row_off, t.n, t.scope, None, t.draw) for t in tasks], n_clusters)

@@ -73,7 +73,9 @@ class BinaryCLTMixture:
         :param n_components: The number of clusters of the k-means (without ``clusters``).
         :param alpha: The Laplace smoothing factor of the trees.
         :param random_state: None, a seed or a Numpy RandomState: seeds the k-means, then draws every tree's root.
-        :param clusters: Optional int labels ``[N]``: the clusters, instead of the k-means.
+        :param clusters: Optional int labels ``[N]``: the clusters, instead of the k-means.  The seeding of the reference's
+                         ``examples/spn_clt_em.py`` is ``clusters=deeprob.spn.learning.splitting.gmm(data, [Bernoulli] * D,
+                         domain, random_state, n=n_components)``: the Gaussian-mixture row split on the device.
         :return: Itself.
         :raises ValueError: If a parameter is out of domain.
         """

@@ -1,7 +1,8 @@
 /*
  * deeprob_learn.h -- C ABI of libdeeprob_learn.so (gfx950 / MI355X): the device side of LearnSPN
  * (deeprob.spn.learning.learnspn.learn_spn) for discrete data and, in its last section, for continuous
- * (all-Gaussian) data, with the histograms of float columns (the entropy, Gini and G-test column splits there) at the end.
+ * (all-Gaussian) data, with the histograms of float columns (the entropy, Gini and G-test column splits there) and the
+ * Gaussian-mixture row split at the end.
  *
  * The reference is Python on numpy (deeprob/spn/learning/learnspn.py:121-222); the statistics it
  * gathers per task -- column histograms (leaf.py:162, 263; learnspn.py:132), the joint histograms
@@ -25,7 +26,8 @@
  *      tails included);
  *   3. nothing it does depends on what the outputs held on entry, except the arguments documented
  *      as updated in place: `labels` and `changed` of dpl_kmeans_assign, `cent` of
- *      dpl_kmeans_update, and the same three of the dpl_kmeansf_ entries;
+ *      dpl_kmeans_update, the same three of the dpl_kmeansf_ entries, and `resp`, `labels`, `lse` of dpl_gmm_estep (written
+ *      for the listed pairs only);
  *   4. it leaves its `const` inputs alone.
  * There is no workspace.  Index arrays handed in are trusted to lie inside the arrays they index,
  * a value x >= the K stated for its column is not counted.  Counts are exact integers (LDS integer
@@ -323,6 +325,75 @@ int dpl_code_counts(const uint16_t *codes, int64_t n_codes, const int64_t *item_
 int dpl_pair_g_codes(const uint16_t *codes, int64_t n_codes, const int64_t *pair_off_a, const int64_t *pair_off_b,
                      const int32_t *pair_n, const int32_t *pair_bins_a, const int32_t *pair_bins_b, int64_t n_pairs,
                      int max_bins_sum, int max_cells, double *g, void *stream);
+
+/* ==== Gaussian-mixture row splits (splitting/cluster.py:14-38: GaussianMixture(n, n_init=3); this project's definition:
+ * DESIGN.md 14.5) ==================================================================================================
+ * One EM iteration of every listed (task, initialisation) PAIR of a generation: dpl_gmm_estep is the density pass,
+ * dpl_gmm_mstats the weighted moments; the Cholesky factors, their inverses and the M-step arithmetic on the moments are
+ * the host's.  `x` is the uint8 matrix (is_float == 0) or the float32 matrix `xf` (is_float != 0), column major as above.
+ *
+ * FEATURES are those of the k-means above: task t has F = task_f[t] features, feature f reads column
+ * feat_col[task_feat_off[t] + f]; with uint8 data feat_val[same] < 0 takes the column's value itself (a column with K <= 2)
+ * and feat_val = v >= 0 the indicator of value v (one of the K one-hot features of a column with K > 2); with float32 data
+ * feat_val is not read and the feature is the value widened.  Feature values are float64.  The rows of task t are
+ * row_index[task_row_off[t] .. + task_n[t]); row r of task t under initialisation i has its label, lse and
+ * responsibilities at position i * n_lab + task_lab_off[t] + r.
+ *
+ * Pair a is task pair_task[a] under initialisation pair_init[a]; its PARAMETERS are at par[pair_par_off[a] + c * (1 + F +
+ * F * F) ...] for component c < n_comp <= DPL_MAX_CLUSTERS: k_c = log pi_c - 0.5 F log(2 pi) - sum log diag L_c, then
+ * mu_c[F], then W_c = L_c^-1 as an F x F row major matrix whose upper triangle holds 0.0.  A pair that is not listed is not
+ * touched: `resp`, `labels` and `lse` are written for every row of every LISTED pair and are otherwise left alone (they
+ * are outputs updated in place, like `labels` of dpl_kmeans_assign); lse_sum and stats are compact over the listed pairs and
+ * every element of them is written. */
+
+/* E-step.  Block b covers rows block_row0[b] .. + 256 of pair block_pair[b]; the caller lists every 256-row block of every
+ * listed pair.  For a row with features x and each component c, in float64, one operation at a time:
+ *   d_j = x_j - mu_c[j];   y_i = sum_j W_c[i][j] * d_j, from 0.0 over j = 0, 1, ... in order (one multiply, one add per term;
+ *   the terms j > i are products with the stored 0.0, or skipped: whole 32-feature tiles above the diagonal are skipped);
+ *   q = sum_i y_i * y_i from 0.0 in order of i;   lp_c = k_c + (-0.5 * q);
+ * never the expanded form x^T P x - 2 x^T P mu + mu^T P mu.  Then m = the largest lp_c, label = the first c that attains
+ * it, s = sum_c exp(lp_c - m) from 0.0 in order of c, lse = m + log(s), resp_c = exp(lp_c - lse).  W_c is taken through LDS
+ * a 32 x 32 tile at a time and a thread holds the 32 y_i of one tile row: nothing is sized by F, any F is tiled.  Built on the
+ * VALU only (a thread per row, the tile of W_c broadcast from LDS); no matrix-core form was built.
+ * lse_sum[a] = the sum of pair a's lse: 256 partial sums (partial l takes rows l, l + 256, ... in order, from 0.0), added in
+ * order of l (a second kernel over `lse`).  resp: [n_init * n_lab * n_comp] float64; labels: [n_init * n_lab] uint8; lse:
+ * [n_init * n_lab] float64; lse_sum: [n_pairs] float64. */
+int dpl_gmm_estep(const void *x, int is_float, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                  const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_lab_off,
+                  const int32_t *task_feat_off, const int32_t *task_f, const int32_t *feat_col, const int32_t *feat_val,
+                  const int32_t *pair_task, const int32_t *pair_init, const int64_t *pair_par_off, int64_t n_pairs,
+                  const int32_t *block_pair, const int32_t *block_row0, int64_t n_blocks, int n_init, int n_comp,
+                  const double *par, double *resp, uint8_t *labels, double *lse, int64_t n_lab, double *lse_sum,
+                  void *stream);
+
+/* Weighted moments about a PIVOT (built: the one-pass pivoted form, not the two-pass one; never raw moments about the
+ * origin).  For listed pair a and component c, with w_r = resp[(i * n_lab + task_lab_off[t] + r) * n_comp + c], the pivot
+ * p = mu_c of the pair's parameters (par[pair_par_off[a] + c * (1 + F + F * F) + 1 ...]; k_c and W_c are not read) and
+ * a_rf = x_rf - p_f, stats[pair_stat_off[a] + c * (1 + F + F * F) ...] receives
+ *   N = sum_r w_r;   s[f] = sum_r w_r * a_rf;   M[g][f] = sum_r (w_r * a_rf) * a_rg,  F x F row major,
+ * each product formed in that order.  Organised like dpl_rdc_gram, whose tile products, partial layout and group sums
+ * it shares: UNIT u is rows [unit_row0[u], + unit_rows[u]) of pair unit_pair[u], component unit_comp[u], and the 32-feature
+ * tiles at unit_i0[u] <= unit_j0[u]; the weighted factor w_r * a_rf runs over the tile at unit_i0, the plain factor a_rg
+ * over the tile at unit_j0 (both tiles are staged even when they coincide).  A unit adds its rows 32 at a time into
+ * partial[u * DPL_GMM_PARTIAL ...]: the DPL_GRAM_PARTIAL numbers of dpl_rdc_gram (products with use_mfma == 0 on the VALU
+ * row by row, with use_mfma != 0 on v_mfma_f64_16x16x4_f64 in blocks of 4 rows; the sums s of the tile at unit_i0 row by
+ * row) and then the sum of w_r row by row.  GROUP g adds the partials of its units group_unit0[g] .. + group_units[g] in
+ * that order and writes M[g'][f'] for f' in the tile at i0 and g' in the tile at j0 and, when the tiles differ, the same
+ * number at M[f'][g']; the group with i0 == j0 also writes s over its tile, and the one with i0 == j0 == 0 writes N.  The
+ * caller lists every tile pair i0 <= j0 of every component of every listed pair, so every element of stats is written.  In
+ * a diagonal tile M[g][f] and M[f][g] differ in the rounding of the weighted factor: the host reads the LOWER triangle
+ * (g >= f), where the weighted factor is the one of the lower index.  partial: [n_units * DPL_GMM_PARTIAL] float64, scratch
+ * like that of dpl_rdc_gram, kept under 256 MiB by splitting the groups over several calls. */
+#define DPL_GMM_PARTIAL 1064 /* DPL_GRAM_PARTIAL + 1, rounded up to a multiple of 8 */
+int dpl_gmm_mstats(const void *x, int is_float, int64_t n_rows, int n_cols, const int32_t *row_index, int64_t n_index,
+                   const int64_t *task_row_off, const int32_t *task_n, const int64_t *task_lab_off,
+                   const int32_t *task_feat_off, const int32_t *task_f, const int32_t *feat_col, const int32_t *feat_val,
+                   const int32_t *pair_task, const int32_t *pair_init, const int64_t *pair_par_off,
+                   const int64_t *pair_stat_off, int64_t n_pairs, const int32_t *unit_pair, const int32_t *unit_comp,
+                   const int32_t *unit_i0, const int32_t *unit_j0, const int32_t *unit_row0, const int32_t *unit_rows,
+                   int64_t n_units, const int32_t *group_unit0, const int32_t *group_units, int64_t n_groups, int n_comp,
+                   const double *par, const double *resp, int64_t n_lab, int use_mfma, double *partial, double *stats,
+                   void *stream);
 
 #ifdef __cplusplus
 }
