@@ -104,6 +104,33 @@ __device__ __forceinline__ void split8(const float (&v)[8], half8 &xh, half8 &xl
     }
 }
 
+// split8 for the slice kernel's K-step (ratspn_gemm_slice.hip), same bits: the low half's x - float(xh) is ONE
+// v_fma_mix_f32 per value -- the f16 half of the packed high pair (op_sel picks it, op_sel_hi marks the source as f16),
+// times -1.0, plus x; the product is exact and the sum rounds once, like the subtraction -- where the plain form spends a
+// v_cvt_f32_f16 and a subtract: 8 vector instructions fewer per K-step.  hipcc does not select the instruction from C++
+// (DESIGN 3.3), hence asm; what the comment above split8 warns of is kept away from: the statement reads the compiler's own
+// v_cvt_pk_f16_f32 result (a whole-register VALU write, interlocked like any other) and its result goes through the
+// compiler's packed conversion -- an ordinary VALU read -- never into an MFMA operand: the high and the low halves the
+// MFMAs read are both written by instructions the hazard recognizer sees.
+__device__ __forceinline__ void split8_mix(const float (&v)[8], half8 &xh, half8 &xl) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const gf32x2 a = {v[2 * p], v[2 * p + 1]};
+        const half2 h = __builtin_convertvector(a, half2);
+        const unsigned hb = __builtin_bit_cast(unsigned, h);
+        gf32x2 d;
+        float d0, d1;
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d0) : "v"(hb), "v"(a[0]));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d1) : "v"(hb), "v"(a[1]));
+        d[0] = d0;
+        d[1] = d1;
+        const half2 l = __builtin_convertvector(d, half2);
+        xh[2 * p] = h[0];
+        xh[2 * p + 1] = h[1];
+        xl[2 * p] = l[0];
+        xl[2 * p + 1] = l[1];
+    }
+}
 
 // The loader waves' side of the LDS ring (see ratspn_gemm.hip "Mapping"): wave `wave` (0..3) copies, for every chunk of
 // every tile of this work-group, the KC = 16*KS features of its 32 rows of x (XOR-swizzled 16-byte pieces) and PB

@@ -40,6 +40,7 @@
 // Results agree with the other two mappings to fp32 rounding, not bit for bit (seven partial sums in a fixed order).
 #include "ratspn_gemm_fused.h"
 #include "ratspn_gemm_prep.h"
+#include "ratspn_slice_lanes.h"
 #include "../../include/deeprob_slice.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -531,7 +532,7 @@ __global__ __launch_bounds__(kSliceThreads) void ratspn_gemm_slice_kernel(const 
             tq2 = __builtin_elementwise_fma(pv, pv, tq2);                                                                     \
         }                                                                                                                     \
         half8 xh, xl;                                                                                                         \
-        split8(v, xh, xl);                                                                                                    \
+        split8_mix(v, xh, xl);                                                                                                \
         _Pragma("unroll") for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(mh[kk][t], xh, acc[t], 0, 0, 0); \
         _Pragma("unroll") for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(mh[kk][t], xl, acc[t], 0, 0, 0); \
         _Pragma("unroll") for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ml[kk][t], xh, acc[t], 0, 0, 0); \
@@ -896,6 +897,7 @@ constexpr int kSliceLanesMax = DPS_LANES_MAX;        // (the flag field's four b
 constexpr int kSliceAutoLanesMax = DPS_AUTO_LANES_MAX;     // auto mode: 1 + busy peers, at most this
 constexpr int kSliceAutoStreak = DPS_AUTO_STREAK;       // ... and only once the peers were busy at this many consecutive launches of the workspace
 constexpr int kSliceAutoRecheck = DPS_AUTO_RECHECK;   // a lane that shares looks at its peers again at every this-many-th launch
+constexpr int kSliceAutoReentry = DPS_AUTO_REENTRY;   // a lane that was sharing when its peers fell idle shares again at once if they are busy within this many launches
 constexpr int kSlicePeers = 8;            // workspaces remembered per device
 constexpr int kSliceDevices = 64;
 static int slice_lanes_initial() {
@@ -907,6 +909,14 @@ static std::atomic<int> &slice_lanes_ref() {
     static std::atomic<int> v{slice_lanes_initial()};
     return v;
 }
+// (measurement: DPK_SLICE_REENTRY in the environment, read once, replaces DPS_AUTO_REENTRY; 0 = no re-entry)
+static int slice_reentry() {
+    static const int v = [] {
+        const char *e = getenv("DPK_SLICE_REENTRY");
+        return e ? std::max(0, atoi(e)) : kSliceAutoReentry;
+    }();
+    return v;
+}
 static std::atomic<int> g_slice_last_grid{0}, g_slice_last_lanes{0};
 
 // Auto mode (eager launches that state nothing).  Per device, the stream of each workspace's last eager slice launch.  At a
@@ -914,14 +924,15 @@ static std::atomic<int> g_slice_last_grid{0}, g_slice_last_lanes{0};
 // when hipStreamQuery on its stream says "not ready".  W takes a share (1 + busy peers) only after its peers were busy at
 // kSliceAutoStreak consecutive launches of W, and goes back to the whole chip at the first launch that finds them idle: two
 // batches on two streams, a lone stream and a synchronised caller all keep the whole chip; a sustained loop over two streams
-// settles at cus / 2 per launch.  What this cannot see: a lane that shares beside a peer whose launches are much shorter
-// gives compute units away -- the hysteresis and the override are for that.
+// settles at cus / 2 per launch.  A loop that synchronises now and then is still that loop: a workspace that was sharing when
+// a look found its peers idle takes its share again at the first look, within kSliceAutoReentry launches, that finds them
+// busy (the decision itself: slice_lanes_next, ratspn_slice_lanes.h).  What this cannot see: a lane that shares beside a
+// peer whose launches are much shorter gives compute units away -- the hysteresis and the override are for that.
 namespace {
 struct SlicePeer {
     const void *ws;
     hipStream_t st;
-    int streak;              // consecutive looks that found a peer busy
-    int lanes;               // what the last look decided
+    SliceLaneState look;     // streak, lanes and what re-entry remembers: the outcome of the last look
     int since;               // launches since the last look
     unsigned long long seq;
 };
@@ -958,10 +969,10 @@ static int slice_lanes_auto(const void *ws_key, hipStream_t st) {
     // behind every launch of the peer cost the two-stream loop 1.3 us per step (41.8 against 40.5 with the lane count
     // fixed at 2, same process).  An idle stream gets no marker: a lane that has the chip to itself looks at every launch.
     for (SlicePeer &e : v)
-        if (e.ws == ws_key && e.st == st && e.lanes > 1 && e.since + 1 < kSliceAutoRecheck) {
+        if (e.ws == ws_key && e.st == st && e.look.lanes > 1 && e.since + 1 < kSliceAutoRecheck) {
             ++e.since;
             e.seq = ++r.seq;
-            return e.lanes;
+            return e.look.lanes;
         }
     int busy = 0;
     for (size_t i = 0; i < v.size();) {
@@ -992,16 +1003,15 @@ static int slice_lanes_auto(const void *ws_key, hipStream_t st) {
             v[old] = v.back();
             v.pop_back();
         }
-        v.push_back(SlicePeer{ws_key, st, 0, 1, 0, 0ull});
+        v.push_back(SlicePeer{ws_key, st, SliceLaneState{0, 1, 0, 0}, 0, 0ull});
         me = v.size() - 1;
     }
     SlicePeer &m = v[me];
     m.st = st;
     m.seq = ++r.seq;
-    m.streak = busy > 0 ? std::min(m.streak + 1, kSliceAutoStreak) : 0;
-    m.lanes = m.streak >= kSliceAutoStreak ? std::min(1 + busy, kSliceAutoLanesMax) : 1;
+    m.look = slice_lanes_next(m.look, busy, kSliceAutoStreak, kSliceAutoLanesMax, slice_reentry());
     m.since = 0;
-    return m.lanes;
+    return m.look.lanes;
 }
 
 // The lane count of the slice launch of workspace `ws_key` on `st`.  Inside a stream capture nothing is queried: the stated

@@ -12,7 +12,9 @@
  *   - else, for an eager launch, 1 + the other workspaces whose last slice launch went to another stream that is still busy
  *     (hipStreamQuery), at most 4, and only once that was so at 4 consecutive launches of the workspace; back to 1 at the
  *     first launch that finds them idle.  A lane that shares looks only at every 8th launch (the query puts a marker into
- *     the stream it asks about: not free for a busy peer), so it can run up to 7 launches on its share beside idle peers;
+ *     the stream it asks about: not free for a busy peer), so it can run up to 7 launches on its share beside idle peers.
+ *     A workspace that was sharing when a look found its peers idle (the caller synchronised) returns to the lane count
+ *     it had at the first look within DPS_AUTO_REENTRY of its launches that finds them busy again: no second streak;
  *   - else (a launch under stream capture: nothing is queried) 1.
  * Per-sample results do not depend on the lane count, bit for bit.
  */
@@ -29,6 +31,7 @@ extern "C" {
 #define DPS_AUTO_LANES_MAX 4 /* most lanes auto mode settles at                                 */
 #define DPS_AUTO_STREAK 4    /* consecutive launches with busy peers before auto mode shares    */
 #define DPS_AUTO_RECHECK 8   /* a lane that shares looks at its peers at every 8th launch only  */
+#define DPS_AUTO_REENTRY 8   /* ... and one that shared when they fell idle: again, if busy in this many */
 
 /* Work-groups of a slice launch over `ntiles` blocks of 32 samples on a device of `cus` compute units, run on `lanes`
  * lanes, whose first `np` work-groups carry the in-launch table check (0: none).  Pure arithmetic.

@@ -33,7 +33,7 @@ def summary(v):
             'runs': [round(t, 5) for t in v]}
 
 
-def eager_two_streams(model, xs, rounds, steps, settings, sl):
+def eager_two_streams(model, xs, rounds, steps, settings, sl, sync_every=0):
     from deeprob.parallel import ShardedLogLikelihood
     dev = xs[0].device
     replicas = [model, copy.deepcopy(model)]
@@ -49,6 +49,8 @@ def eager_two_streams(model, xs, rounds, steps, settings, sl):
             if count is not None:
                 g = sl.last_grid()
                 count[g] = count.get(g, 0) + 1
+            if sync_every and (i + 1) % sync_every == 0:      # (a caller that synchronises now and then: DPS_AUTO_REENTRY)
+                torch.cuda.synchronize()
 
     def drain():
         torch.cuda.synchronize()
@@ -73,7 +75,8 @@ def eager_two_streams(model, xs, rounds, steps, settings, sl):
     sl.lanes(0)
     ref = means[settings[0]]
     assert all(abs(m - ref) <= 1e-9 * abs(ref) for m in means.values()), means
-    return {'case': 'eager two streams', 'B': xs[0].shape[0], 'steps': steps,
+    return {'case': 'eager two streams', 'B': xs[0].shape[0], 'steps': steps, 'sync_every': sync_every,
+            'reentry': os.environ.get('DPK_SLICE_REENTRY', 'DPS_AUTO_REENTRY'),
             'ms_per_step': {str(s): dict(summary(v), grids=grids[s]) for s, v in out.items()}}
 
 
@@ -118,6 +121,7 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--fixed', type=int, default=0, help='also measure this fixed lane count in the eager loop (0: no)')
     ap.add_argument('--no-window', action='store_true')
+    ap.add_argument('--sync-every', type=int, default=0, help='synchronise after every this many steps of the eager loop (0: never)')
     ap.add_argument('--window-lanes', type=int, nargs='*', default=[], help='further fixed lane counts for the windows')
     args = ap.parse_args()
     from deeprob.hip import slice as sl
@@ -128,7 +132,7 @@ def main():
     with torch.no_grad():
         xs = [torch.randn(65536, D, device=dev) for _ in range(4)]
         settings = [1, 0] + ([args.fixed] if args.fixed > 1 else [])
-        print(json.dumps(eager_two_streams(model, xs, args.rounds, args.steps, settings, sl)), flush=True)
+        print(json.dumps(eager_two_streams(model, xs, args.rounds, args.steps, settings, sl, args.sync_every)), flush=True)
         for B in (() if args.no_window else (65536, 32768, 16384, 8192)):
             nb = max(2, -(-(320 << 20) // (B * D * 4)))
             xb = xs[:nb] if B == 65536 else [torch.randn(B, D, device=dev) for _ in range(nb)]
