@@ -155,7 +155,7 @@ extern "C" {
 
 const char *dpc_last_error(void) { return dpc_detail::g_error; }
 
-int dpc_abi_version(void) { return 5; }
+int dpc_abi_version(void) { return 6; }
 
 int dpc_pack_bits(const float *x, int64_t n, int d, uint64_t *planes, void *stream) {
     DPC_REQUIRE(d >= 1 && d <= DPC_MAX_D, "dpc_pack_bits: d = %d is outside 1..%d", d, DPC_MAX_D);

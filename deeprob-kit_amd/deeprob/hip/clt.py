@@ -49,7 +49,8 @@ def rows_on_device(x, name: str) -> torch.Tensor:
 def run_on_device(model, name: str, op, x, *args):
     """``op(model._on_device(device), x on the device, *args)`` under the input rules of ``BinaryCLT`` and ``BinaryCNet``
     (``model``: one of them, ``name``: what it calls itself in a message): numpy in, numpy out through the current device;
-    a device tensor stays on its device; a CPU tensor or a missing library raises ``HipError``."""
+    a device tensor stays on its device; a CPU tensor or a missing library raises ``HipError``.  An ``op`` that returns a
+    tuple of tensors gives a tuple."""
     load_library()
     as_numpy = not isinstance(x, torch.Tensor)
     if as_numpy:
@@ -63,7 +64,9 @@ def run_on_device(model, name: str, op, x, *args):
     if x.dim() != 2 or x.shape[1] != len(model.scope):
         raise ValueError("expected inputs [B, {}], got {}".format(len(model.scope), tuple(x.shape)))
     out = op(model._on_device(x.device), x, *args)
-    return out.cpu().numpy() if as_numpy else out
+    if not as_numpy:
+        return out
+    return tuple(o.cpu().numpy() for o in out) if isinstance(out, tuple) else out.cpu().numpy()
 
 
 def children_csr(bfs, parent):
@@ -325,3 +328,76 @@ def mixture_em_stats(mix: DeviceMixture, codes: torch.Tensor, rows, resp: torch.
     call(lib.dpc_mix_em_stats, codes.data_ptr(), b, mix.d, rows_ptr, nb, mix.k, resp.data_ptr(), mix.parent.data_ptr(),
          part.data_ptr(), stats.data_ptr(), hip.stream_ptr(dev))
     return stats
+
+
+# ---- posterior queries of a mixture (the dpc_mixq_* section of the header) -------------------------------------------------
+#: the ``dpc_abi_version()`` that has the ``dpc_mixq_*`` entry points
+MIXQ_ABI_VERSION = 6
+
+
+def _mixq_library():
+    lib = load_library()
+    version = lib.dpc_abi_version()
+    if version < MIXQ_ABI_VERSION:
+        raise HipError("libdeeprob_clt.so at {} has ABI version {}, the posterior queries of a mixture of trees need {} -- "
+                       "rebuild it with `make -C deeprob-kit_amd/csrc` (or __graft_entry__.build())".format(
+                           BINDING.lib_path, version, MIXQ_ABI_VERSION))
+    return lib
+
+
+def mixture_query_row_bytes(mix: DeviceMixture, what: str) -> int:
+    """Bytes of scratch per row of ``dpc_mixq_marginals`` (``what == 'marginals'``) or of the two fills: the header's
+    ``16 D + 8 K`` and ``8 D + 8 K``."""
+    return (16 if what == 'marginals' else 8) * mix.d + 8 * mix.k
+
+
+def _mixture_query(mix: DeviceMixture, x: torch.Tensor, what: str, seed: int = 0, row0: int = 0, want_component: bool = False):
+    lib = _mixq_library()
+    x = _rows(x, 'x')
+    if x.shape[1] != mix.d:
+        raise ValueError("expected inputs [B, {}], got {}".format(mix.d, tuple(x.shape)))
+    if x.device != mix.device:
+        raise HipError("x lives on '{}', the mixture on '{}'".format(x.device, mix.device))
+    b, d = x.shape
+    st = hip.stream_ptr(x.device)
+    out = torch.empty((b, d), dtype=torch.float32, device=x.device)
+    component = torch.empty(b, dtype=torch.int32, device=x.device) if want_component else None
+    step = query_rows(d)        # the piece of `marginals`
+    # (float64: the allocator then gives the 8-byte alignment the entry points ask for)
+    work = torch.empty(mixture_query_row_bytes(mix, what) * min(b, step) // 8, dtype=torch.float64, device=x.device)
+    for r0 in range(0, b, step):
+        xs, os_ = x[r0:r0 + step], out[r0:r0 + step]
+        n = xs.shape[0]
+        codes = pack_query(xs)
+        head = (xs.data_ptr(), codes.data_ptr(), n, d, mix.k) + mix.pointers()
+        comp = component[r0:r0 + step].data_ptr() if want_component else None
+        if what == 'marginals':
+            call(lib.dpc_mixq_marginals, *head, work.data_ptr(), os_.data_ptr(), st)
+        elif what == 'mpe':
+            call(lib.dpc_mixq_mpe, *head, work.data_ptr(), os_.data_ptr(), comp, st)
+        else:
+            call(lib.dpc_mixq_sample, *head, seed, row0 + r0, work.data_ptr(), os_.data_ptr(), comp, st)
+    return (out, component) if want_component else out
+
+
+def mixture_marginals(mix: DeviceMixture, x: torch.Tensor) -> torch.Tensor:
+    """``[B, D]`` float32: ``x`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)`` under the
+    mixture, exact (``dpc_mixq_marginals``); NaN where the evidence is impossible under every component."""
+    return _mixture_query(mix, x, 'marginals')
+
+
+def mixture_sample(mix: DeviceMixture, x: torch.Tensor, seed: int, row0: int = 0, want_component: bool = False):
+    """``[B, D]`` float32: ``x`` with its NaN entries drawn given the observed ones (``dpc_mixq_sample``): first the
+    component from its posterior, then the entries from that tree.  ``row0``: the number of the first row in the generator's
+    counters (a batch sampled in pieces gives the bytes of the whole).  With ``want_component`` also ``[B]`` int32, the
+    drawn component (-1 where the evidence is impossible; such a row keeps its NaN)."""
+    if row0 < 0:
+        raise ValueError("row0 must not be negative")
+    return _mixture_query(mix, x, 'sample', int(seed) & 0xFFFFFFFFFFFFFFFF, int(row0), want_component)
+
+
+def mixture_mpe(mix: DeviceMixture, x: torch.Tensor, want_component: bool = False):
+    """``[B, D]`` float32: ``x`` with its NaN entries filled by the completion of the pair (component, completion) that
+    maximises ``w_k p_k(x)`` (``dpc_mixq_mpe``): the max-product MPE of the mixture's circuit, not the MAP of the mixture
+    density.  With ``want_component`` also ``[B]`` int32, the winning component (-1 where the evidence is impossible)."""
+    return _mixture_query(mix, x, 'mpe', want_component=want_component)

@@ -2,7 +2,14 @@
 reference's examples/spn_clt_em.py -- as one object, evaluated and trained on the HIP device through the ``dpc_mix_*`` entry
 points of ``libdeeprob_clt.so`` (include/deeprob_clt.h, last section).  ``FlatSpn`` has no multivariate leaf, so the model
 cannot be a node graph here; ``to_pc()`` gives the equivalent ``FlatSpn`` (a Sum over the trees' circuits), through which
-``mpe``, ``sample``, the posterior marginals and the moments of ``deeprob.spn.algorithms`` are reached.
+the node-graph algorithms of ``deeprob.spn.algorithms`` (the moments, for one) are reached.
+
+The posterior queries are the model's own: ``marginals``, ``sample`` and ``mpe`` are one launch each (``dpc_mixq_*``,
+DESIGN.md 15.2) that visits the trees one at a time -- ``2 D`` floats and ``D + K`` doubles of scratch per row, where the
+circuit of ``to_pc()`` keeps a value per node and row.  ``mpe`` maximises ``w_k p_k(x)`` over the completions AND the
+components (the max-product MPE of the circuit); it is not the MAP of the mixture density ``sum_k w_k p_k(x)``, which is
+NP-hard, and ``algorithms.mpe(mix.to_pc(), x)`` follows the reference's rule (the values of the sum pass choose the branch)
+and need not agree with it.
 
 ``em`` is the reference's batch EM (learning/em.py:18-113) for this shape, with the CPTs of every tree TIED as
 ``BinaryCLT.em_step`` ties them (cltree.py:127-155) and the mixture weights updated as ``Sum.em_step`` does
@@ -247,6 +254,34 @@ class BinaryCLTMixture:
         zero for a row that is impossible under every component)."""
         from deeprob.hip import clt
         return self._run(lambda mix, xd: clt.mixture_log_likelihood(mix, xd, want_resp=True)[2], x)
+
+    def marginals(self, x):
+        """A copy of ``x`` ``[B, D]`` with every NaN entry replaced by ``p(x_j = 1 | the row's observed entries)`` under the
+        mixture, exact: the trees' posterior marginals weighted by the posterior of the components.  Observed entries come
+        back bit for bit; an all-NaN row gives the prior marginals; a row whose evidence is impossible under every component
+        gets NaN in its unobserved entries."""
+        from deeprob.hip import clt
+        return self._run(clt.mixture_marginals, x)
+
+    def sample(self, x, seed: Optional[int] = None, return_component: bool = False):
+        """A copy of ``x`` with every NaN entry drawn given the observed entries: the component from its posterior, then the
+        entries from that tree.  ``seed``: the seed of the counter-based generator (the same seed gives the same bytes); None
+        draws one from numpy's global generator.  With ``return_component`` also ``[B]`` int32, the drawn component -- for a
+        complete row a posterior draw of its cluster; -1 (and the row's NaN left in place) where the evidence is impossible
+        under every component."""
+        from deeprob.hip import clt
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        return self._run(clt.mixture_sample, x, int(seed), 0, bool(return_component))
+
+    def mpe(self, x, return_component: bool = False):
+        """A copy of ``x`` with every NaN entry filled by the completion of the pair (component, completion) that maximises
+        ``w_k p_k(x)`` given the observed entries: the max-product MPE of the mixture's circuit.  It is NOT the MAP of the
+        mixture density ``sum_k w_k p_k(x)`` (NP-hard), and ``algorithms.mpe(self.to_pc(), x)``, which follows the
+        reference's rule, need not agree with it.  With ``return_component`` also ``[B]`` int32, the winning component (-1,
+        and the row's NaN left in place, where the evidence is impossible under every component)."""
+        from deeprob.hip import clt
+        return self._run(clt.mixture_mpe, x, bool(return_component))
 
     # ---- parameters and structure ------------------------------------------------------------------------------------
     def params_count(self) -> int:

@@ -369,6 +369,57 @@ int dpc_mix_log_likelihood(const uint8_t *codes, int64_t b, int d, const int32_t
 int dpc_mix_em_stats(const uint8_t *codes, int64_t b, int d, const int32_t *rows, int64_t nb, int n_comp,
                      const float *resp, const int32_t *parent, double *part, double *stats, void *stream);
 
+/* ---- Posterior queries of a mixture of Chow-Liu trees (BinaryCLTMixture.marginals / sample / mpe): posterior marginals,
+ * conditional sampling and max-product MPE, one launch each.  ABI version 6.
+ *
+ * x: [b, d] float32 row major, NaN = unknown; codes: the output of dpc_pack_query for the same rows.  The model is the
+ * stacked tables of dpc_mix_log_likelihood (trusted) and logw [n_comp] float32 (-inf allowed); n_comp <= DPC_MIX_MAX_K,
+ * d <= DPC_MAX_D.  out: [b, d] float32: an observed entry comes back bit for bit.  b = 0 writes nothing.
+ *
+ * The mixture level, common to the three, is float64:
+ *   a_k  = (double)logw[k] + (double)V_k;   M = max over k of a_k;
+ *   S    = the sum over k INCREASING FROM 0.0 of exp(a_k - M);   T = M + log(S);   pi_k = exp(a_k - T).
+ * V_k is the float32 value of tree k on the row.  For the marginals and for sampling it is the value
+ * dpc_clt_log_likelihood gives: the float64 gather for a row without NaN, the upward pass with R = lse otherwise.  For
+ * MPE it is the same with R = max.  pi_k is the posterior probability of component k given the row's observed entries.
+ * The trees are visited one at a time, in increasing k, through ONE [2 * d] float32 message table per row; a tree that is
+ * needed again is passed again, so that the scratch does not grow with n_comp * d.
+ * work is scratch, 8-byte aligned: b * (16 * d + 8 * n_comp) bytes for the marginals (per row the 2 * d floats of the
+ * messages, d float64 accumulators and the n_comp values a_k), b * (8 * d + 8 * n_comp) bytes for the two fills (the
+ * messages and the a_k).
+ *
+ * dpc_mixq_marginals.  A row without NaN is a copy.  Otherwise the accumulators of the row start at 0.0 and, for k
+ * increasing, every component with pi_k > 0 runs the two passes of dpc_mar_clt (the same expressions in the same order)
+ * and adds pi_k * (double)expf(b_j[1]) to the accumulator of every NaN entry j; the entry becomes its accumulator rounded to
+ * float32.  M = -inf (the evidence is impossible under every component, or every weight is zero): NaN in the NaN entries.
+ * With n_comp = 1 and M finite, pi_0 = 1 exactly and the result is that of dpc_mar_clt bit for bit. */
+int dpc_mixq_marginals(const float *x, const uint8_t *codes, int64_t b, int d, int n_comp, const int32_t *bfs,
+                       const int32_t *parent, const float *params, const int32_t *child_off, const int32_t *child_idx,
+                       const float *logw, void *work, float *out, void *stream);
+
+/* dpc_mixq_sample: an exact draw of (component, the NaN entries) given the observed entries.  u(i) = the generator of
+ * dpc_clt_sample with ctr = (row0 + r) * (1 + d) + i, so that a row's output depends only on (seed, row0 + r, the row);
+ * `row0` lets a caller sample a long batch in pieces.  The component is the smallest k with (double)u(0) < c_k, c_k the
+ * running sum pi_0 + ... + pi_k added in increasing k from 0.0; if rounding leaves none, the largest k with pi_k > 0.
+ * Then tree k's upward pass (R = lse) is run again and its NaN columns are filled in `bfs` order by the rule of
+ * dpc_cnq_sample: for position j with parent value xp (row 0 at the root), a_v = params[j][xp][v] + m_j[v] in float32 and
+ * the entry is 1 iff u(1 + j) < expf(a_1 - lse(a_0, a_1)): the normalised conditional (NOT the expression of
+ * dpc_clt_sample).  A row without NaN is a copy, and its component is still drawn: a posterior draw of the row's
+ * cluster.  M = -inf: the NaN entries stay NaN and component[r] = -1.  component: [b] int32 or null. */
+int dpc_mixq_sample(const float *x, const uint8_t *codes, int64_t b, int d, int n_comp, const int32_t *bfs,
+                    const int32_t *parent, const float *params, const int32_t *child_off, const int32_t *child_idx,
+                    const float *logw, uint64_t seed, int64_t row0, void *work, float *out, int32_t *component, void *stream);
+
+/* dpc_mixq_mpe: the (component, completion) that maximises logw[k] + log p_k(x) over the completions of the row AND the
+ * components -- the max-product MPE of the mixture's circuit.  (It is NOT the MAP of the mixture density, the completion
+ * that maximises the SUM over k, which is NP-hard.)  The component is the smallest k that attains max over k of a_k (V_k
+ * with R = max); tree k's upward pass (R = max) is run again and its NaN columns are filled in `bfs` order by the rule of
+ * dpc_clt_mpe: 1 iff a_1 > a_0.  With n_comp = 1 and M finite the result is that of dpc_clt_mpe bit for bit.  M = -inf: the
+ * NaN entries stay NaN and component[r] = -1.  component: [b] int32 or null. */
+int dpc_mixq_mpe(const float *x, const uint8_t *codes, int64_t b, int d, int n_comp, const int32_t *bfs, const int32_t *parent,
+                 const float *params, const int32_t *child_off, const int32_t *child_idx, const float *logw, void *work,
+                 float *out, int32_t *component, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
